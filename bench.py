@@ -19,9 +19,17 @@ Other workloads (BASELINE.json configs[2..4]):
     --compute-dtype bf16 --graph --rays-per-gpu 4096 | 40000
                                         configs[4]: bf16 MLP + fp32 composite, render+loss+backward replayed as one hipGraph
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` for the dominant kernel and
-`cpu_baseline` (the pure-PyTorch CPU port of the same render step, oracle/torch_port.py, on a bounded sample).
-The GPU leg is printed to stderr as soon as it is done; the CPU leg runs after it, inside a hard time budget.
+Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` for the dominant kernel (from the HIP
+events of the timed steps themselves).  A plain run does nothing else: set-up, warm-up, the timed steps, the outputs
+(--dump-outputs) and the line.  --full adds the checks that run after the timed region: `psnr_vs_oracle_db` (the final
+parameters rendered against the fp32 CPU oracle pipeline) and `cpu_baseline` (the pure-PyTorch CPU port of the same render
+step, oracle/torch_port.py, on a bounded sample).  The GPU leg is printed to stderr as soon as it is done; the CPU leg runs
+after it, inside a hard time budget.
+
+--dump-outputs DIR writes what the last timed step computed, as float32 / float64 .npy files (at most 64 MB in all): the
+loss as the step returns it, the rendered pixels of the step (eager steps; a captured step returns its loss only), its
+emitted-sample count, and the parameters after its optimiser step (the MLP block whole, a fixed seeded sample of the hash
+tables).  Inputs depend on the arguments alone (--seed), so two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -68,8 +76,12 @@ def parse():
                          "the first 256 steps, full updates (C x H^3 queries)")
     ap.add_argument('--sort-samples', choices=['auto', 'on', 'off'], default='auto',
                     help="spatially ordered table scatter in the backward (nsr_sample_order): 'auto' = batches of >= 90 000 rays, dense pixel sets from 16 384")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--psnr-rays', type=int, default=4096, help='rays of the PSNR-vs-oracle check after the timed region (0: skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run the PSNR-vs-oracle check and the CPU baseline (a plain run only times the steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave the CPU baseline out')
+    ap.add_argument('--psnr-rays', type=int, default=4096, help='--full: rays of the PSNR-vs-oracle check after the timed region (0: skip)')
     ap.add_argument('--no-loss-scaler', action='store_true', help='constant loss scale, no inf/nan check (round 2 behaviour)')
     ap.add_argument('--style-backprop', choices=['resident', 'deferred'], default='resident',
                     help="style stage: 'resident' = ONE render of the frame with autograd, activations kept in HBM, d loss / d rgb "
@@ -83,7 +95,10 @@ def parse():
     ap.add_argument('--cpu-budget-s', type=float, default=12.0)
     ap.add_argument('--max-steps', type=int, default=None, help='march steps per ray (1024; README stylisation command: 512)')
     ap.add_argument('--seed', type=int, default=69420)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -274,6 +289,44 @@ def psnr_vs_oracle(r, poses_np, intr, nc, n_rays):
                          'oracle pipeline on the same parameters, pose 0, fixed pixels; computed after the timed region'}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+DUMP_TABLE_SAMPLE = 1 << 22          # hash-table entries of the parameter dump (16.8 MB of the 100.9 MB arena)
+DUMP_ROWS_BYTES = 40 * 1000 * 1000   # per-pixel outputs beyond this are dumped as a fixed seeded sample of rows
+
+
+def _seeded_rows(n, k, seed):
+    """k of n row indices, sorted, the same for every run with the same (n, k, seed)"""
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(dirname, model, loss, samples=None, pixels=None):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy in float32 (float64 for the scalars).
+    pixels = {name: per-pixel tensor of the step} (rows in the step's pixel order); model = the parameters after the step."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {'loss': np.asarray([float(loss)], np.float64)}
+    if samples is not None:
+        out['samples'] = np.asarray([float(samples)], np.float64)
+    pixels = {k: v.detach().float().reshape(v.shape[0], -1) for k, v in (pixels or {}).items()}
+    row_bytes = sum(4 * v.shape[1] for v in pixels.values())
+    for name, v in pixels.items():
+        n = v.shape[0]
+        if n * row_bytes > DUMP_ROWS_BYTES:
+            rows = torch.from_numpy(_seeded_rows(n, DUMP_ROWS_BYTES // row_bytes, 1)).to(v.device)
+            v = v.index_select(0, rows)
+            name += '_rows_sample'
+        out[name] = v.cpu().numpy()
+    arena = model.arena.detach()
+    te = int(model.table_elems)
+    out['params_mlp'] = arena[te:].float().cpu().numpy()
+    idx = torch.from_numpy(_seeded_rows(te, min(te, DUMP_TABLE_SAMPLE), 2)).to(arena.device)
+    out['params_table_sample'] = arena.index_select(0, idx).float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, 'output dump of {} bytes exceeds {}'.format(total, DUMP_LIMIT_BYTES)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    return sorted(out)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and 'RANK' not in os.environ:
@@ -299,7 +352,7 @@ def main():
         result['rccl_ranks'] = dist.get_world_size() if dist.is_initialized() else 1
         result['dist_backend'] = dist.get_backend() if dist.is_initialized() else 'none (single process)'
         print('[bench] gpu leg done: ' + json.dumps(result), file=sys.stderr, flush=True)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(args.cpu_budget_s, args.num_classes)
         print(json.dumps(result), flush=True)
     P.barrier()
@@ -395,6 +448,7 @@ def run_recon(args, dev, rank, world):
     side_stream = torch.cuda.Stream(device=dev) if (world == 1 and not args.graph and side_on) else None
     last_it = args.warmup + args.steps - 1
     stage = [None, None]
+    last_out = {}
 
     def inputs(it):
         # (two entries are kept: the captured step with prefetch is told the NEXT step's pose and pixels, and recognises them
@@ -431,6 +485,9 @@ def run_recon(args, dev, rank, world):
             loss = loss_fn(out, pix)
             if loss.requires_grad:         # the sparsity term; the reconstruction loss has back-propagated itself
                 loss.backward()
+            if it == last_it and args.dump_outputs:
+                # --dump-outputs: the last step's pixels (detached: the autograd graph of the render is not kept alive)
+                last_out.update({k: out[k].detach() for k in ('rgb_map', 'trans_map', 'classes') if torch.is_tensor(out.get(k))})
             if side_stream is not None and it < last_it and not r.occupancy_update_due():
                 # the next step's ray generation + march + compaction + sample sort, on the side stream, beside this step's
                 # backward (Renderer.begin_train_on)
@@ -571,8 +628,10 @@ def run_recon(args, dev, rank, world):
                     'avg_launch_ms': round(ms, 4), 'algorithmic_bytes_per_sample': bytes_per_sample['field_fwd'] + bytes_per_sample['field_bwd'],
                     'samples_per_launch': int(samples / args.steps),
                     'note': 'small-batch steps are launch/latency-bound, not bandwidth-bound; per-kernel split in profiles/'}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, loss, int(timed_counts[-1]), last_out)
     psnr = {}
-    if args.psnr_rays > 0 and world == 1:
+    if args.full and args.psnr_rays > 0 and world == 1:
         psnr = psnr_vs_oracle(r, poses.cpu().numpy(), intr, nc, args.psnr_rays)
     wl = "LLFF '{}' reconstruction stage, {}x{} frames, {} rays/step/GPU, synthetic occupancy (28 seeded boxes), {:.1f} samples/ray".format(
         args.scene, intr.w, intr.h, n_rays, spr)
@@ -654,6 +713,8 @@ def run_style(args, dev, rank, world):
     n_patches = len(patch_list(W, H, 200))
     patch_graphs = None if args.no_patch_graphs else {'streams': int(os.environ.get('NSR_PATCH_STREAMS', '4'))}                        # pass 2: one hipGraph per patch shape (graph.GraphedPatchBackward)
     total_samples = torch.zeros(1, dtype=torch.int64, device=dev)
+    last_it = args.warmup + args.steps - 1
+    last_out = {}
 
     def step(it):
         frame = (it * 7) % poses.shape[0]                                       # every rank works on the SAME frame
@@ -665,12 +726,14 @@ def run_style(args, dev, rank, world):
         def image_loss(rgb, classes):
             return crit(rgb, targets[frame], classes, frame_key=frame, it=it)[0]
         if args.style_backprop == 'resident':
-            loss, _ = resident_backprop_step(r, poses[frame], image_loss, loss_scale=loss_scale, rank=rank, world=world,
-                                             optimizer=opt, with_classes=True)
+            loss, rgb = resident_backprop_step(r, poses[frame], image_loss, loss_scale=loss_scale, rank=rank, world=world,
+                                               optimizer=opt, with_classes=True)
         else:
-            loss, _ = deferred_backprop_step(r, poses[frame], image_loss, patch_size=200, loss_scale=loss_scale, rank=rank, world=world,
-                                             optimizer=opt, with_classes=True, patch_graphs=patch_graphs)
+            loss, rgb = deferred_backprop_step(r, poses[frame], image_loss, patch_size=200, loss_scale=loss_scale, rank=rank, world=world,
+                                               optimizer=opt, with_classes=True, patch_graphs=patch_graphs)
         opt.step(scaler=scaler)
+        if it == last_it and args.dump_outputs:
+            last_out['rgb_map'] = rgb.reshape(-1, 3)                           # --dump-outputs: the frame of the last step
         return loss
 
     for it in range(args.warmup):
@@ -694,6 +757,8 @@ def run_style(args, dev, rank, world):
     prof = profiling.summary()
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, loss, None, last_out)
     # rays whose forward+backward completed: the frame's pixels once per iteration (pass 2 covers every pixel once with
     # autograd; the no-grad pass 1 is overhead of the method, not counted as extra rays)
     value = W * H * args.steps / elapsed / 1e6

@@ -60,7 +60,11 @@ def test_bbox_truncexp_psnr(O, golden):
     y = TP.TruncExp.apply(x)
     y.backward(torch.ones_like(y) * 0.5)
     assert np.array_equal(y.detach().numpy(), golden['texp_y'])
-    assert np.array_equal(x.grad.numpy(), golden['texp_gx'])
+    # the reference's backward is g * exp(clamp(x, -15, 15)) (tcnn_nerf.py:66): exactly that, on this host's torch.exp ...
+    assert np.array_equal(x.grad.numpy(), (0.5 * torch.exp(x.detach().clamp(-15, 15))).numpy())
+    # ... and the golden recorded it on another host: CPU exp implementations round e^15 to either float neighbour
+    # (3269017.25 / .5), so the recorded values hold to one ulp
+    np.testing.assert_array_max_ulp(x.grad.numpy(), golden['texp_gx'], maxulp=1)
     assert abs(O.compute_psnr(float(golden['psnr_in'])) - float(golden['psnr_out'])) < 1e-4
 
 
