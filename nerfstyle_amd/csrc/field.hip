@@ -12,19 +12,10 @@
 // The forward kernel keeps all 32 table gathers of a lane's four levels in flight before it consumes the first (125
 // instead of 74 VGPRs, still 4 waves per SIMD): 8.2 -> 8.0 ms on the bench frame.  Forward only -- the backward's re-gather
 // path shares field_encode and has no registers to spare.
-#ifndef NSR_FWD_BATCH_GATHER
-#define NSR_FWD_BATCH_GATHER 1
-#endif
 #include "field_common.h"
 
 template <typename TT, int CD, bool SIGMA_ONLY>
-#ifndef NSR_FWD_WAVES_PER_EU
-#define NSR_FWD_WAVES_PER_EU 0
-#endif
 __global__ void __launch_bounds__(256)
-#if NSR_FWD_WAVES_PER_EU
-__attribute__((amdgpu_waves_per_eu(NSR_FWD_WAVES_PER_EU, NSR_FWD_WAVES_PER_EU)))
-#endif
 k_field_fwd(FieldArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     short *wl = reinterpret_cast<short *>(smem);
@@ -58,7 +49,7 @@ k_field_fwd(FieldArgs a) {
         // gridencoder.cu:107-132: inputs outside [0,1] encode to zeros
         const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);   // NaN -> zeros too
         s8v xd, xc;
-        field_encode<TT, CD, SIGMA_ONLY>(lds_lv, tables, u0, u1, u2, live, g, xd, xc, a.fast_levels);
+        field_encode<TT, CD, SIGMA_ONLY, true>(lds_lv, tables, u0, u1, u2, live, g, xd, xc, a.fast_levels);
         if (!SIGMA_ONLY && a.feats) {
             s8v *fo = reinterpret_cast<s8v *>(a.feats) + ((size_t)tile * 64 + lane) * 2;
             fo[0] = xd;

@@ -100,13 +100,8 @@ template <> struct RowLd<_Float16> {
     // conversions per level disappear from a kernel that is VALU-issue-bound half of the time
     static __device__ __forceinline__ void accumulate(const _Float16 *t, const uint32_t (&rows)[8], const float (&w)[8], float4 &acc) {
         uint2 v[8];
-#ifdef NSR_ABL_FWD_HALFGATHER
-#pragma unroll
-        for (int idx = 0; idx < 8; idx += 2) v[idx] = v[idx + 1] = reinterpret_cast<const uint2 *>(t)[rows[idx]];
-#else
 #pragma unroll
         for (int idx = 0; idx < 8; idx++) v[idx] = reinterpret_cast<const uint2 *>(t)[rows[idx]];
-#endif
 #pragma unroll
         for (int idx = 0; idx < 8; idx++) {
             asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "+v"(acc.x) : "v"(w[idx]), "v"(v[idx].x));
@@ -167,10 +162,6 @@ __device__ __forceinline__ float4 field_encode_level(const NsrLevel &lv, const T
     return acc;
 }
 
-#ifndef NSR_FWD_BATCH_GATHER
-#define NSR_FWD_BATCH_GATHER 0     /* all 32 gathers of a lane's four levels in flight before the first is used (set by field.hip) */
-#endif
-#if NSR_FWD_BATCH_GATHER
 // rows and weights of one level (the first half of field_encode_level)
 template <bool FAST>
 __device__ __forceinline__ void field_level_rows(const NsrLevel &lv, float u0, float u1, float u2, uint32_t (&rows)[8], float (&w)[8]) {
@@ -198,17 +189,16 @@ __device__ __forceinline__ void field_level_rows(const NsrLevel &lv, float u0, f
         }
     }
 }
-#endif
 
 // Encodes this lane's four levels; returns the two K=32 B fragments (density, colour).
-template <typename TT, int CD, bool SIGMA_ONLY>
+// BATCH_GATHER (the forward only): all 32 gathers of a lane's four levels in flight before the first is used.
+template <typename TT, int CD, bool SIGMA_ONLY, bool BATCH_GATHER = false>
 __device__ __forceinline__ void field_encode(const NsrLevel *lds_lv, const TT *__restrict__ tables, float u0, float u1, float u2,
                                              bool live, int g, s8v &xd, s8v &xc, uint32_t fast_levels) {
     const int lvl[4] = {2 * g, 2 * g + 1, 8 + 2 * g, 9 + 2 * g};
     // levels per call (one per lane group): {0,2,4,6} {1,3,5,7} {8,10,12,14} {9,11,13,15}
     const uint32_t call_levels[4] = {0x0055u, 0x00AAu, 0x5500u, 0xAA00u};
-#if NSR_FWD_BATCH_GATHER
-    if (!SIGMA_ONLY && sizeof(TT) == 2) {
+    if constexpr (BATCH_GATHER && !SIGMA_ONLY && sizeof(TT) == 2) {
         uint2 v[4][8];
         float w[4][8];
         if (live) {
@@ -241,7 +231,6 @@ __device__ __forceinline__ void field_encode(const NsrLevel *lds_lv, const TT *_
         }
         return;
     }
-#endif
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const NsrLevel lv = lds_lv[lvl[i]];
@@ -286,10 +275,8 @@ static int field_fill_args(const nsr_field_desc *d, FieldArgs &a, uint32_t M, ui
     const uint32_t ntiles = (M + 15) / 16;
     // >= 8 tiles per wave so the per-block weight-image build amortises; <= 8 blocks per CU
     uint32_t nb = (ntiles + 31) / 32;
-#ifndef NSR_FIELD_MAX_BLOCKS
-#define NSR_FIELD_MAX_BLOCKS 2048
-#endif
-    if (nb > NSR_FIELD_MAX_BLOCKS) nb = NSR_FIELD_MAX_BLOCKS;
+    constexpr uint32_t max_blocks = 2048;
+    if (nb > max_blocks) nb = max_blocks;
     if (nb == 0) nb = 1;
     nblocks = nb;
     a.tiles_per_block = (ntiles + nb - 1) / nb;

@@ -3,8 +3,6 @@
 // the structure does not: offsets come from a wave64 shuffle scan + one look-up of per-block
 // totals (deterministic, no atomics), the composite backward keeps its running sums in
 // registers (no rgbs_buf round trip), and every entry point takes an explicit stream.
-#include <stdlib.h>
-
 #include "nsr_common.h"
 #include "rm_util.h"
 
@@ -348,7 +346,7 @@ k_march_emit_mask(const float *__restrict__ rays_o, const float *__restrict__ ra
                   uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float *__restrict__ nears,
                   const float *__restrict__ noises, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ block_bases,
                   const uint32_t *__restrict__ mask, float *__restrict__ xyzs, float *__restrict__ dirs,
-                  float *__restrict__ deltas, int32_t *__restrict__ rays, int closed_form) {
+                  float *__restrict__ deltas, int32_t *__restrict__ rays) {
     __shared__ uint32_t wave_sums[RM_BLOCK / 64];
     const uint32_t n = blockIdx.x * RM_BLOCK + threadIdx.x;
     const uint32_t num_steps = n < N ? counts[n] : 0u;
@@ -387,7 +385,7 @@ k_march_emit_mask(const float *__restrict__ rays_o, const float *__restrict__ ra
         // MARKED steps cost instructions.  Words that cross a binade keep the serial form.
         bool closed = false;
         uint32_t b1 = 0, cc = 0;
-        if (closed_form && dt_gamma == 0.0f && t > 0.0f) {
+        if (dt_gamma == 0.0f && t > 0.0f) {
 #pragma clang fp contract(off)
             const float dt0 = rm_clamp(t * dt_gamma, c.dt_min, c.dt_max);
             const float t1 = t + dt0, t2 = t1 + dt0;
@@ -1010,16 +1008,12 @@ int nsr_march_rays_train(const float *rays_o, const float *rays_d, const float *
     const uint32_t nblocks = (N + RM_BLOCK - 1) / RM_BLOCK;
     uint32_t *counts = (uint32_t *)workspace;
     uint32_t *block_sums = counts + N;
-    // small batches: one wave per ray (k_march_wpr), bit-identical results; NSR_MARCH_WPR=0/1 forces a path
-    static const int wpr_env = [] { const char *e = getenv("NSR_MARCH_WPR"); return e ? atoi(e) : -1; }();
-    const bool wpr = !is_ndc && (wpr_env >= 0 ? wpr_env != 0 : N <= NSR_MARCH_WPR_MAX_RAYS);
-    if (wpr) {
+    // small batches: one wave per ray (k_march_wpr), bit-identical results
+    if (!is_ndc && N <= NSR_MARCH_WPR_MAX_RAYS) {
         const uint32_t wblocks = (N + 3) / 4;
-        // the counting pass records every block's start and sample mask; the emit replays them (no second probe).  The records
-        // need the workspace of nsr_march_rays_train_workspace_bytes for THIS N (a forced wave-per-ray march of a large batch,
-        // NSR_MARCH_WPR=1, re-marches instead: its workspace was sized for the thread-per-ray mask)
-        static const int slots_env = [] { const char *e = getenv("NSR_MARCH_WPR_SLOTS"); return e ? atoi(e) : 1; }();
-        const uint32_t slot_cap = (slots_env && !march_uses_mask(N, 0)) ? march_wpr_slot_cap(bound, max_steps) : 0u;
+        // the counting pass records every block's start and sample mask; the emit replays them (no second probe).  When a
+        // ray can need more records than a wave has lanes (slot_cap = 0), the emit marches again instead.
+        const uint32_t slot_cap = march_wpr_slot_cap(bound, max_steps);
         uint32_t *slots = slot_cap ? block_sums + nblocks + 64 : nullptr;
         hipLaunchKernelGGL((k_march_wpr<false>), dim3(wblocks), dim3(256), 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C,
                            H, M, nears, fars, noises, counts, (const uint32_t *)nullptr, (float *)nullptr, (float *)nullptr,
@@ -1036,7 +1030,7 @@ int nsr_march_rays_train(const float *rays_o, const float *rays_d, const float *
     }
     // large batches, thread per ray: the counting pass marks the samples in a per-ray bit mask, the emitting pass replays the
     // t sequence without probing the grid again (NDC keeps the re-marching emit)
-    const bool use_mask = !wpr && march_uses_mask(N, is_ndc);
+    const bool use_mask = march_uses_mask(N, is_ndc);
     uint32_t *mask = use_mask ? block_sums + nblocks + 64 : nullptr;
     const uint32_t kcap = march_kcap(bound, max_steps);
     hipLaunchKernelGGL(k_march_count, dim3(nblocks), dim3(RM_BLOCK), 0, s, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N,
@@ -1048,12 +1042,10 @@ int nsr_march_rays_train(const float *rays_o, const float *rays_d, const float *
     // the ~30 waves per CU its 32 registers allow, more partially written lines are open than the L2 holds.  60 KB of (unused)
     // dynamic LDS per workgroup keeps two workgroups per CU: 1.12-1.20 -> 0.87-1.09 ms on the bench frame (box to box); the
     // closed-form step of k_march_emit_mask takes another ~15 us at that occupancy, nothing at full occupancy.
-    static const int emit_lds = [] { const char *e = getenv("NSR_MARCH_EMIT_LDS"); const int v = e ? atoi(e) : 61440; return v < 0 ? 0 : (v > 64000 ? 64000 : v); }();
-    static const int closed_env = [] { const char *e = getenv("NSR_MARCH_EMIT_CLOSED"); return e ? atoi(e) : 1; }();
-    if (use_mask) {
-        hipLaunchKernelGGL(k_march_emit_mask, dim3(nblocks), dim3(RM_BLOCK), (size_t)emit_lds, s, rays_o, rays_d, bound, dt_gamma, max_steps, N, C,
-                           H, M, nears, noises, counts, block_sums, mask, xyzs, dirs, deltas, rays, closed_env);
-    }
+    constexpr size_t emit_lds = 61440;
+    if (use_mask)
+        hipLaunchKernelGGL(k_march_emit_mask, dim3(nblocks), dim3(RM_BLOCK), emit_lds, s, rays_o, rays_d, bound, dt_gamma, max_steps, N, C,
+                           H, M, nears, noises, counts, block_sums, mask, xyzs, dirs, deltas, rays);
     else
         hipLaunchKernelGGL(k_march_emit, dim3(nblocks), dim3(RM_BLOCK), 0, s, rays_o, rays_d, z_hats, grid, bound, dt_gamma,
                            max_steps, is_ndc, N, C, H, M, nears, fars, noises, counts, block_sums, 0u, xyzs, dirs, deltas, rays);

@@ -48,9 +48,7 @@
 #define SO_BINS 512
 #define SO_BPT (SO_BINS / SO_THREADS)          // digits per thread in the per-digit loops
 #define SO_MAX_BLOCKS 1024
-#ifndef SO_BLOCKS_TARGET
-#define SO_BLOCKS_TARGET 768                   // 3 resident blocks per CU (52 KB of LDS each)
-#endif
+constexpr uint32_t SO_BLOCKS_TARGET = 768;   // 3 resident blocks per CU (52 KB of LDS each)
 
 struct OrderArgs {
     const float *xyzs;

@@ -46,13 +46,11 @@ struct LatGeom {
     uint8_t S[16];          // corners per axis
     uint8_t shift[16];      // the level's lattice is anchored at the origin of the 2^shift-block group the walk is in
 };
-#ifndef NSR_TS_THREADS
-#define NSR_TS_THREADS 256        /* measured on the bench frame: 64 -> 35.6 ms, 128 -> 30.6, 256 -> 29.4 (A + B) */
-#endif
+constexpr int TS_THREADS = 256;     // measured on the bench frame: 64 -> 35.6 ms, 128 -> 30.6, 256 -> 29.4 (A + B)
 // float4 slots per wave, from the 64 KB of LDS a workgroup may ask for: level table + per wave (256 B + 16 B per slot), the
 // slot count rounded up to 64 (4 waves: 960).  nsr_table_scatter_supported() and the launch share THIS bound, so a grid is
 // rejected before anything is launched or never (round 2 rejected totals of 961..1024 after the MLP backward had run)
-constexpr int LAT_MAX_SLOTS = (int)(((65536 - 16 * sizeof(NsrLevel)) / (NSR_TS_THREADS / 64) - 256) / 16 / 64 * 64);
+constexpr int LAT_MAX_SLOTS = (int)(((65536 - 16 * sizeof(NsrLevel)) / (TS_THREADS / 64) - 256) / 16 / 64 * 64);
 constexpr int LAT_KEY_BITS = 10;                     // must match nsr_sample_order's quantisation
 constexpr uint32_t LAT_NONE = 0xFFFFFFFFu;
 struct LatState {
@@ -79,11 +77,8 @@ static bool lat_geometry(const NsrLevel *lv, LatGeom &g) {
         const uint32_t res = lv[l].resolution;
         uint32_t shift = 0, S = lat_corners(res, 0);
         while (shift < (uint32_t)LAT_KEY_BITS && lat_corners(res, shift + 1) <= (S > 3u ? S : 3u)) shift++;   // free
-#ifdef NSR_TS_FINE_GROUPS
-        // experiment: the NSR_TS_FINE_GROUPS finest levels pay a larger lattice for a group of 2^3 blocks (bench frame,
-        // backward pair: 1 level 22.14 ms, 2 -> 22.09, 3 -> 22.91 against 22.2: nothing to gain)
-        if (l >= 16 - NSR_TS_FINE_GROUPS && lat_corners(res, shift + 1) <= 6u) { shift++; S = lat_corners(res, shift); }
-#endif
+        // (letting the 1, 2 or 3 finest levels pay a larger lattice for a group of 2^3 blocks: bench frame, backward pair
+        // 22.14, 22.09, 22.91 ms against 22.2 -- nothing to gain)
         S = lat_corners(res, shift) > S ? lat_corners(res, shift) : S;
         if (S < 2u || S > 6u) return false;
         g.S[l] = (uint8_t)S;
@@ -133,11 +128,7 @@ __device__ __forceinline__ void lat_flush_level(float4 *__restrict__ lat4, uint3
             if (rec) {
                 const float val = lf[(k0 + 16 * q + t) * 4 + i];
                 const uint32_t row = rows[16 * q + t];
-#ifndef NSR_ABL_NO_ATOMIC
                 if (on) atomicAdd(gt + (size_t)row * 4 + i, val);
-#else
-                if (on && row == 0xFFFFFFFFu) gt[i] = val;
-#endif
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -149,9 +140,6 @@ __device__ __forceinline__ void lat_flush_level(float4 *__restrict__ lat4, uint3
 // kernel-argument segment here would be a vector-memory load, and waiting for it means waiting for every atomic in flight.
 __device__ __forceinline__ void lat_flush_dispatch(float4 *__restrict__ lat, int fl, const LatState &st,
                                                    const NsrLevel *__restrict__ lds_lv, float *__restrict__ gt, int lane, bool td, bool tc) {
-#ifdef NSR_ABL_TS_NOFLUSH
-    return;
-#endif
     const uint32_t o0 = (uint32_t)__builtin_amdgcn_readlane((int)st.b0, fl * 4);
     if (o0 == LAT_NONE) return;
     const uint32_t o1 = (uint32_t)__builtin_amdgcn_readlane((int)st.b1, fl * 4);
@@ -181,33 +169,10 @@ struct TableScatterArgs {
     NsrLevel lv[16];              // pad_ = S | shift << 4 | base << 8
 };
 
-#ifndef NSR_TS_THREADS
-#define NSR_TS_THREADS 256        /* measured on the bench frame: 64 -> 35.6 ms, 128 -> 30.6, 256 -> 29.4 (A + B) */
-#endif
-#ifndef NSR_TS_LDS_ATOMIC
-#define NSR_TS_LDS_ATOMIC 0
-#endif
-#ifndef NSR_TS_RING
-#define NSR_TS_RING 8           /* gradient rows in flight per wave (0: one-step-ahead prefetch, the r2 first version) */
-#endif
-#ifndef NSR_TS_UNROLL
-#define NSR_TS_UNROLL 4         /* 1 -> 31.7 ms, 2 -> 30.6, 4 -> 29.4, 8 -> 29.6 */
-#endif
-constexpr int TS_THREADS = NSR_TS_THREADS;
-#ifdef NSR_ABL_TS_NOGIN
-#define TS_GIN(v, ln) make_float4(1.0f, 2.0f, 3.0f, (float)(ln))
-#else
-#define TS_GIN(v, ln) a.gin[(size_t)(uint32_t)__builtin_amdgcn_readlane((int)(v), (ln)) * 16 + l]
-#endif
+constexpr int TS_RING = 8;          // gradient rows in flight per wave
 static size_t ts_wave_bytes(uint32_t lat_slots) { return 256 + (size_t)lat_slots * 16; }
 
-#ifndef NSR_TS_WAVES_PER_EU
-#define NSR_TS_WAVES_PER_EU 0
-#endif
 __global__ void __launch_bounds__(TS_THREADS)
-#if NSR_TS_WAVES_PER_EU
-__attribute__((amdgpu_waves_per_eu(NSR_TS_WAVES_PER_EU, NSR_TS_WAVES_PER_EU)))
-#endif
 k_table_scatter(TableScatterArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem);
@@ -251,13 +216,13 @@ k_table_scatter(TableScatterArgs a) {
     uint32_t idx = fetch_idx(w_begin);
     uint32_t idx_next = w_begin + 1 < w_end ? fetch_idx(w_begin + 1) : idx;
     float x0 = a.xyzs[(size_t)idx * 3], x1 = a.xyzs[(size_t)idx * 3 + 1], x2 = a.xyzs[(size_t)idx * 3 + 2];
-#if NSR_TS_RING
-    // The per-level gradients of the next NSR_TS_RING samples, in registers: a 256-byte row gathered by sample index is a
-    // full HBM round trip (~1 us under load), far longer than a step, so a row is requested 8 steps before its use.
-    float4 gq[NSR_TS_RING];
+    // The per-level gradients of the next TS_RING samples, in registers: a 256-byte row gathered by sample index is a
+    // full HBM round trip (~1 us under load), far longer than a step, so a row is requested 8 steps before its use (a
+    // one-step-ahead prefetch was the first version).  ts_gin(v, ln): level l's row of the sample of lane ln's index v.
+    auto ts_gin = [&](uint32_t v, int ln) { return a.gin[(size_t)(uint32_t)__builtin_amdgcn_readlane((int)v, ln) * 16 + l]; };
+    float4 gq[TS_RING];
 #pragma unroll
-    for (int i = 0; i < NSR_TS_RING; i++) gq[i] = TS_GIN(idx, i);
-#endif
+    for (int i = 0; i < TS_RING; i++) gq[i] = ts_gin(idx, i);
 
     for (uint32_t tile = w_begin; tile < w_end; tile++) {
         // next tile's inputs: the permutation entry was fetched one tile ahead, so these loads depend on nothing in flight
@@ -283,120 +248,89 @@ k_table_scatter(TableScatterArgs a) {
         const uint32_t bkey_e = live ? bkey : LAT_NONE;
         const uint32_t bkey_l = (uint32_t)__builtin_amdgcn_update_dpp((int)cur_key, (int)bkey_e, 0x111, 0xF, 0xF, false);   // row_shr:1
         const uint32_t chg16 = (uint32_t)(__ballot(bkey_e != bkey_l) & 0xFFFFull);
-#if NSR_TS_RING
 #pragma unroll 1
-        for (int part = 0; part < 16 / NSR_TS_RING; part++) {
-        // refills: the rest of this tile first, then the head of the next one (its permutation entries are already here)
-        const bool wrap = part == 16 / NSR_TS_RING - 1;
-        const uint32_t src = wrap ? idx_next : idx;
-        const int src_lane0 = wrap ? 0 : (part + 1) * NSR_TS_RING;
+        for (int part = 0; part < 16 / TS_RING; part++) {
+            // refills: the rest of this tile first, then the head of the next one (its permutation entries are already here)
+            const bool wrap = part == 16 / TS_RING - 1;
+            const uint32_t src = wrap ? idx_next : idx;
+            const int src_lane0 = wrap ? 0 : (part + 1) * TS_RING;
 #pragma unroll
-        for (int ri = 0; ri < NSR_TS_RING; ri++) {
-            const int step = part * NSR_TS_RING + ri;
-            const float4 gr = gq[ri];
-            do {
-            if (!((live16 >> step) & 1u)) break;                               // wave-uniform
-#else
-        // the per-level gradients of a sample are fetched one step ahead of their use
-        float4 gr_next = TS_GIN(idx, 0);
-#pragma unroll NSR_TS_UNROLL
-        for (int step = 0; step < 16; step++) {
-            const float4 gr = gr_next;
-            if (step < 15) gr_next = TS_GIN(idx, step + 1);
-            if (!((live16 >> step) & 1u)) continue;                            // wave-uniform
-#endif
-            uint32_t key = cur_key;
-            if ((chg16 >> step) & 1u) key = (uint32_t)__builtin_amdgcn_readlane((int)bkey, step);       // wave-uniform
-            if (key != cur_key) {
-                // ---- the walk enters another block: re-anchor every level at the cell of the block's origin ----
-                cur_key = key;
-                // origin of the group of 2^ashift blocks (this lane's level) the block belongs to
-                const uint32_t kq0 = key & ((1u << LAT_KEY_BITS) - 1u), kq1 = (key >> LAT_KEY_BITS) & ((1u << LAT_KEY_BITS) - 1u),
-                               kq2 = key >> (2 * LAT_KEY_BITS);
-                const float o0 = (float)((kq0 >> ashift) << ashift) * rk, o1 = (float)((kq1 >> ashift) << ashift) * rk,
-                            o2 = (float)((kq2 >> ashift) << ashift) * rk;
-                float ff;
-                uint32_t n0, n1, n2;
-                nsr_grid_locate(o0, lv.resolution, 1, ff, n0);
-                nsr_grid_locate(o1, lv.resolution, 1, ff, n1);
-                nsr_grid_locate(o2, lv.resolution, 1, ff, n2);
-                const bool chg = (n0 != st.b0) | (n1 != st.b1) | (n2 != st.b2);
-                unsigned long long mm = __ballot(chg);
-                while (mm) {
-                    const int fl = (int)(__builtin_ctzll(mm) >> 2);
-                    mm &= ~(0xFull << (fl * 4));
-                    lat_flush_dispatch(lat, fl, st, lds_lv, gt, lane, td, tc);
-                }
-                if (chg) { st.b0 = n0; st.b1 = n1; st.b2 = n2; bf0 = (float)n0; bf1 = (float)n1; bf2 = (float)n2; }
-            }
-            const float su0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u0), step));
-            const float su1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u1), step));
-            const float su2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u2), step));
-            // nsr_grid_locate (align_corners = 1) with the cell kept as a float: p = u * res, c = min(floor(p), res - 1), f = p - c
-            float f0, f1, f2, cf0, cf1, cf2;
-            {
-#pragma clang fp contract(off)
-                const float p0 = su0 * lscale, p1 = su1 * lscale, p2 = su2 * lscale;
-                cf0 = fminf(floorf(p0), lcmax); cf1 = fminf(floorf(p1), lcmax); cf2 = fminf(floorf(p2), lcmax);
-                f0 = p0 - cf0; f1 = p1 - cf1; f2 = p2 - cf2;
-            }
-            // cell relative to the anchor: 0 .. S - 2 by construction (the sample lies in the block the anchor was taken
-            // from; floor(u * res) is monotonic in u)
-            const float d0 = cf0 - bf0, d1 = cf1 - bf1, d2 = cf2 - bf2;
-            const float r0 = fminf(d0, Sm2), r1 = fminf(d1, Sm2), r2 = fminf(d2, Sm2);
-            // this sample's contribution to the lane's two x corners
-            const float wyz = fmaf(f1, sy, oy) * fmaf(f2, sz, oz);
-            float wB = f0 * wyz, wA = wyz - wB;
-            if (fmaxf(d0, fmaxf(d1, d2)) > Sm2) {
-                const uint32_t c0 = (uint32_t)cf0, c1 = (uint32_t)cf1, c2 = (uint32_t)cf2;
-                // fp32 rounding put the cell one past the lattice (u * res of a sample at the very end of its block can
-                // round up across a cell boundary that the block's real extent stops short of): this sample's two corners
-                // go straight to the table, exactly; the (clamped) lattice slots get nothing
-                const uint32_t rowA = lv.offset + lat_row(lv, c0, c1 + (uint32_t)py, c2 + (uint32_t)pz);
-                const uint32_t rowB = lv.offset + lat_row(lv, c0 + 1u, c1 + (uint32_t)py, c2 + (uint32_t)pz);
-                const float ga[4] = {gr.x, gr.y, gr.z, gr.w};
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    if ((i < 2 ? td : tc) && ga[i] != 0.0f) {
-                        atomicAdd(gt + (size_t)rowA * 4 + i, wA * ga[i]);
-                        atomicAdd(gt + (size_t)rowB * 4 + i, wB * ga[i]);
+            for (int ri = 0; ri < TS_RING; ri++) {
+                const int step = part * TS_RING + ri;
+                const float4 gr = gq[ri];
+                if ((live16 >> step) & 1u) {                                       // wave-uniform
+                    uint32_t key = cur_key;
+                    if ((chg16 >> step) & 1u) key = (uint32_t)__builtin_amdgcn_readlane((int)bkey, step);       // wave-uniform
+                    if (key != cur_key) {
+                        // ---- the walk enters another block: re-anchor every level at the cell of the block's origin ----
+                        cur_key = key;
+                        // origin of the group of 2^ashift blocks (this lane's level) the block belongs to
+                        const uint32_t kq0 = key & ((1u << LAT_KEY_BITS) - 1u), kq1 = (key >> LAT_KEY_BITS) & ((1u << LAT_KEY_BITS) - 1u),
+                                       kq2 = key >> (2 * LAT_KEY_BITS);
+                        const float o0 = (float)((kq0 >> ashift) << ashift) * rk, o1 = (float)((kq1 >> ashift) << ashift) * rk,
+                                    o2 = (float)((kq2 >> ashift) << ashift) * rk;
+                        float ff;
+                        uint32_t n0, n1, n2;
+                        nsr_grid_locate(o0, lv.resolution, 1, ff, n0);
+                        nsr_grid_locate(o1, lv.resolution, 1, ff, n1);
+                        nsr_grid_locate(o2, lv.resolution, 1, ff, n2);
+                        const bool chg = (n0 != st.b0) | (n1 != st.b1) | (n2 != st.b2);
+                        unsigned long long mm = __ballot(chg);
+                        while (mm) {
+                            const int fl = (int)(__builtin_ctzll(mm) >> 2);
+                            mm &= ~(0xFull << (fl * 4));
+                            lat_flush_dispatch(lat, fl, st, lds_lv, gt, lane, td, tc);
+                        }
+                        if (chg) { st.b0 = n0; st.b1 = n1; st.b2 = n2; bf0 = (float)n0; bf1 = (float)n1; bf2 = (float)n2; }
                     }
+                    const float su0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u0), step));
+                    const float su1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u1), step));
+                    const float su2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u2), step));
+                    // nsr_grid_locate (align_corners = 1) with the cell kept as a float: p = u * res, c = min(floor(p), res - 1), f = p - c
+                    float f0, f1, f2, cf0, cf1, cf2;
+                    {
+#pragma clang fp contract(off)
+                        const float p0 = su0 * lscale, p1 = su1 * lscale, p2 = su2 * lscale;
+                        cf0 = fminf(floorf(p0), lcmax); cf1 = fminf(floorf(p1), lcmax); cf2 = fminf(floorf(p2), lcmax);
+                        f0 = p0 - cf0; f1 = p1 - cf1; f2 = p2 - cf2;
+                    }
+                    // cell relative to the anchor: 0 .. S - 2 by construction (the sample lies in the block the anchor was taken
+                    // from; floor(u * res) is monotonic in u)
+                    const float d0 = cf0 - bf0, d1 = cf1 - bf1, d2 = cf2 - bf2;
+                    const float r0 = fminf(d0, Sm2), r1 = fminf(d1, Sm2), r2 = fminf(d2, Sm2);
+                    // this sample's contribution to the lane's two x corners
+                    const float wyz = fmaf(f1, sy, oy) * fmaf(f2, sz, oz);
+                    float wB = f0 * wyz, wA = wyz - wB;
+                    if (fmaxf(d0, fmaxf(d1, d2)) > Sm2) {
+                        const uint32_t c0 = (uint32_t)cf0, c1 = (uint32_t)cf1, c2 = (uint32_t)cf2;
+                        // fp32 rounding put the cell one past the lattice (u * res of a sample at the very end of its block can
+                        // round up across a cell boundary that the block's real extent stops short of): this sample's two corners
+                        // go straight to the table, exactly; the (clamped) lattice slots get nothing
+                        const uint32_t rowA = lv.offset + lat_row(lv, c0, c1 + (uint32_t)py, c2 + (uint32_t)pz);
+                        const uint32_t rowB = lv.offset + lat_row(lv, c0 + 1u, c1 + (uint32_t)py, c2 + (uint32_t)pz);
+                        const float ga[4] = {gr.x, gr.y, gr.z, gr.w};
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            if ((i < 2 ? td : tc) && ga[i] != 0.0f) {
+                                atomicAdd(gt + (size_t)rowA * 4 + i, wA * ga[i]);
+                                atomicAdd(gt + (size_t)rowB * 4 + i, wB * ga[i]);
+                            }
+                        }
+                        wA = 0.0f;
+                        wB = 0.0f;
+                    }
+                    float4 *const slot = mylat + (uint32_t)fmaf(fmaf(r2, Sf, r1), Sf, r0);
+                    float4 va = slot[0], vb = slot[1];
+                    va.x = fmaf(wA, gr.x, va.x); va.y = fmaf(wA, gr.y, va.y); va.z = fmaf(wA, gr.z, va.z); va.w = fmaf(wA, gr.w, va.w);
+                    vb.x = fmaf(wB, gr.x, vb.x); vb.y = fmaf(wB, gr.y, vb.y); vb.z = fmaf(wB, gr.z, vb.z); vb.w = fmaf(wB, gr.w, vb.w);
+                    slot[0] = va;
+                    slot[1] = vb;
                 }
-                wA = 0.0f;
-                wB = 0.0f;
+                // the slot's refill is issued AFTER the last use of its old value, so every ring slot stays in the same registers
+                // (a refill issued earlier gets other registers, and the copies at the loop edge wait for every load in flight)
+                asm volatile("" ::: "memory");
+                gq[ri] = ts_gin(src, src_lane0 + ri);
             }
-            float4 *const slot = mylat + (uint32_t)fmaf(fmaf(r2, Sf, r1), Sf, r0);
-#if NSR_TS_LDS_ATOMIC
-            // fire-and-forget LDS float adds: no read -> fma -> write round trip to wait for (the lattice is private to the wave
-            // and the 64 lanes of a step touch 128 different slots, so nothing conflicts)
-            float *const sf = reinterpret_cast<float *>(slot);
-            __hip_atomic_fetch_add(sf + 0, wA * gr.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __hip_atomic_fetch_add(sf + 1, wA * gr.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __hip_atomic_fetch_add(sf + 2, wA * gr.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __hip_atomic_fetch_add(sf + 3, wA * gr.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __hip_atomic_fetch_add(sf + 4, wB * gr.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __hip_atomic_fetch_add(sf + 5, wB * gr.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __hip_atomic_fetch_add(sf + 6, wB * gr.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __hip_atomic_fetch_add(sf + 7, wB * gr.w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#else
-#ifdef NSR_ABL_TS_NORMW
-            if (wA == 123.0f) slot[0] = gr;
-#else
-            float4 va = slot[0], vb = slot[1];
-            va.x = fmaf(wA, gr.x, va.x); va.y = fmaf(wA, gr.y, va.y); va.z = fmaf(wA, gr.z, va.z); va.w = fmaf(wA, gr.w, va.w);
-            vb.x = fmaf(wB, gr.x, vb.x); vb.y = fmaf(wB, gr.y, vb.y); vb.z = fmaf(wB, gr.z, vb.z); vb.w = fmaf(wB, gr.w, vb.w);
-            slot[0] = va;
-            slot[1] = vb;
-#endif
-#endif
-#if NSR_TS_RING
-            } while (0);
-            // the slot's refill is issued AFTER the last use of its old value, so every ring slot stays in the same registers
-            // (a refill issued earlier gets other registers, and the copies at the loop edge wait for every load in flight)
-            asm volatile("" ::: "memory");
-            gq[ri] = TS_GIN(src, src_lane0 + ri);
-        }
-#endif
         }
         x0 = nx0; x1 = nx1; x2 = nx2;
         idx = idx_next;
@@ -428,10 +362,7 @@ int nsr_table_scatter_launch(const NsrLevel *levels, const float *bmin, const fl
     a.xyzs = xyzs; a.perm = perm; a.m_dev = m_dev; a.M = M; a.gin = (const float4 *)gin; a.grad_tables = grad_tables;
     for (int i = 0; i < 3; i++) { a.bmin[i] = bmin[i]; a.bsize[i] = bsize[i]; }
     a.td = td; a.tc = tc;
-#ifndef NSR_ABL_TS_PAD_LDS
-#define NSR_ABL_TS_PAD_LDS 0      /* ablation: extra LDS bytes per workgroup, to lower the occupancy */
-#endif
-    const size_t lds = 16 * sizeof(NsrLevel) + (TS_THREADS / 64) * ts_wave_bytes(a.lat_slots) + NSR_ABL_TS_PAD_LDS;
+    const size_t lds = 16 * sizeof(NsrLevel) + (TS_THREADS / 64) * ts_wave_bytes(a.lat_slots);
     static bool attr_set[64] = {};
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -444,11 +375,7 @@ int nsr_table_scatter_launch(const NsrLevel *levels, const float *bmin, const fl
     // 16 workgroups per CU (4 096 in all), although only 3-4 are resident at a time: the cost of a run of tiles depends on
     // how often its samples change block, and with one workgroup per resident slot the slowest run decides the launch
     // (bench frame, backward pair: 4 per CU 25.5 ms, 6 -> 24.2, 8 -> 23.9, 16 -> 23.55, 32 -> 23.6)
-    uint32_t per_cu = 16;
-#ifdef NSR_ABL_TS_PER_CU
-    per_cu = NSR_ABL_TS_PER_CU;
-#endif
-    uint32_t nblocks = 256u * per_cu;
+    uint32_t nblocks = 256u * 16u;
     const uint32_t ntiles = (M + 15) / 16;
     if (nblocks > (ntiles + 3) / 4) nblocks = (ntiles + 3) / 4;
     if (nblocks == 0) nblocks = 1;

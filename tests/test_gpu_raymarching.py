@@ -40,11 +40,12 @@ def test_near_far_morton_packbits(O, dev):
 
 
 @pytest.mark.parametrize('n_rays,max_steps,dt_gamma', [(4096, 1024, 0.), (1000, 512, 0.), (257, 64, 0.), (24001, 1024, 0.),
-                                                       (3001, 1024, 1. / 128), (22001, 1024, 1. / 256)])
+                                                       (3001, 1024, 1. / 128), (22001, 1024, 1. / 256), (3001, 4096, 0.)])
 def test_march_rays_train_bit_exact(O, dev, n_rays, max_steps, dt_gamma):
     """Both march implementations against the sequential oracle, bit for bit: batches up to 20 480 rays run
     one wave per ray (k_march_wpr: speculative probes + successor walk), larger ones one thread per ray;
-    dt_gamma != 0 makes the step grow along the ray (cone marching, raymarching.cu:468)."""
+    dt_gamma != 0 makes the step grow along the ray (cone marching, raymarching.cu:468).  With bound 2 and
+    4096 steps a ray can need more block records than a wave has lanes: the wave-per-ray emit marches again."""
     from nerfstyle_amd import raymarching as R
     grid, bits = small_scene()
     ro, rd = room_rays(O, n_rays, seed=n_rays)
