@@ -350,6 +350,30 @@ int nsr_adam_step_scaled(float *params, float *grads, float *exp_avg, float *exp
                          void *half_copy, uint64_t n, uint64_t half_n, float beta1, float beta2, float eps,
                          uint32_t elem_mask4, const void *scaler_state, nsr_stream_t stream);
 
+/* Lane-packed tables: ONE of the two interleaved hash tables trained alone (the stylisation stage, trainers/style.py:25),
+ * its optimiser step sharded across data-parallel ranks.  lane_mask: 0x3 = density table (lanes 0, 1 of every 16-byte row),
+ * 0xC = colour table (lanes 2, 3); the trained float2 of row r is packed[2r .. 2r+1].  Stream-ordered, capture-safe
+ * (no host read, no allocation).
+ *   nsr_lanes_pack         packed[2r..2r+1] = trained lanes of grad row r, r < rows; all four lanes of every row are then
+ *                          zeroed (untrained gradients are still zeroed).  grad_arena 16-byte, packed 8-byte aligned.
+ *   nsr_lanes_adam(_scaled) Adam + EMA for rows [row_lo, row_hi): grad, exp_avg, exp_avg_sq and packed_out are packed and
+ *                          shard-local (element 2 (r - row_lo) + l); ema (may be NULL) holds all four lanes of those rows
+ *                          (float4 per row, shard-local), moved as nsr_adam_step moves every element of a trained row.
+ *                          arena and half_copy (f16, may be NULL) are the whole tables, updated in place at row r.
+ *                          packed_out (may alias grad) receives the rows' trained lanes after the step, skipped or not.
+ *                          Arithmetic identical to nsr_adam_step / nsr_adam_step_scaled (host scalars / scaler_state).
+ *   nsr_lanes_unpack       rows [row_lo, row_hi) of a gathered packed buffer (indexed by global row) -> their arena lanes
+ *                          and all four lanes of half_copy (may be NULL). */
+int nsr_lanes_pack(float *grad_arena, uint64_t rows, uint32_t lane_mask, float *packed, nsr_stream_t stream);
+int nsr_lanes_adam(float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq, float *ema,
+                   float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, float lr, float beta1,
+                   float beta2, float eps, float grad_scale_inv, float ema_decay, uint32_t step, nsr_stream_t stream);
+int nsr_lanes_adam_scaled(float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq,
+                          float *ema, float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask,
+                          float beta1, float beta2, float eps, const void *scaler_state, nsr_stream_t stream);
+int nsr_lanes_unpack(const float *packed, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, float *arena,
+                     void *half_copy, nsr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Occupancy-grid update on the device: replaces Renderer.update_state / _compute_occ_sigmas
  * (renderer.py:120-194), which is torch glue with two host reads (`mean_density.item()`, the size of

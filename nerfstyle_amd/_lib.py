@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, 'libnsr_hip.so')
 
 NSR_F32, NSR_F16, NSR_BF16 = 0, 1, 2
 NSR_ACT_NONE, NSR_ACT_SIGMOID = 0, 1
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _DT = {torch.float32: NSR_F32, torch.float16: NSR_F16, torch.bfloat16: NSR_BF16}
 
@@ -77,6 +77,10 @@ SIGNATURES = {
     'nsr_grad_check': (i32, [vp, u64, u32, vp, vp]),
     'nsr_scaler_update': (i32, [vp, f32, f32, f32, f32, f32, f32, u32, i32, f32, vp]),
     'nsr_adam_step_scaled': (i32, [vp, vp, vp, vp, vp, vp, u64, u64, f32, f32, f32, u32, vp, vp]),
+    'nsr_lanes_pack': (i32, [vp, u64, u32, vp, vp]),
+    'nsr_lanes_adam': (i32, [vp, vp, vp, vp, vp, vp, vp, u64, u64, u32, f32, f32, f32, f32, f32, f32, u32, vp]),
+    'nsr_lanes_adam_scaled': (i32, [vp, vp, vp, vp, vp, vp, vp, u64, u64, u32, f32, f32, f32, vp, vp]),
+    'nsr_lanes_unpack': (i32, [vp, u64, u64, u32, vp, vp, vp]),
     'nsr_occ_workspace_bytes': (u64, [u32, u32]),
     'nsr_occ_num_points': (u32, [u32, u32, i32]),
     'nsr_occ_sample_points': (i32, [vp, u32, u32, f32, i32, u64, u32, vp, vp, vp, vp, vp, vp]),

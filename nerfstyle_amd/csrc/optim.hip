@@ -31,6 +31,16 @@ __device__ __forceinline__ float adam_one(float &p, float g, float &m, float &v,
     return p;
 }
 
+// this step's scalars from the device-side scaler state (no-op on the host-scalar path); true: the step is skipped
+__device__ __forceinline__ bool adam_scalars(AdamArgs &a) {
+    if (!a.dyn) return false;
+    a.step_size = __uint_as_float(a.dyn[SC_STEP_SIZE]);
+    a.inv_sqrt_bc2 = __uint_as_float(a.dyn[SC_INV_BC2]);
+    a.grad_scale_inv = __uint_as_float(a.dyn[SC_INV_SCALE]);
+    if (a.ema) a.ema_decay = __uint_as_float(a.dyn[SC_EMA_DECAY]);
+    return a.dyn[SC_SKIP] != 0u;
+}
+
 // any non-finite value among the trained elements -> found_inf (GradScaler.unscale_'s check, one streaming pass)
 __global__ void __launch_bounds__(256)
 k_grad_check(const float *__restrict__ g, uint64_t n, uint32_t mask4, uint32_t *__restrict__ found) {
@@ -103,14 +113,7 @@ __global__ void k_scaler_update(uint32_t *st, float lr_base, float lr_decay_step
 __global__ void __launch_bounds__(256)
 k_adam(AdamArgs a) {
     const uint64_t n4 = a.n / 4;
-    bool skip = false;
-    if (a.dyn) {
-        skip = a.dyn[SC_SKIP] != 0u;
-        a.step_size = __uint_as_float(a.dyn[SC_STEP_SIZE]);
-        a.inv_sqrt_bc2 = __uint_as_float(a.dyn[SC_INV_BC2]);
-        a.grad_scale_inv = __uint_as_float(a.dyn[SC_INV_SCALE]);
-        if (a.ema) a.ema_decay = __uint_as_float(a.dyn[SC_EMA_DECAY]);
-    }
+    const bool skip = adam_scalars(a);
     if (skip) {
         // GradScaler skipped optimizer.step(): parameters and moments stay; the gradient is cleared (the reference's
         // zero_grad at the top of the next iteration) and the EMA still moves (ema.update() is unconditional, base.py:426)
@@ -167,6 +170,13 @@ k_adam(AdamArgs a) {
     }
 }
 
+// host-scalar path: Adam's bias corrections for step `step`, in double precision as torch computes them
+static void adam_host_bias_corrections(AdamArgs &a, float lr, uint32_t step) {
+    const double bc1 = 1.0 - pow((double)a.beta1, (double)step), bc2 = 1.0 - pow((double)a.beta2, (double)step);
+    a.step_size = (float)((double)lr / bc1);
+    a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+}
+
 static int adam_launch(AdamArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_adam, dim3(nsr_grid_1d(a.n / 4 + 1, 256)), dim3(256), 0, s, a);
     return nsr_launch_status();
@@ -186,9 +196,7 @@ extern "C" int nsr_adam_step(float *params, float *grads, float *exp_avg, float 
     a.half_n = n; a.dyn = nullptr;
     a.mask4 = elem_mask4 & 0xFu;
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.grad_scale_inv = grad_scale_inv; a.ema_decay = ema_decay;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    a.step_size = (float)((double)lr / bc1);
-    a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    adam_host_bias_corrections(a, lr, step);
     return adam_launch(a, (hipStream_t)stream);
 }
 
@@ -229,4 +237,153 @@ extern "C" int nsr_adam_step_scaled(float *params, float *grads, float *exp_avg,
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.ema_decay = 0.0f;           // (read from the state in the kernel)
     a.step_size = 0.0f; a.inv_sqrt_bc2 = 1.0f; a.grad_scale_inv = 1.0f;
     return adam_launch(a, (hipStream_t)stream);
+}
+
+// ---- lane-packed tables: one hash table of the interleaved rows (tables[row][enc][feat], 16 B per row), trained alone ----
+// (the stylisation stage, trainers/style.py:25) and sharded across data-parallel ranks.  The trained float2 of row r is
+// packed[2r .. 2r+1]; lane0 = 0 (density table, mask 0x3) or 2 (colour table, mask 0xC).
+
+__device__ __forceinline__ float2 lanes_of(const float4 &p, uint32_t lane0) {
+    return lane0 ? make_float2(p.z, p.w) : make_float2(p.x, p.y);
+}
+
+__device__ __forceinline__ void store_half_row(_Float16 *half_copy, uint64_t r, const float4 &p) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    h4 h;
+    h[0] = (_Float16)p.x; h[1] = (_Float16)p.y; h[2] = (_Float16)p.z; h[3] = (_Float16)p.w;
+    reinterpret_cast<h4 *>(half_copy)[r] = h;
+}
+
+// trained lanes of every row -> packed; all four lanes of the row's gradient zeroed (untrained gradients are still zeroed)
+__global__ void __launch_bounds__(256)
+k_lanes_pack(float *__restrict__ g, uint64_t rows, uint32_t lane0, float *__restrict__ packed) {
+    for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < rows; r += (uint64_t)gridDim.x * blockDim.x) {
+        const float4 v = reinterpret_cast<const float4 *>(g)[r];
+        reinterpret_cast<float2 *>(packed)[r] = lanes_of(v, lane0);
+        reinterpret_cast<float4 *>(g)[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+struct LanesArgs {
+    AdamArgs s;                      // scalars (+ dyn); its pointers are unused
+    float *arena;                    // interleaved table rows, updated in place (trained lanes only)
+    _Float16 *half_copy;             // f16 gather copy of the rows or NULL
+    const float *g;                  // packed gradient of rows [row_lo, row_hi): g[2 (r - row_lo) + l]
+    float *m, *v;                    // packed moments, same indexing
+    float *ema;                      // EMA shadow of all four lanes of rows [row_lo, row_hi): ema[r - row_lo] (float4) or NULL
+    float *out;                      // packed updated parameters, same indexing as g (may alias g)
+    uint64_t row_lo, row_hi;
+    uint32_t lane0;
+};
+
+// k_adam on the trained lanes of rows [row_lo, row_hi): the same adam_one and the same EMA expression over the whole row
+// (k_adam's EMA moves all four elements of a region's float4), so a world of one equals nsr_adam_step* with elem_mask4 bit for bit
+__global__ void __launch_bounds__(256)
+k_lanes_adam(LanesArgs a) {
+    const bool skip = adam_scalars(a.s);
+    const uint64_t n = a.row_hi - a.row_lo;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = a.row_lo + i;
+        float4 p = reinterpret_cast<const float4 *>(a.arena)[r];
+        if (!skip) {
+            const float2 g = reinterpret_cast<const float2 *>(a.g)[i];
+            float2 m = reinterpret_cast<const float2 *>(a.m)[i];
+            float2 v = reinterpret_cast<const float2 *>(a.v)[i];
+            if (a.lane0) {
+                adam_one(p.z, g.x, m.x, v.x, a.s);
+                adam_one(p.w, g.y, m.y, v.y, a.s);
+            } else {
+                adam_one(p.x, g.x, m.x, v.x, a.s);
+                adam_one(p.y, g.y, m.y, v.y, a.s);
+            }
+            reinterpret_cast<float4 *>(a.arena)[r] = p;
+            reinterpret_cast<float2 *>(a.m)[i] = m;
+            reinterpret_cast<float2 *>(a.v)[i] = v;
+            if (a.half_copy) store_half_row(a.half_copy, r, p);
+        }
+        reinterpret_cast<float2 *>(a.out)[i] = lanes_of(p, a.lane0);
+        if (a.ema) {
+            float4 e = reinterpret_cast<float4 *>(a.ema)[i];
+            const float k = 1.0f - a.s.ema_decay;
+            e.x -= k * (e.x - p.x); e.y -= k * (e.y - p.y); e.z -= k * (e.z - p.z); e.w -= k * (e.w - p.w);
+            reinterpret_cast<float4 *>(a.ema)[i] = e;
+        }
+    }
+}
+
+// gathered packed parameters of rows [row_lo, row_hi) -> their arena lanes and all four lanes of the f16 copy
+__global__ void __launch_bounds__(256)
+k_lanes_unpack(const float *__restrict__ packed, uint64_t row_lo, uint64_t row_hi, uint32_t lane0, float *__restrict__ arena,
+               _Float16 *__restrict__ half_copy) {
+    for (uint64_t r = row_lo + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < row_hi; r += (uint64_t)gridDim.x * blockDim.x) {
+        const float2 q = reinterpret_cast<const float2 *>(packed)[r];
+        float4 p = reinterpret_cast<const float4 *>(arena)[r];
+        if (lane0) { p.z = q.x; p.w = q.y; } else { p.x = q.x; p.y = q.y; }
+        reinterpret_cast<float4 *>(arena)[r] = p;
+        if (half_copy) store_half_row(half_copy, r, p);
+    }
+}
+
+static int lane0_of(uint32_t lane_mask) { return lane_mask == 0x3u ? 0 : lane_mask == 0xCu ? 2 : -1; }
+
+extern "C" int nsr_lanes_pack(float *grad_arena, uint64_t rows, uint32_t lane_mask, float *packed, nsr_stream_t stream) {
+    if (rows == 0) return NSR_OK;
+    NSR_CHECK_PTR(grad_arena); NSR_CHECK_PTR(packed);
+    const int lane0 = lane0_of(lane_mask);
+    if (lane0 < 0 || ((uintptr_t)grad_arena & 15u) || ((uintptr_t)packed & 7u)) return NSR_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_lanes_pack, dim3(nsr_grid_1d(rows, 256)), dim3(256), 0, (hipStream_t)stream, grad_arena, rows,
+                       (uint32_t)lane0, packed);
+    return nsr_launch_status();
+}
+
+static int lanes_adam_launch(LanesArgs &a, float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq,
+                             float *ema, float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, hipStream_t s) {
+    if (row_hi < row_lo) return NSR_ERR_INVALID_ARG;
+    if (row_hi == row_lo) return NSR_OK;
+    if (!arena || !grad || !exp_avg || !exp_avg_sq || !packed_out) return NSR_ERR_INVALID_ARG;
+    const int lane0 = lane0_of(lane_mask);
+    const uintptr_t al8 = (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)packed_out | (uintptr_t)half_copy;
+    if (lane0 < 0 || (al8 & 7u) || (((uintptr_t)arena | (uintptr_t)ema) & 15u)) return NSR_ERR_INVALID_ARG;
+    a.arena = arena; a.half_copy = (_Float16 *)half_copy; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.ema = ema;
+    a.out = packed_out; a.row_lo = row_lo; a.row_hi = row_hi; a.lane0 = (uint32_t)lane0;
+    a.s.p = a.s.g = a.s.m = a.s.v = nullptr; a.s.ema = ema; a.s.half_copy = nullptr; a.s.n = a.s.half_n = 0; a.s.mask4 = lane_mask;
+    hipLaunchKernelGGL(k_lanes_adam, dim3(nsr_grid_1d(row_hi - row_lo, 256)), dim3(256), 0, s, a);
+    return nsr_launch_status();
+}
+
+extern "C" int nsr_lanes_adam(float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq, float *ema,
+                              float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, float lr, float beta1,
+                              float beta2, float eps, float grad_scale_inv, float ema_decay, uint32_t step, nsr_stream_t stream) {
+    if (step == 0) return NSR_ERR_INVALID_ARG;
+    LanesArgs a;
+    a.s.beta1 = beta1; a.s.beta2 = beta2; a.s.eps = eps; a.s.grad_scale_inv = grad_scale_inv; a.s.ema_decay = ema_decay;
+    a.s.dyn = nullptr;
+    adam_host_bias_corrections(a.s, lr, step);
+    return lanes_adam_launch(a, arena, half_copy, grad, exp_avg, exp_avg_sq, ema, packed_out, row_lo, row_hi, lane_mask,
+                             (hipStream_t)stream);
+}
+
+extern "C" int nsr_lanes_adam_scaled(float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq,
+                                     float *ema, float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask,
+                                     float beta1, float beta2, float eps, const void *scaler_state, nsr_stream_t stream) {
+    NSR_CHECK_PTR(scaler_state);
+    if ((uintptr_t)scaler_state & 3u) return NSR_ERR_INVALID_ARG;
+    LanesArgs a;
+    a.s.beta1 = beta1; a.s.beta2 = beta2; a.s.eps = eps; a.s.ema_decay = 0.0f;   // (read from the state in the kernel)
+    a.s.step_size = 0.0f; a.s.inv_sqrt_bc2 = 1.0f; a.s.grad_scale_inv = 1.0f;
+    a.s.dyn = (const uint32_t *)scaler_state;
+    return lanes_adam_launch(a, arena, half_copy, grad, exp_avg, exp_avg_sq, ema, packed_out, row_lo, row_hi, lane_mask,
+                             (hipStream_t)stream);
+}
+
+extern "C" int nsr_lanes_unpack(const float *packed, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, float *arena,
+                                void *half_copy, nsr_stream_t stream) {
+    if (row_hi < row_lo) return NSR_ERR_INVALID_ARG;
+    if (row_hi == row_lo) return NSR_OK;
+    NSR_CHECK_PTR(packed); NSR_CHECK_PTR(arena);
+    const int lane0 = lane0_of(lane_mask);
+    if (lane0 < 0 || (((uintptr_t)packed | (uintptr_t)half_copy) & 7u) || ((uintptr_t)arena & 15u)) return NSR_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_lanes_unpack, dim3(nsr_grid_1d(row_hi - row_lo, 256)), dim3(256), 0, (hipStream_t)stream, packed, row_lo,
+                       row_hi, (uint32_t)lane0, arena, (_Float16 *)half_copy);
+    return nsr_launch_status();
 }

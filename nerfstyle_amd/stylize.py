@@ -121,7 +121,8 @@ def deferred_backprop_step(renderer, pose, image_loss: Callable, patch_size: int
     (requires_grad) -- and, with_classes, the class logits [H, W, nc] of the same pass -- to a scalar.
     Gradients accumulate into model.arena.grad.  Returns (loss value, rgb_map of pass 1).
     loss_scale: float or 0-dim device tensor (optim.LossScaler.scale_tensor).  optimizer: the FusedAdam that will step; at
-    world > 1 the all-reduce covers exactly what it trains (parallel.sync_gradients) -- None reduces the whole arena.
+    world > 1 the all-reduce covers exactly what it trains (parallel.sync_gradients) -- None reduces the whole arena; an
+    optimiser whose `reduces_gradients` is true (sharded_optim.ShardedFusedAdam) reduces them itself in its step.
     patch_graphs: a dict the caller keeps across iterations; when given, pass 2 replays one hipGraph per patch shape
     (graph.GraphedPatchBackward) instead of launching every patch's kernels from the host."""
     W, H = renderer.intr.size()
@@ -179,7 +180,7 @@ def deferred_backprop_step(renderer, pose, image_loss: Callable, patch_size: int
                 patch_graphs[key](pose_t, pix, g)
     for sd in sides[:nstreams - 1]:
         main.wait_stream(sd)
-    if world > 1:
+    if world > 1 and not getattr(optimizer, 'reduces_gradients', False):      # (ShardedFusedAdam reduces them itself)
         P.sync_gradients(renderer.model, optimizer=optimizer)
     return loss.detach(), rgb.detach()
 
@@ -223,6 +224,6 @@ def resident_backprop_step(renderer, pose, image_loss: Callable, loss_scale=1.0,
     (loss * loss_scale).backward()
     if out is not None:
         out['rgb_map'].backward(rgb.grad.reshape(-1, 3)[y0 * W:y1 * W])
-    if world > 1:
+    if world > 1 and not getattr(optimizer, 'reduces_gradients', False):      # (ShardedFusedAdam reduces them itself)
         P.sync_gradients(renderer.model, optimizer=optimizer)
     return loss.detach(), rgb.detach()
