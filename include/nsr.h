@@ -150,6 +150,17 @@ int nsr_recon_loss(const float *rgb_map, const float *classes, uint32_t N, uint3
                    const int64_t *target_cls, const int64_t *pix, float ce_lambda, float factor, const float *scale,
                    float *grad_rgb_map, float *grad_classes, float *loss_out, void *workspace, nsr_stream_t stream);
 
+/* Matting-Laplacian photorealism loss of Deep Photo Style Transfer, the reference's MattingLaplacian (loss.py:217-278,
+ * win_rad r, eps): loss_out[0] (device fp64) = trace(V M V^T), M the matting Laplacian of `target` over every (2r+1)^2
+ * window inside the image, V = v reshaped [3, H*W]; grad_v (may be NULL) [3,H,W] f32 = d loss / d v, rounded once.
+ * Matrix-free (no HW x HW matrix): inputs are read in f32 and every operation is fp64.  target, v [3,H,W] f32.
+ * r in {1, 2} (else NSR_ERR_UNSUPPORTED); H, W >= 2r+1.  No atomics: the value is summed in a fixed order (block partials +
+ * one-block final pass), so value and gradient are run-to-run identical.
+ * workspace: nsr_matting_laplacian_workspace_bytes(H, W, win_rad) bytes, 8-byte aligned. */
+uint64_t nsr_matting_laplacian_workspace_bytes(uint32_t H, uint32_t W, uint32_t win_rad);
+int nsr_matting_laplacian(const float *target, const float *v, uint32_t H, uint32_t W, uint32_t win_rad, double eps,
+                          double *loss_out, float *grad_v, void *workspace, nsr_stream_t stream);
+
 /* replaces march_rays (raymarching.h:17, raymarching.cu:1004-1130), inference. */
 int nsr_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t,
                    const float *rays_o, const float *rays_d, const float *z_hats, float bound,

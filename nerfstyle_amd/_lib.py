@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, 'libnsr_hip.so')
 
 NSR_F32, NSR_F16, NSR_BF16 = 0, 1, 2
 NSR_ACT_NONE, NSR_ACT_SIGMOID = 0, 1
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _DT = {torch.float32: NSR_F32, torch.float16: NSR_F16, torch.bfloat16: NSR_BF16}
 
@@ -22,6 +22,7 @@ u32 = ctypes.c_uint32
 u64 = ctypes.c_uint64
 i32 = ctypes.c_int
 f32 = ctypes.c_float
+f64 = ctypes.c_double
 
 
 class FieldDesc(ctypes.Structure):
@@ -53,6 +54,8 @@ SIGNATURES = {
     'nsr_render_train_backward': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, f32, vp, vp, vp]),
     'nsr_recon_loss_workspace_bytes': (u64, [u32]),
     'nsr_recon_loss': (i32, [vp, vp, u32, u32, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp]),
+    'nsr_matting_laplacian_workspace_bytes': (u64, [u32, u32, u32]),
+    'nsr_matting_laplacian': (i32, [vp, vp, u32, u32, u32, f64, vp, vp, vp, vp]),
     'nsr_march_rays': (i32, [u32, u32, vp, vp, vp, vp, vp, f32, f32, u32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp,
                              vp]),
     'nsr_composite_rays': (i32, [u32, u32, f32, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp]),

@@ -16,6 +16,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .matting import MattingLaplacian  # noqa: F401  (loss.py:217-278; HIP, nerfstyle_amd/matting.py)
+
 
 def compute_centroid(mask: torch.Tensor) -> torch.Tensor:
     """loss.py:15-21: (row, column) centroid of a boolean mask, normalised by the mask's height / width."""

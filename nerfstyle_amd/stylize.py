@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from . import parallel as P
 from .common import Box2D
+from .matting import MattingLaplacian
 
 
 class StyleCriterion:
@@ -32,16 +33,23 @@ class StyleCriterion:
     frame, the ground-truth frame and the style image; content = MSE(rendered, ground-truth features) * content_lambda,
     style = SemanticStyleLoss(rendered features | class predictions) * style_lambda (cfgs/training/style.yaml:
     content_lambda 0.001, style_lambda 1.0).  The features of the fixed images are computed once and cached (the
-    reference re-extracts target and style features every iteration, style.py:88-89)."""
+    reference re-extracts target and style features every iteration, style.py:88-89).
+
+    photo_lambda != 0 adds the photorealism term photo_lambda * MattingLaplacian(target, rendered) (the reference's
+    commented-out style.py:98,102; photo_lambda in config.py:440), evaluated in fp64 by matting.py and cast to the dtype of
+    the other terms.  0 (the default, cfgs/training/style.yaml:11) launches nothing."""
 
     def __init__(self, fx, style_loss, content_lambda: float = 0.001, style_lambda: float = 1.0, content_feat: str = 'relu3',
-                 amp_dtype=None):
+                 amp_dtype=None, photo_lambda: float = 0.0):
         """amp_dtype: torch.float16 / torch.bfloat16 runs the loss under torch.autocast, as the reference does with
         enable_amp (cfgs/training/default.yaml:16, style.py:182-184: convolutions and the feature products in half
         precision, reductions in fp32); None = fp32."""
         self.fx, self.style_loss = fx, style_loss
         self.content_lambda, self.style_lambda, self.content_feat = content_lambda, style_lambda, content_feat
         self.amp_dtype = amp_dtype
+        self.photo_lambda = float(photo_lambda)
+        self.photo_loss = MattingLaplacian() if self.photo_lambda != 0.0 else None       # style.py:54
+        self.last_photo = None      # detached fp64 device tensor photo_lambda * L of the last call (never read on the host)
         self._target_feats = {}
 
     def _autocast(self, device):
@@ -66,7 +74,12 @@ class StyleCriterion:
             preds = torch.argmax(classes_hwc, dim=-1)                                   # style.py:85
             content = F.mse_loss(rgb_feats[self.content_feat], tgt) * self.content_lambda
             style = self.style_loss(rgb_feats, None, preds, it) * self.style_lambda
-        return content + style, content.detach(), style.detach()
+        total = content + style
+        if self.photo_loss is not None:
+            photo = self.photo_loss(target_chw, rgb_hw3.permute(2, 0, 1)) * self.photo_lambda      # style.py:98,102 (fp64)
+            self.last_photo = photo.detach()
+            total = total + photo.to(total.dtype)
+        return total, content.detach(), style.detach()
 
 
 def patch_list(w: int, h: int, patch: int) -> List[Box2D]:
