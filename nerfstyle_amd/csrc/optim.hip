@@ -4,13 +4,18 @@
 // 16-byte accesses instead of ~10 elementwise launches over 25 M parameters.
 #include "nsr_common.h"
 
+// the scalars of one step, shared by the flat (k_adam) and the lane-packed (k_lanes_adam) kernel
+struct AdamScalars {
+    float beta1, beta2, eps, step_size, inv_sqrt_bc2, grad_scale_inv, ema_decay;
+    const uint32_t *dyn;             // device-side scaler state (nsr_scaler_update) or NULL: host-side scalars above
+};
+
 struct AdamArgs {
     float *p, *g, *m, *v, *ema;
     _Float16 *half_copy;
     uint64_t n, half_n;              // half_copy covers the first half_n elements (the tables of a whole-arena launch)
-    float beta1, beta2, eps, step_size, inv_sqrt_bc2, grad_scale_inv, ema_decay;
     uint32_t mask4;
-    const uint32_t *dyn;             // device-side scaler state (nsr_scaler_update) or NULL: host-side scalars above
+    AdamScalars s;
 };
 
 // Device-side GradScaler + step bookkeeping (torch.cuda.amp.GradScaler's policy, trainers/base.py:228,420-425), 16 words:
@@ -22,7 +27,7 @@ struct AdamArgs {
 enum { SC_SCALE = 0, SC_TRACKER = 1, SC_FOUND = 2, SC_STEP = 3, SC_SKIPPED = 4, SC_EMA_N = 5, SC_SKIP = 8, SC_STEP_SIZE = 9,
        SC_INV_BC2 = 10, SC_INV_SCALE = 11, SC_LR = 12, SC_EMA_DECAY = 13 };
 
-__device__ __forceinline__ float adam_one(float &p, float g, float &m, float &v, const AdamArgs &a) {
+__device__ __forceinline__ float adam_one(float &p, float g, float &m, float &v, const AdamScalars &a) {
     g *= a.grad_scale_inv;
     m = a.beta1 * m + (1.0f - a.beta1) * g;          // torch: exp_avg.lerp_(grad, 1 - beta1)
     v = a.beta2 * v + (1.0f - a.beta2) * g * g;      // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
@@ -32,13 +37,31 @@ __device__ __forceinline__ float adam_one(float &p, float g, float &m, float &v,
 }
 
 // this step's scalars from the device-side scaler state (no-op on the host-scalar path); true: the step is skipped
-__device__ __forceinline__ bool adam_scalars(AdamArgs &a) {
+__device__ __forceinline__ bool adam_scalars(AdamScalars &a) {
     if (!a.dyn) return false;
     a.step_size = __uint_as_float(a.dyn[SC_STEP_SIZE]);
     a.inv_sqrt_bc2 = __uint_as_float(a.dyn[SC_INV_BC2]);
     a.grad_scale_inv = __uint_as_float(a.dyn[SC_INV_SCALE]);
-    if (a.ema) a.ema_decay = __uint_as_float(a.dyn[SC_EMA_DECAY]);
+    a.ema_decay = __uint_as_float(a.dyn[SC_EMA_DECAY]);          // (read only where there is an EMA shadow)
     return a.dyn[SC_SKIP] != 0u;
+}
+
+// torch_ema: shadow.sub_((1 - decay) * (shadow - param)), k = 1 - decay
+__device__ __forceinline__ void ema_move(float &e, float p, float k) { e -= k * (e - p); }
+
+__device__ __forceinline__ void ema_move(float *ema, uint64_t i, const float4 &p, float decay) {
+    float4 e = reinterpret_cast<float4 *>(ema)[i];
+    const float k = 1.0f - decay;
+    ema_move(e.x, p.x, k); ema_move(e.y, p.y, k); ema_move(e.z, p.z, k); ema_move(e.w, p.w, k);
+    reinterpret_cast<float4 *>(ema)[i] = e;
+}
+
+// four parameters -> the f16 gather copy (one table row of the interleaved layout)
+__device__ __forceinline__ void store_half_row(_Float16 *half_copy, uint64_t r, const float4 &p) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    h4 h;
+    h[0] = (_Float16)p.x; h[1] = (_Float16)p.y; h[2] = (_Float16)p.z; h[3] = (_Float16)p.w;
+    reinterpret_cast<h4 *>(half_copy)[r] = h;
 }
 
 // any non-finite value among the trained elements -> found_inf (GradScaler.unscale_'s check, one streaming pass)
@@ -113,24 +136,18 @@ __global__ void k_scaler_update(uint32_t *st, float lr_base, float lr_decay_step
 __global__ void __launch_bounds__(256)
 k_adam(AdamArgs a) {
     const uint64_t n4 = a.n / 4;
-    const bool skip = adam_scalars(a);
+    const bool skip = adam_scalars(a.s);
     if (skip) {
         // GradScaler skipped optimizer.step(): parameters and moments stay; the gradient is cleared (the reference's
         // zero_grad at the top of the next iteration) and the EMA still moves (ema.update() is unconditional, base.py:426)
         for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * blockDim.x) {
             reinterpret_cast<float4 *>(a.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (a.ema) {
-                const float4 p = reinterpret_cast<float4 *>(a.p)[i];
-                float4 e = reinterpret_cast<float4 *>(a.ema)[i];
-                const float k = 1.0f - a.ema_decay;
-                e.x -= k * (e.x - p.x); e.y -= k * (e.y - p.y); e.z -= k * (e.z - p.z); e.w -= k * (e.w - p.w);
-                reinterpret_cast<float4 *>(a.ema)[i] = e;
-            }
+            if (a.ema) ema_move(a.ema, i, reinterpret_cast<float4 *>(a.p)[i], a.s.ema_decay);
         }
         if (blockIdx.x == 0 && threadIdx.x < (a.n & 3u)) {
             const uint64_t i = n4 * 4 + threadIdx.x;
             a.g[i] = 0.0f;
-            if (a.ema) a.ema[i] -= (1.0f - a.ema_decay) * (a.ema[i] - a.p[i]);
+            if (a.ema) ema_move(a.ema[i], a.p[i], 1.0f - a.s.ema_decay);
         }
         return;
     }
@@ -139,46 +156,46 @@ k_adam(AdamArgs a) {
         const float4 g = reinterpret_cast<float4 *>(a.g)[i];
         float4 m = reinterpret_cast<float4 *>(a.m)[i];
         float4 v = reinterpret_cast<float4 *>(a.v)[i];
-        if (a.mask4 & 1u) adam_one(p.x, g.x, m.x, v.x, a);
-        if (a.mask4 & 2u) adam_one(p.y, g.y, m.y, v.y, a);
-        if (a.mask4 & 4u) adam_one(p.z, g.z, m.z, v.z, a);
-        if (a.mask4 & 8u) adam_one(p.w, g.w, m.w, v.w, a);
+        if (a.mask4 & 1u) adam_one(p.x, g.x, m.x, v.x, a.s);
+        if (a.mask4 & 2u) adam_one(p.y, g.y, m.y, v.y, a.s);
+        if (a.mask4 & 4u) adam_one(p.z, g.z, m.z, v.z, a.s);
+        if (a.mask4 & 8u) adam_one(p.w, g.w, m.w, v.w, a.s);
         reinterpret_cast<float4 *>(a.p)[i] = p;
         reinterpret_cast<float4 *>(a.m)[i] = m;
         reinterpret_cast<float4 *>(a.v)[i] = v;
         reinterpret_cast<float4 *>(a.g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (a.ema) {
-            float4 e = reinterpret_cast<float4 *>(a.ema)[i];
-            const float k = 1.0f - a.ema_decay;   // torch_ema: shadow.sub_((1 - decay) * (shadow - param))
-            e.x -= k * (e.x - p.x); e.y -= k * (e.y - p.y); e.z -= k * (e.z - p.z); e.w -= k * (e.w - p.w);
-            reinterpret_cast<float4 *>(a.ema)[i] = e;
-        }
-        if (a.half_copy && i * 4 < a.half_n) {
-            typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-            h4 h;
-            h[0] = (_Float16)p.x; h[1] = (_Float16)p.y; h[2] = (_Float16)p.z; h[3] = (_Float16)p.w;
-            reinterpret_cast<h4 *>(a.half_copy)[i] = h;
-        }
+        if (a.ema) ema_move(a.ema, i, p, a.s.ema_decay);
+        if (a.half_copy && i * 4 < a.half_n) store_half_row(a.half_copy, i, p);
     }
     if (blockIdx.x == 0 && threadIdx.x < (a.n & 3u)) {
         const uint64_t i = n4 * 4 + threadIdx.x;
         float p = a.p[i], m = a.m[i], v = a.v[i];
-        if (a.mask4 & (1u << (i & 3u))) adam_one(p, a.g[i], m, v, a);
+        if (a.mask4 & (1u << (i & 3u))) adam_one(p, a.g[i], m, v, a.s);
         a.p[i] = p; a.m[i] = m; a.v[i] = v; a.g[i] = 0.0f;
-        if (a.ema) a.ema[i] -= (1.0f - a.ema_decay) * (a.ema[i] - p);
+        if (a.ema) ema_move(a.ema[i], p, 1.0f - a.s.ema_decay);
         if (a.half_copy && i < a.half_n) a.half_copy[i] = (_Float16)p;
     }
 }
 
 // host-scalar path: Adam's bias corrections for step `step`, in double precision as torch computes them
-static void adam_host_bias_corrections(AdamArgs &a, float lr, uint32_t step) {
-    const double bc1 = 1.0 - pow((double)a.beta1, (double)step), bc2 = 1.0 - pow((double)a.beta2, (double)step);
-    a.step_size = (float)((double)lr / bc1);
-    a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+static AdamScalars host_scalars(float lr, float beta1, float beta2, float eps, float grad_scale_inv, float ema_decay, uint32_t step) {
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    return AdamScalars{beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), grad_scale_inv, ema_decay, nullptr};
 }
 
-static int adam_launch(AdamArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL(k_adam, dim3(nsr_grid_1d(a.n / 4 + 1, 256)), dim3(256), 0, s, a);
+// device-state path: step size, bias correction, 1 / scale and the EMA decay are read from the state in the kernel
+static AdamScalars device_scalars(float beta1, float beta2, float eps, const void *scaler_state) {
+    return AdamScalars{beta1, beta2, eps, 0.0f, 1.0f, 1.0f, 0.0f, (const uint32_t *)scaler_state};
+}
+
+static int adam_launch(float *params, float *grads, float *exp_avg, float *exp_avg_sq, float *ema, void *half_copy, uint64_t n,
+                       uint64_t half_n, uint32_t elem_mask4, const AdamScalars &sc, nsr_stream_t stream) {
+    NSR_CHECK_PTR(params); NSR_CHECK_PTR(grads); NSR_CHECK_PTR(exp_avg); NSR_CHECK_PTR(exp_avg_sq);
+    const uintptr_t al = (uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq |
+                         (uintptr_t)ema | (uintptr_t)half_copy;
+    if (al & 15u) return NSR_ERR_INVALID_ARG;
+    const AdamArgs a{params, grads, exp_avg, exp_avg_sq, ema, (_Float16 *)half_copy, n, half_n, elem_mask4 & 0xFu, sc};
+    hipLaunchKernelGGL(k_adam, dim3(nsr_grid_1d(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return nsr_launch_status();
 }
 
@@ -186,18 +203,9 @@ extern "C" int nsr_adam_step(float *params, float *grads, float *exp_avg, float 
                              uint64_t n, float lr, float beta1, float beta2, float eps, float grad_scale_inv, float ema_decay,
                              uint32_t step, uint32_t elem_mask4, nsr_stream_t stream) {
     if (n == 0) return NSR_OK;
-    NSR_CHECK_PTR(params); NSR_CHECK_PTR(grads); NSR_CHECK_PTR(exp_avg); NSR_CHECK_PTR(exp_avg_sq);
     if (step == 0) return NSR_ERR_INVALID_ARG;
-    const uintptr_t al = (uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq |
-                         (uintptr_t)ema | (uintptr_t)half_copy;
-    if (al & 15u) return NSR_ERR_INVALID_ARG;
-    AdamArgs a;
-    a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.ema = ema; a.half_copy = (_Float16 *)half_copy; a.n = n;
-    a.half_n = n; a.dyn = nullptr;
-    a.mask4 = elem_mask4 & 0xFu;
-    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.grad_scale_inv = grad_scale_inv; a.ema_decay = ema_decay;
-    adam_host_bias_corrections(a, lr, step);
-    return adam_launch(a, (hipStream_t)stream);
+    return adam_launch(params, grads, exp_avg, exp_avg_sq, ema, half_copy, n, n, elem_mask4,
+                       host_scalars(lr, beta1, beta2, eps, grad_scale_inv, ema_decay, step), stream);
 }
 
 extern "C" int nsr_grad_check(const float *grads, uint64_t n, uint32_t elem_mask4, void *scaler_state, nsr_stream_t stream) {
@@ -226,17 +234,10 @@ extern "C" int nsr_adam_step_scaled(float *params, float *grads, float *exp_avg,
                                     uint64_t n, uint64_t half_n, float beta1, float beta2, float eps, uint32_t elem_mask4,
                                     const void *scaler_state, nsr_stream_t stream) {
     if (n == 0) return NSR_OK;
-    NSR_CHECK_PTR(params); NSR_CHECK_PTR(grads); NSR_CHECK_PTR(exp_avg); NSR_CHECK_PTR(exp_avg_sq); NSR_CHECK_PTR(scaler_state);
-    const uintptr_t al = (uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq |
-                         (uintptr_t)ema | (uintptr_t)half_copy;
-    if ((al & 15u) || ((uintptr_t)scaler_state & 3u) || half_n > n || (half_n & 3u)) return NSR_ERR_INVALID_ARG;
-    AdamArgs a;
-    a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.ema = ema; a.half_copy = (_Float16 *)half_copy; a.n = n;
-    a.half_n = half_n; a.dyn = (const uint32_t *)scaler_state;
-    a.mask4 = elem_mask4 & 0xFu;
-    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.ema_decay = 0.0f;           // (read from the state in the kernel)
-    a.step_size = 0.0f; a.inv_sqrt_bc2 = 1.0f; a.grad_scale_inv = 1.0f;
-    return adam_launch(a, (hipStream_t)stream);
+    NSR_CHECK_PTR(scaler_state);
+    if (((uintptr_t)scaler_state & 3u) || half_n > n || (half_n & 3u)) return NSR_ERR_INVALID_ARG;
+    return adam_launch(params, grads, exp_avg, exp_avg_sq, ema, half_copy, n, half_n, elem_mask4,
+                       device_scalars(beta1, beta2, eps, scaler_state), stream);
 }
 
 // ---- lane-packed tables: one hash table of the interleaved rows (tables[row][enc][feat], 16 B per row), trained alone ----
@@ -245,13 +246,6 @@ extern "C" int nsr_adam_step_scaled(float *params, float *grads, float *exp_avg,
 
 __device__ __forceinline__ float2 lanes_of(const float4 &p, uint32_t lane0) {
     return lane0 ? make_float2(p.z, p.w) : make_float2(p.x, p.y);
-}
-
-__device__ __forceinline__ void store_half_row(_Float16 *half_copy, uint64_t r, const float4 &p) {
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    h4 h;
-    h[0] = (_Float16)p.x; h[1] = (_Float16)p.y; h[2] = (_Float16)p.z; h[3] = (_Float16)p.w;
-    reinterpret_cast<h4 *>(half_copy)[r] = h;
 }
 
 // trained lanes of every row -> packed; all four lanes of the row's gradient zeroed (untrained gradients are still zeroed)
@@ -265,7 +259,6 @@ k_lanes_pack(float *__restrict__ g, uint64_t rows, uint32_t lane0, float *__rest
 }
 
 struct LanesArgs {
-    AdamArgs s;                      // scalars (+ dyn); its pointers are unused
     float *arena;                    // interleaved table rows, updated in place (trained lanes only)
     _Float16 *half_copy;             // f16 gather copy of the rows or NULL
     const float *g;                  // packed gradient of rows [row_lo, row_hi): g[2 (r - row_lo) + l]
@@ -274,6 +267,7 @@ struct LanesArgs {
     float *out;                      // packed updated parameters, same indexing as g (may alias g)
     uint64_t row_lo, row_hi;
     uint32_t lane0;
+    AdamScalars s;
 };
 
 // k_adam on the trained lanes of rows [row_lo, row_hi): the same adam_one and the same EMA expression over the whole row
@@ -302,12 +296,7 @@ k_lanes_adam(LanesArgs a) {
             if (a.half_copy) store_half_row(a.half_copy, r, p);
         }
         reinterpret_cast<float2 *>(a.out)[i] = lanes_of(p, a.lane0);
-        if (a.ema) {
-            float4 e = reinterpret_cast<float4 *>(a.ema)[i];
-            const float k = 1.0f - a.s.ema_decay;
-            e.x -= k * (e.x - p.x); e.y -= k * (e.y - p.y); e.z -= k * (e.z - p.z); e.w -= k * (e.w - p.w);
-            reinterpret_cast<float4 *>(a.ema)[i] = e;
-        }
+        if (a.ema) ema_move(a.ema, i, p, a.s.ema_decay);
     }
 }
 
@@ -336,18 +325,17 @@ extern "C" int nsr_lanes_pack(float *grad_arena, uint64_t rows, uint32_t lane_ma
     return nsr_launch_status();
 }
 
-static int lanes_adam_launch(LanesArgs &a, float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq,
-                             float *ema, float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, hipStream_t s) {
+static int lanes_adam_launch(float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq, float *ema,
+                             float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, const AdamScalars &sc,
+                             nsr_stream_t stream) {
     if (row_hi < row_lo) return NSR_ERR_INVALID_ARG;
     if (row_hi == row_lo) return NSR_OK;
     if (!arena || !grad || !exp_avg || !exp_avg_sq || !packed_out) return NSR_ERR_INVALID_ARG;
     const int lane0 = lane0_of(lane_mask);
     const uintptr_t al8 = (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)packed_out | (uintptr_t)half_copy;
     if (lane0 < 0 || (al8 & 7u) || (((uintptr_t)arena | (uintptr_t)ema) & 15u)) return NSR_ERR_INVALID_ARG;
-    a.arena = arena; a.half_copy = (_Float16 *)half_copy; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.ema = ema;
-    a.out = packed_out; a.row_lo = row_lo; a.row_hi = row_hi; a.lane0 = (uint32_t)lane0;
-    a.s.p = a.s.g = a.s.m = a.s.v = nullptr; a.s.ema = ema; a.s.half_copy = nullptr; a.s.n = a.s.half_n = 0; a.s.mask4 = lane_mask;
-    hipLaunchKernelGGL(k_lanes_adam, dim3(nsr_grid_1d(row_hi - row_lo, 256)), dim3(256), 0, s, a);
+    const LanesArgs a{arena, (_Float16 *)half_copy, grad, exp_avg, exp_avg_sq, ema, packed_out, row_lo, row_hi, (uint32_t)lane0, sc};
+    hipLaunchKernelGGL(k_lanes_adam, dim3(nsr_grid_1d(row_hi - row_lo, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return nsr_launch_status();
 }
 
@@ -355,12 +343,8 @@ extern "C" int nsr_lanes_adam(float *arena, void *half_copy, const float *grad, 
                               float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, float lr, float beta1,
                               float beta2, float eps, float grad_scale_inv, float ema_decay, uint32_t step, nsr_stream_t stream) {
     if (step == 0) return NSR_ERR_INVALID_ARG;
-    LanesArgs a;
-    a.s.beta1 = beta1; a.s.beta2 = beta2; a.s.eps = eps; a.s.grad_scale_inv = grad_scale_inv; a.s.ema_decay = ema_decay;
-    a.s.dyn = nullptr;
-    adam_host_bias_corrections(a.s, lr, step);
-    return lanes_adam_launch(a, arena, half_copy, grad, exp_avg, exp_avg_sq, ema, packed_out, row_lo, row_hi, lane_mask,
-                             (hipStream_t)stream);
+    return lanes_adam_launch(arena, half_copy, grad, exp_avg, exp_avg_sq, ema, packed_out, row_lo, row_hi, lane_mask,
+                             host_scalars(lr, beta1, beta2, eps, grad_scale_inv, ema_decay, step), stream);
 }
 
 extern "C" int nsr_lanes_adam_scaled(float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq,
@@ -368,12 +352,8 @@ extern "C" int nsr_lanes_adam_scaled(float *arena, void *half_copy, const float 
                                      float beta1, float beta2, float eps, const void *scaler_state, nsr_stream_t stream) {
     NSR_CHECK_PTR(scaler_state);
     if ((uintptr_t)scaler_state & 3u) return NSR_ERR_INVALID_ARG;
-    LanesArgs a;
-    a.s.beta1 = beta1; a.s.beta2 = beta2; a.s.eps = eps; a.s.ema_decay = 0.0f;   // (read from the state in the kernel)
-    a.s.step_size = 0.0f; a.s.inv_sqrt_bc2 = 1.0f; a.s.grad_scale_inv = 1.0f;
-    a.s.dyn = (const uint32_t *)scaler_state;
-    return lanes_adam_launch(a, arena, half_copy, grad, exp_avg, exp_avg_sq, ema, packed_out, row_lo, row_hi, lane_mask,
-                             (hipStream_t)stream);
+    return lanes_adam_launch(arena, half_copy, grad, exp_avg, exp_avg_sq, ema, packed_out, row_lo, row_hi, lane_mask,
+                             device_scalars(beta1, beta2, eps, scaler_state), stream);
 }
 
 extern "C" int nsr_lanes_unpack(const float *packed, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask, float *arena,

@@ -118,10 +118,7 @@ class GraphedRenderStep:
         s.wait_stream(torch.cuda.current_stream())
         if self.optimizer is not None:
             # the scaler state lives on the device before capture (no allocation / upload inside it), and the EMA count moves there
-            self.scaler.state_on(self.r.device)
-            if getattr(self.optimizer, '_scaler', None) is not self.scaler:
-                self.scaler.adopt_ema_updates(self.optimizer.ema_updates, self.r.device)
-                self.optimizer._scaler = self.scaler
+            self.optimizer.attach_scaler(self.scaler, self.r.device)
         with torch.cuda.stream(s):
             for _ in range(self._warmup):
                 self._body(with_optimizer=False)   # warm-up renders only: no parameter update, no step counted

@@ -15,6 +15,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .optim import single_trained_table
+
 
 def env_world():
     return int(os.environ.get('RANK', 0)), int(os.environ.get('LOCAL_RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -94,8 +96,8 @@ def sync_gradients(model, optimizer=None, only_color_table=None):
     half = None
     if only_color_table:
         half = 1
-    elif only_color_table is None and optimizer is not None and not optimizer.nets and optimizer.table_mask in (0x3, 0xC):
-        half = 0 if optimizer.table_mask == 0x3 else 1
+    elif only_color_table is None and optimizer is not None:
+        half = single_trained_table(optimizer.table_mask, optimizer.nets)
     if half is None:
         return all_reduce_sum_(g)
     part = g[:model.table_elems].view(model.rows, 2, 2)[:, half, :]
@@ -133,9 +135,7 @@ def sync_gradients_async(model, optimizer=None, buckets: int = 1) -> _GradSync:
     g = model._ensure_grad()
     if world_size() == 1:
         return _GradSync([])
-    half = None
-    if optimizer is not None and not optimizer.nets and optimizer.table_mask in (0x3, 0xC):
-        half = 0 if optimizer.table_mask == 0x3 else 1
+    half = single_trained_table(optimizer.table_mask, optimizer.nets) if optimizer is not None else None
     if half is None:
         flat, unpack = g, None
     else:

@@ -1,7 +1,9 @@
 """Data-parallel optimiser step sharded across ranks (SURVEY.md sections 5 and 8e: reduce-scatter + all-gather).
 
-`ShardedFusedAdam` takes the constructor arguments and the `step(grad_scale=..., scaler=..., lr_decay_steps=...)` semantics
-of `optim.FusedAdam`, but every rank checks, steps and keeps Adam / EMA state for 1/N of the trained elements only:
+`ShardedFusedAdam` is a sibling of `optim.FusedAdam` under `optim.AdamBase`, which gives both the same constructor
+bookkeeping, step scalars, scaler adoption, counters and state dicts.  It takes FusedAdam's constructor arguments and
+`step(grad_scale=..., scaler=..., lr_decay_steps=...)` semantics, but every rank checks, steps and keeps Adam / EMA state for
+1/N of the trained elements only:
 
     1. reduce-scatter of the gradient (the whole arena in place, or the packed lanes of one table: nsr_lanes_pack)
     2. scaler path: nsr_grad_check on the rank's reduced shard, MAX of found_inf over the ranks, nsr_scaler_update
@@ -27,7 +29,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .optim import FusedAdam, select_regions
+from .optim import AdamBase, select_regions, single_trained_table
 from .style_nerf import MLP_LAYOUT, MLP_PARAMS, StyleTCNerf
 
 SHARD_ALIGN = 16          # floats: 64 B, and a multiple of 4 keeps the element-mask phase of the interleaved rows
@@ -39,7 +41,7 @@ def trained_lane_mask(model: StyleTCNerf, keywords=None) -> int:
     mask, nets = select_regions(model, keywords)
     if mask == 0xF and len(nets) == len(MLP_LAYOUT):
         return 0xF
-    if not nets and mask in (0x3, 0xC):
+    if single_trained_table(mask, nets) is not None:
         return mask
     raise NotImplementedError(
         'ShardedFusedAdam supports keywords=None (everything) and one hash table without nets (e.g. keywords='
@@ -125,7 +127,7 @@ class _Reduction:
         self.work = self.after = None
 
 
-class ShardedFusedAdam:
+class ShardedFusedAdam(AdamBase):
     """FusedAdam with the optimiser step sharded across the data-parallel ranks (module docstring).  Construct it after the
     model has been moved to its device: the whole-arena set re-homes `model.arena` (the same nn.Parameter) and its gradient
     arena in padded storage, so that the collectives work in place."""
@@ -134,8 +136,6 @@ class ShardedFusedAdam:
 
     def __init__(self, model: StyleTCNerf, lr=1e-2, betas=(0.9, 0.999), eps=1e-15, keywords=None, ema_decay=None,
                  process_group=None):
-        self.model = model
-        self.table_mask, self.nets = select_regions(model, keywords)
         self.group = process_group
         if dist.is_initialized():
             world, rank = dist.get_world_size(process_group), dist.get_rank(process_group)
@@ -143,11 +143,7 @@ class ShardedFusedAdam:
         else:
             world, rank, self._staged = 1, 0, False
         self.geo = geo = ShardGeometry.of(model, keywords, world, rank)
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.base_lr = lr
-        self.step_count = 0
-        self.ema_decay = ema_decay
-        self.ema_updates = 0
+        super().__init__(model, lr, betas, eps, keywords, ema_decay)
         self._pending = None
         self._frozen = None               # packed set: full-layout moments of the untrained elements, as last loaded
         a = model.arena.detach()
@@ -155,7 +151,6 @@ class ShardedFusedAdam:
         self.exp_avg = torch.zeros(geo.chunk, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(geo.chunk, dtype=torch.float32, device=dev)
         if geo.packed:
-            model._ensure_grad()
             # gradient in (reduce-scatter), updated parameters out (all-gather): one buffer
             self._packed = torch.zeros(geo.padded, dtype=torch.float32, device=dev)
             # EMA of all four lanes of the rank's rows (FusedAdam's EMA moves every element of the rows it steps); the
@@ -170,10 +165,6 @@ class ShardedFusedAdam:
             if ema_decay is not None:
                 self.ema = torch.zeros(geo.chunk, dtype=torch.float32, device=dev)
                 self.ema[:geo.n].copy_(a[geo.lo:geo.hi])
-        model.train_density_table = bool(self.table_mask & 0x3)
-        model.train_color_table = bool(self.table_mask & 0xC)
-        model.train_mlps = bool(self.nets)
-        self.param_groups = [{'lr': lr, 'initial_lr': lr, 'params': [model.arena]}]
 
     # ---- storage -------------------------------------------------------------------------------------------------------
     def _home(self):
@@ -269,12 +260,9 @@ class ShardedFusedAdam:
         self._pending = _Reduction(self, work, zero_foreign)
         return self._pending
 
-    def _ema_decay_now(self):
-        return FusedAdam._ema_decay_now(self)
-
     @torch.no_grad()
     def step(self, grad_scale=1.0, scaler=None, lr_decay_steps=0.0):
-        """FusedAdam.step on this rank's shard, between a gradient reduce-scatter and a parameter all-gather."""
+        """FusedAdam's step on this rank's shard, between a gradient reduce-scatter and a parameter all-gather."""
         (self._pending or self.reduce_gradients_async()).wait()
         self._pending = None
         m, geo = self.model, self.geo
@@ -289,27 +277,19 @@ class ShardedFusedAdam:
             grad = self._grad_store[geo.slot:geo.slot + geo.chunk]
         st = None
         if scaler is None:
-            self.step_count += 1
-            decay = self._ema_decay_now()
-            lr = self.param_groups[0]['lr']
+            lr, decay, step = self._host_scalars()
         else:
-            if getattr(self, '_scaler', None) is not scaler:
-                scaler.adopt_ema_updates(self.ema_updates, a.device)
-                self._scaler = scaler
-            st = scaler.state_on(a.device)
+            st = self.attach_scaler(scaler, a.device)
             L.check(lib.nsr_grad_check(L.p(grad), geo.n, 0xF, L.p(st), L.stream()), 'grad_check')
             if geo.world > 1:
                 self._all_reduce_max(st[2:3])             # found_inf: every rank takes the same decision
-            L.check(lib.nsr_scaler_update(L.p(st), float(self.param_groups[0]['initial_lr']), float(lr_decay_steps),
-                                          float(self.betas[0]), float(self.betas[1]), float(scaler.growth_factor),
-                                          float(scaler.backoff_factor), int(scaler.growth_interval), int(scaler.enabled),
-                                          float(self.ema_decay) if self.ema is not None else -1.0, L.stream()), 'scaler_update')
+            self._scaler_update(scaler, st, lr_decay_steps)
         b1, b2, eps = float(self.betas[0]), float(self.betas[1]), float(self.eps)
         if geo.packed:
             args = (a.data_ptr(), half.data_ptr() if half is not None else None, L.p(grad), L.p(self.exp_avg),
                     L.p(self.exp_avg_sq), L.p(self.ema), L.p(grad), geo.row_lo, geo.row_hi, geo.lane_mask)
             if st is None:
-                L.check(lib.nsr_lanes_adam(*args, float(lr), b1, b2, eps, float(1.0 / grad_scale), float(decay), self.step_count,
+                L.check(lib.nsr_lanes_adam(*args, float(lr), b1, b2, eps, float(1.0 / grad_scale), float(decay), step,
                                            L.stream()), 'lanes_adam')
             else:
                 L.check(lib.nsr_lanes_adam_scaled(*args, b1, b2, eps, L.p(st), L.stream()), 'lanes_adam_scaled')
@@ -330,7 +310,7 @@ class ShardedFusedAdam:
                         L.check(lib.nsr_adam_step(
                             ptr(a, o), ptr(g, o), ptr(self.exp_avg, o - geo.lo), ptr(self.exp_avg_sq, o - geo.lo), ema(o),
                             hptr(o) if (half is not None and o < te) else None, k, float(lr), b1, b2, eps,
-                            float(1.0 / grad_scale), float(decay), self.step_count, 0xF, L.stream()), 'adam_step')
+                            float(1.0 / grad_scale), float(decay), step, 0xF, L.stream()), 'adam_step')
             else:
                 ho, hn = geo.half_own()
                 L.check(lib.nsr_adam_step_scaled(
@@ -344,10 +324,6 @@ class ShardedFusedAdam:
                         L.check(lib.nsr_cast_f32_to_f16(ptr(a, o), hptr(o), k, L.stream()), 'cast_f32_to_f16')
         if half is not None and self.table_mask:
             m.mark_half_synced()
-
-    # ---- bookkeeping (as FusedAdam) --------------------------------------------------------------------------------------
-    steps_taken = FusedAdam.steps_taken
-    ema_updates_made = FusedAdam.ema_updates_made
 
     # ---- state: full layout in, full layout out ---------------------------------------------------------------------------
     def _full(self, shard, base):
@@ -371,12 +347,10 @@ class ShardedFusedAdam:
             return flat[:geo.total].clone()
         return torch.cat([flat[:geo.table_elems], self.ema_rest])
 
-    def state_dict(self):
-        """Collective.  FusedAdam.state_dict()'s layout, bit for bit."""
+    def _full_state(self):
+        """Collective: state_dict() then has the layout of FusedAdam's, bit for bit."""
         fr = self._frozen or {}
-        return {'step': self.steps_taken, 'exp_avg': self._full(self.exp_avg, fr.get('exp_avg')),
-                'exp_avg_sq': self._full(self.exp_avg_sq, fr.get('exp_avg_sq')), 'ema': self._full_ema(),
-                'ema_updates': self.ema_updates_made, 'lr': self.param_groups[0]['lr']}
+        return self._full(self.exp_avg, fr.get('exp_avg')), self._full(self.exp_avg_sq, fr.get('exp_avg_sq')), self._full_ema()
 
     def gathered(self):
         """Collective.  An object with FusedAdam's state_dict(), ema and ema_updates: what checkpoint.save_checkpoint reads
@@ -385,7 +359,7 @@ class ShardedFusedAdam:
         return types.SimpleNamespace(state_dict=lambda: sd, ema=sd['ema'], ema_updates=self.ema_updates)
 
     def _load_full(self, exp_avg, exp_avg_sq, ema):
-        """this rank's shard of full-layout tensors"""
+        """keeps this rank's shard of full-layout tensors (a state_dict() of either optimiser, or the reference's state)"""
         m, geo = self.model, self.geo
         with torch.no_grad():
             if geo.packed:
@@ -402,23 +376,3 @@ class ShardedFusedAdam:
                 self.exp_avg_sq[:geo.n].copy_(exp_avg_sq[geo.lo:geo.hi])
                 if self.ema is not None and ema is not None:
                     self.ema[:geo.n].copy_(ema[geo.lo:geo.hi])
-
-    def load_state_dict(self, sd):
-        """FusedAdam.state_dict()'s layout (or the reference's optimiser state); keeps this rank's shard."""
-        if 'param_groups' in sd and 'state' in sd:
-            return self.load_reference_state(sd)
-        self.step_count = sd['step']
-        self._load_full(sd['exp_avg'], sd['exp_avg_sq'], sd.get('ema'))
-        self.ema_updates = sd.get('ema_updates', 0)
-        self.param_groups[0]['lr'] = sd.get('lr', self.lr)
-
-    def load_reference_state(self, optim_sd, ema_sd=None):
-        """FusedAdam.load_reference_state into full-layout host tensors, then this rank's shard of them."""
-        n = self.geo.arena_elems
-        full = types.SimpleNamespace(
-            model=self.model, nets=self.nets, table_mask=self.table_mask, lr=self.lr, param_groups=self.param_groups,
-            exp_avg=torch.zeros(n), exp_avg_sq=torch.zeros(n), step_count=self.step_count, ema_updates=self.ema_updates,
-            ema=torch.zeros(n) if (self.ema is not None and ema_sd is not None and ema_sd.get('shadow_params') is not None) else None)
-        FusedAdam.load_reference_state(full, optim_sd, ema_sd)
-        self._load_full(full.exp_avg, full.exp_avg_sq, full.ema)
-        self.step_count, self.ema_updates = full.step_count, full.ema_updates

@@ -305,38 +305,31 @@ class StyleTCNerf(nn.Module):
         return d
 
     # ---- reference-shaped checkpoints ----------------------------------------------------------
-    def state_dict(self, *args, **kwargs):
-        t = self.tables_view()
-        sd = {
-            'x_density_embedder.embeddings': t[:, 0, :].clone(),
-            'x_density_embedder.offsets': self.x_density_embedder.offsets.clone(),
-            'x_color_embedder.embeddings': t[:, 1, :].clone(),
-            'x_color_embedder.offsets': self.x_color_embedder.offsets.clone(),
-        }
-        m = self._mlp_flat()
+    def views_of(self, flat):
+        """name -> view of an arena-shaped flat tensor (the parameter arena, a moment or an EMA arena of an optimiser), in the
+        reference's named_parameters() order.  The one place that writes the arena layout out."""
+        t = flat[:self.table_elems].view(self.rows, 2, 2)
+        out = {'x_density_embedder.embeddings': t[:, 0, :], 'x_color_embedder.embeddings': t[:, 1, :]}
         for name, off, n in MLP_LAYOUT:
-            sd[name + '.params'] = m[off:off + n].clone()
+            out[name + '.params'] = flat[self.table_elems + off: self.table_elems + off + n]
+        return out
+
+    def state_dict(self, *args, **kwargs):
+        sd = {name: v.clone() for name, v in self.views_of(self.arena.detach()).items()}
+        sd['x_density_embedder.offsets'] = self.x_density_embedder.offsets.clone()
+        sd['x_color_embedder.offsets'] = self.x_color_embedder.offsets.clone()
         return sd
 
     def load_state_dict(self, sd, strict=True):
         with torch.no_grad():
-            t = self.tables_view()
-            t[:, 0, :].copy_(sd['x_density_embedder.embeddings'])
-            t[:, 1, :].copy_(sd['x_color_embedder.embeddings'])
-            m = self._mlp_flat()
-            for name, off, n in MLP_LAYOUT:
-                m[off:off + n].copy_(sd[name + '.params'].reshape(-1))
+            for name, v in self.views_of(self.arena.detach()).items():
+                v.copy_(sd[name].reshape(v.shape))
             self.arena.add_(0)   # bump the version counter: the half copy is stale
         return self
 
     def named_views(self):
         """(name, arena slice or strided view) pairs in the reference's named_parameters() order."""
-        t = self.tables_view()
-        out = [('x_density_embedder.embeddings', t[:, 0, :]), ('x_color_embedder.embeddings', t[:, 1, :])]
-        m = self._mlp_flat()
-        for name, off, n in MLP_LAYOUT:
-            out.append((name + '.params', m[off:off + n]))
-        return out
+        return list(self.views_of(self.arena.detach()).items())
 
     # ---- forward -------------------------------------------------------------------------------
     def field(self, pts, sigma_only=False, m_dev=None, density_scale=1.0, perm=None):
