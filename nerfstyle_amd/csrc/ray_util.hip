@@ -1,0 +1,159 @@
+// What is neither march nor composite: near/far against the AABB, morton codes, the occupancy bitfield, device ray
+// generation, and the library's identity functions (ABI version, status strings, target).
+#include "rm_probe.h"
+
+// ---------------------------------------------------------------------------------------------
+// utilities
+// ---------------------------------------------------------------------------------------------
+// raymarching.cu:190-244
+__global__ void k_near_far_from_aabb(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                     const float *__restrict__ aabb, uint32_t N, float min_near,
+                                     float *__restrict__ nears, float *__restrict__ fars) {
+#pragma clang fp contract(off)
+    const float a0 = aabb[0], a1 = aabb[1], a2 = aabb[2], a3 = aabb[3], a4 = aabb[4], a5 = aabb[5];
+    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
+        const RmRay r = rm_load_ray(rays_o, rays_d, n);
+        const float big = 3.402823466e+38f;
+        float near = (a0 - r.ox) * r.rdx, far = (a3 - r.ox) * r.rdx;
+        if (near > far) { const float c = near; near = far; far = c; }
+        float near_y = (a1 - r.oy) * r.rdy, far_y = (a4 - r.oy) * r.rdy;
+        if (near_y > far_y) { const float c = near_y; near_y = far_y; far_y = c; }
+        if (near > far_y || near_y > far) { nears[n] = big; fars[n] = big; continue; }
+        if (near_y > near) near = near_y;
+        if (far_y < far) far = far_y;
+        float near_z = (a2 - r.oz) * r.rdz, far_z = (a5 - r.oz) * r.rdz;
+        if (near_z > far_z) { const float c = near_z; near_z = far_z; far_z = c; }
+        if (near > far_z || near_z > far) { nears[n] = big; fars[n] = big; continue; }
+        if (near_z > near) near = near_z;
+        if (far_z < far) far = far_z;
+        if (near < min_near) near = min_near;
+        nears[n] = near;
+        fars[n] = far;
+    }
+}
+
+// raymarching.cu:313-325
+__global__ void k_morton3d(const int32_t *__restrict__ coords, uint32_t N, int32_t *__restrict__ indices) {
+    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x)
+        indices[n] = (int32_t)rm_morton3d((uint32_t)coords[n * 3], (uint32_t)coords[n * 3 + 1],
+                                          (uint32_t)coords[n * 3 + 2]);
+}
+
+// raymarching.cu:336-353
+__global__ void k_morton3d_invert(const int32_t *__restrict__ indices, uint32_t N, int32_t *__restrict__ coords) {
+    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
+        const int32_t ind = indices[n];
+        coords[n * 3 + 0] = (int32_t)rm_morton3d_invert((uint32_t)(ind >> 0));
+        coords[n * 3 + 1] = (int32_t)rm_morton3d_invert((uint32_t)(ind >> 1));
+        coords[n * 3 + 2] = (int32_t)rm_morton3d_invert((uint32_t)(ind >> 2));
+    }
+}
+
+// raymarching.cu:366-388.  One thread per output byte, 8 floats in as two 16-byte loads.
+__global__ void k_packbits(const float *__restrict__ grid, uint32_t N, float thresh, uint8_t *__restrict__ bitfield) {
+    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
+        const float4 a = reinterpret_cast<const float4 *>(grid)[(size_t)n * 2];
+        const float4 b = reinterpret_cast<const float4 *>(grid)[(size_t)n * 2 + 1];
+        uint32_t bits = 0;
+        bits |= (a.x > thresh) ? 1u : 0u;
+        bits |= (a.y > thresh) ? 2u : 0u;
+        bits |= (a.z > thresh) ? 4u : 0u;
+        bits |= (a.w > thresh) ? 8u : 0u;
+        bits |= (b.x > thresh) ? 16u : 0u;
+        bits |= (b.y > thresh) ? 32u : 0u;
+        bits |= (b.z > thresh) ? 64u : 0u;
+        bits |= (b.w > thresh) ? 128u : 0u;
+        bitfield[n] = (uint8_t)bits;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// device ray generation (nerf_lib.py:69-142, common.py:139-147)
+// ---------------------------------------------------------------------------------------------
+__global__ void k_generate_rays(const float *__restrict__ pose, uint32_t w, uint32_t h, float fx, float fy, float cx,
+                                float cy, int camera_flip, const int32_t *__restrict__ pix, uint32_t N,
+                                float *__restrict__ rays_o, float *__restrict__ rays_d) {
+#pragma clang fp contract(off)
+    const float r00 = pose[0], r01 = pose[1], r02 = pose[2], tx = pose[3];
+    const float r10 = pose[4], r11 = pose[5], r12 = pose[6], ty = pose[7];
+    const float r20 = pose[8], r21 = pose[9], r22 = pose[10], tz = pose[11];
+    const float f0 = (camera_flip >> 2) & 1 ? -1.0f : 1.0f;   // nerf_lib.py:121, bit order [2,1,0]
+    const float f1 = (camera_flip >> 1) & 1 ? -1.0f : 1.0f;
+    const float f2 = (camera_flip >> 0) & 1 ? -1.0f : 1.0f;
+    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
+        const uint32_t p = pix ? (uint32_t)pix[n] : n;
+        const uint32_t py = p / w, px = p - py * w;
+        // np.linspace(0, w, 2w+1)[1::2] == x + 0.5 exactly in fp32 for w < 2^22
+        const float i = (float)px + 0.5f, j = (float)py + 0.5f;
+        const float d0 = ((i - cx) / fx) * f0, d1 = ((j - cy) / fy) * f1, d2 = f2;
+        const float wx = r00 * d0 + r01 * d1 + r02 * d2;
+        const float wy = r10 * d0 + r11 * d1 + r12 * d2;
+        const float wz = r20 * d0 + r21 * d1 + r22 * d2;
+        const float nrm = sqrtf(wx * wx + wy * wy + wz * wz);
+        rays_d[n * 3 + 0] = wx / nrm; rays_d[n * 3 + 1] = wy / nrm; rays_d[n * 3 + 2] = wz / nrm;
+        rays_o[n * 3 + 0] = tx; rays_o[n * 3 + 1] = ty; rays_o[n * 3 + 2] = tz;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+
+const char *nsr_status_string(int status) {
+    switch (status) {
+        case NSR_OK: return "ok";
+        case NSR_ERR_INVALID_ARG: return "invalid argument (null pointer, bad size or enum)";
+        case NSR_ERR_UNSUPPORTED: return "unsupported configuration for the gfx950 kernels";
+        case NSR_ERR_LAUNCH: return "HIP kernel launch failed";
+        default: return "unknown status";
+    }
+}
+int nsr_abi_version(void) { return 6; }
+const char *nsr_target_arch(void) { return "gfx950"; }
+
+int nsr_near_far_from_aabb(const float *rays_o, const float *rays_d, const float *aabb, uint32_t N, float min_near,
+                           float *nears, float *fars, nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(rays_o); NSR_CHECK_PTR(rays_d); NSR_CHECK_PTR(aabb); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
+    hipLaunchKernelGGL(k_near_far_from_aabb, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d,
+                       aabb, N, min_near, nears, fars);
+    return nsr_launch_status();
+}
+
+int nsr_morton3d(const int32_t *coords, uint32_t N, int32_t *indices, nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(coords); NSR_CHECK_PTR(indices);
+    hipLaunchKernelGGL(k_morton3d, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, coords, N, indices);
+    return nsr_launch_status();
+}
+
+int nsr_morton3d_invert(const int32_t *indices, uint32_t N, int32_t *coords, nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(coords); NSR_CHECK_PTR(indices);
+    hipLaunchKernelGGL(k_morton3d_invert, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, indices, N, coords);
+    return nsr_launch_status();
+}
+
+int nsr_packbits(const float *grid, uint32_t N, float density_thresh, uint8_t *bitfield, nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(grid); NSR_CHECK_PTR(bitfield);
+    if (((uintptr_t)grid & 15u) != 0) return NSR_ERR_INVALID_ARG;   // 16-byte loads
+    hipLaunchKernelGGL(k_packbits, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, grid, N, density_thresh,
+                       bitfield);
+    return nsr_launch_status();
+}
+
+int nsr_generate_rays(const float *pose, uint32_t w, uint32_t h, float fx, float fy, float cx, float cy, int camera_flip,
+                      const int32_t *pix, uint32_t N, float *rays_o, float *rays_d, nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(pose); NSR_CHECK_PTR(rays_o); NSR_CHECK_PTR(rays_d);
+    if (w == 0 || h == 0) return NSR_ERR_INVALID_ARG;
+    if (pix == nullptr && (uint64_t)N != (uint64_t)w * h) return NSR_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_generate_rays, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, pose, w, h, fx, fy, cx, cy,
+                       camera_flip, pix, N, rays_o, rays_d);
+    return nsr_launch_status();
+}
+
+}   // extern "C"
+

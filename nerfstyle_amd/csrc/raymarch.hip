@@ -1,182 +1,103 @@
-// Occupancy-grid ray march, sample compaction and alpha compositing for gfx950.
+// Occupancy-grid training march and sample compaction for gfx950.  The probe core is rm_probe.h, the inference march and
+// composites are raymarch_infer.hip, the training composite is composite.hip.
 // Behaviour follows hkust-vgd/nerfstyle raymarching/src/raymarching.cu (cited per function);
 // the structure does not: offsets come from a wave64 shuffle scan + one look-up of per-block
 // totals (deterministic, no atomics), the composite backward keeps its running sums in
 // registers (no rgbs_buf round trip), and every entry point takes an explicit stream.
-#include "nsr_common.h"
-#include "rm_util.h"
+#include "rm_probe.h"
 
-#define RM_BLOCK 256
-#define RM_SQRT3 1.7320508075688772f
 #define NSR_MARCH_WPR_MAX_RAYS 20480u   // batches up to this size march one wave per ray (k_march_wpr)
 
 // ---------------------------------------------------------------------------------------------
-// small device helpers
+// pieces the emitting kernels share
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float rm_clamp(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
-__device__ __forceinline__ float rm_sign(float x) { return copysignf(1.0f, x); }
-
-// ---------------------------------------------------------------------------------------------
-// marching core (raymarching.cu:460-500, 530-588, 1059-1119)
-// ---------------------------------------------------------------------------------------------
-struct RmRay {
-    float ox, oy, oz, dx, dy, dz, rdx, rdy, rdz;
-};
-struct RmCfg {
-    float bound, rbound, dt_gamma, dt_min, dt_max, rH, H3, Hf, halfH, Cf;
-    uint32_t H;
-    const uint8_t *grid;
-};
-
-__device__ __forceinline__ RmCfg rm_cfg(float bound, float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H,
-                                        const uint8_t *grid) {
-    RmCfg c;
-    c.bound = bound;
-    c.rbound = 1 / bound;
-    c.halfH = 0.5f * (float)H;
-    c.dt_gamma = dt_gamma;
-    c.dt_min = 2 * RM_SQRT3 / (float)max_steps;               // :446
-    c.dt_max = 2 * RM_SQRT3 * (float)(1 << (C - 1)) / (float)H;  // :447
-    c.rH = 1 / (float)H;
-    c.H3 = (float)(H * H * H);
-    c.Hf = (float)H;
-    c.Cf = (float)C;
-    c.H = H;
-    c.grid = grid;
-    return c;
+// A dropped ray (point_index + num_steps >= M, :517): the reference's buffers are zero-filled before the launch
+// (raymarching.py:238-240), here they are torch.empty -- write the in-buffer part, so that no consumer bounded by
+// min(counter[0], M) ever reads uninitialised positions (a NaN bit pattern would poison the weight gradients as 0 * NaN).
+// One thread calls it with (first, stride) = (0, 1), a wave with (lane, 64).
+__device__ __forceinline__ void rm_zero_dropped(uint32_t point_index, uint32_t num_steps, uint32_t M, uint32_t first, uint32_t stride,
+                                                float *xyzs, float *dirs, float *deltas) {
+    for (uint32_t i = point_index + first; i < min(point_index + num_steps, M); i += stride) {
+        xyzs[(size_t)i * 3 + 0] = 0.f; xyzs[(size_t)i * 3 + 1] = 0.f; xyzs[(size_t)i * 3 + 2] = 0.f;
+        if (dirs) { dirs[(size_t)i * 3 + 0] = 0.f; dirs[(size_t)i * 3 + 1] = 0.f; dirs[(size_t)i * 3 + 2] = 0.f; }
+        reinterpret_cast<float4 *>(deltas)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
 }
 
-__device__ __forceinline__ int rm_mip(float v, float max_cascade) {
-    int e;
-    frexpf(v, &e);
-    return (int)fminf(max_cascade - 1, fmaxf(0.0f, (float)e));
+// Start of a thread-per-ray emit (:505-517): the ray's offset from the block scan of the counts, its `rays` triple, and the
+// zero-fill of a dropped ray.  Every thread of the block calls it (the scan synchronises); true = the ray emits samples.
+__device__ __forceinline__ bool rm_thread_ray_begin(uint32_t n, uint32_t N, uint32_t M, const uint32_t *counts, const uint32_t *block_bases,
+                                                    uint32_t *wave_sums, float *xyzs, float *dirs, float *deltas, int32_t *rays,
+                                                    uint32_t &point_index, uint32_t &num_steps) {
+    num_steps = n < N ? counts[n] : 0u;
+    uint32_t total;
+    point_index = block_bases[blockIdx.x] + rm_block_exclusive_scan(num_steps, wave_sums, total);
+    if (n >= N) return false;
+    rays[n * 3 + 0] = (int32_t)n;
+    rays[n * 3 + 1] = (int32_t)point_index;
+    rays[n * 3 + 2] = (int32_t)num_steps;
+    if (num_steps == 0) return false;
+    if (point_index + num_steps >= M) {
+        rm_zero_dropped(point_index, num_steps, M, 0u, 1u, xyzs, dirs, deltas);
+        return false;
+    }
+    return true;
 }
 
-// Evaluates the sample at parameter t.  Same operation order as the reference (and the oracle);
-// contraction is off so that every rounding matches the restatement bit for bit.
-__device__ __forceinline__ bool rm_probe(const RmRay &r, const RmCfg &c, float t, float &x, float &y, float &z,
-                                         float &dt, float &tt) {
+// The same for a wave per ray: base of the ray's 256-ray block + the counts of the rays before it in the block.
+__device__ __forceinline__ bool rm_wave_ray_begin(uint32_t n, uint32_t lane, uint32_t M, const uint32_t *counts, const uint32_t *block_bases,
+                                                  float *xyzs, float *dirs, float *deltas, int32_t *rays, uint32_t &point_index,
+                                                  uint32_t &num_steps) {
+    const uint32_t blk0 = (n / RM_BLOCK) * RM_BLOCK;
+    uint32_t part = 0;
+    for (uint32_t i = blk0 + lane; i < n; i += 64) part += counts[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
+    point_index = block_bases[n / RM_BLOCK] + part;
+    num_steps = counts[n];
+    if (lane == 0) {
+        rays[n * 3 + 0] = (int32_t)n;
+        rays[n * 3 + 1] = (int32_t)point_index;
+        rays[n * 3 + 2] = (int32_t)num_steps;
+    }
+    if (num_steps == 0) return false;
+    if (point_index + num_steps >= M) {
+        rm_zero_dropped(point_index, num_steps, M, lane, 64u, xyzs, dirs, deltas);
+        return false;
+    }
+    return true;
+}
+
+// Constant step (LLFF: dt_gamma = 0): t_{j+1} = fl(t_j + dt).  Inside one binade every t_j is a multiple of the
+// binade's ulp u, so the rounded sum advances the BIT PATTERN by a constant c = dt / u rounded to an integer (ties
+// to even make the very first step the only possible exception: after it the mantissa parity repeats).  Two real
+// additions give t_1 and t_2, c = bits(t_2) - bits(t_1), and t_j = bits(t_1) + (j - 1) c for j = 1..span -- the same
+// floats as `span` serial additions, as long as t_1 .. t_span share an exponent.  Returns whether that holds for the
+// sequence that starts at t, with b1 = bits(t_1) and cc = c; otherwise the caller adds serially.
+__device__ __forceinline__ bool rm_const_step(const RmCfg &c, float t, uint32_t span, uint32_t &b1, uint32_t &cc) {
+    bool closed = false;
+    b1 = 0; cc = 0;
+    if (c.dt_gamma == 0.0f && t > 0.0f) {
 #pragma clang fp contract(off)
-    x = rm_clamp(r.ox + t * r.dx, -c.bound, c.bound);
-    y = rm_clamp(r.oy + t * r.dy, -c.bound, c.bound);
-    z = rm_clamp(r.oz + t * r.dz, -c.bound, c.bound);
-    dt = rm_clamp(t * c.dt_gamma, c.dt_min, c.dt_max);
-    const int m1 = rm_mip(fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z))), c.Cf);   // :42-47
-    const int m2 = rm_mip((dt * c.Hf) * 0.5f, c.Cf);                             // :49-54 (x 0.5 is exact in either width)
-    const int level = max(m1, m2);
-    const float mip_pow = scalbnf(1.0f, level);
-    const float mip_bound = fminf(mip_pow, c.bound);
-    // 1 / mip_bound (:474): the reciprocal of a power of two is exact, the other case is the loop-invariant
-    // 1 / bound -- the same correctly rounded quotients as the division, without a division per probe
-    const float mip_rbound = mip_pow < c.bound ? scalbnf(1.0f, -level) : c.rbound;
-    // :475-477 computes 0.5 * (double)v * (double)H and narrows once.  v has 24 significant bits, H at most 11:
-    // the double product is exact, so the single rounding of the float product v * (0.5f * H) gives the same
-    // float (0.5f * H is exact too) -- no fp64 in the probe
-    const int nx = (int)rm_clamp((x * mip_rbound + 1) * c.halfH, 0.0f, (float)(c.H - 1));
-    const int ny = (int)rm_clamp((y * mip_rbound + 1) * c.halfH, 0.0f, (float)(c.H - 1));
-    const int nz = (int)rm_clamp((z * mip_rbound + 1) * c.halfH, 0.0f, (float)(c.H - 1));
-    const uint32_t index = (uint32_t)((float)level * c.H3 + (float)rm_morton3d(nx, ny, nz));   // :479
-    const bool occ = c.grid[index / 8] & (1 << (index % 8));
-    if (!occ) {
-        // :491-495
-        const float tx = ((((float)nx + 0.5f + 0.5f * rm_sign(r.dx)) * c.rH * 2 - 1) * mip_bound - x) * r.rdx;
-        const float ty = ((((float)ny + 0.5f + 0.5f * rm_sign(r.dy)) * c.rH * 2 - 1) * mip_bound - y) * r.rdy;
-        const float tz = ((((float)nz + 0.5f + 0.5f * rm_sign(r.dz)) * c.rH * 2 - 1) * mip_bound - z) * r.rdz;
-        tt = t + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
+        const float dt0 = rm_clamp(t * c.dt_gamma, c.dt_min, c.dt_max);
+        const float t1 = t + dt0, t2 = t1 + dt0;
+        b1 = __float_as_uint(t1);
+        const uint32_t b2 = __float_as_uint(t2);
+        cc = b2 - b1;
+        const uint32_t b_last = b1 + (span - 1u) * cc;
+        closed = b2 > b1 && (b1 >> 23) == (b_last >> 23) && cc < (1u << 23);
     }
-    return occ;
+    return closed;
 }
 
-// Returns the number of additions made (the march's step index k advances by it: k_march_count's sample mask).
-__device__ __forceinline__ uint32_t rm_skip(const RmCfg &c, float &t, float tt) {
-#pragma clang fp contract(off)
-    // do { t += clamp(t * dt_gamma, dt_min, dt_max); } while (t < tt);  (:497) -- the same additions in the same
-    // order, four per trip: the first partial sum that is not below tt is the loop's result
-    uint32_t adds = 0;
-    for (;;) {
-        const float t1 = t + rm_clamp(t * c.dt_gamma, c.dt_min, c.dt_max);
-        const float t2 = t1 + rm_clamp(t1 * c.dt_gamma, c.dt_min, c.dt_max);
-        const float t3 = t2 + rm_clamp(t2 * c.dt_gamma, c.dt_min, c.dt_max);
-        const float t4 = t3 + rm_clamp(t3 * c.dt_gamma, c.dt_min, c.dt_max);
-        const bool b1 = t1 < tt, b2 = t2 < tt, b3 = t3 < tt, b4 = t4 < tt;
-        t = !b1 ? t1 : (!b2 ? t2 : (!b3 ? t3 : t4));
-        adds += !b1 ? 1u : (!b2 ? 2u : (!b3 ? 3u : 4u));
-        if (!(b1 && b2 && b3 && b4)) break;
-    }
-    return adds;
-}
-
-__device__ __forceinline__ RmRay rm_load_ray(const float *rays_o, const float *rays_d, uint32_t n) {
-    RmRay r;
-    r.ox = rays_o[n * 3 + 0]; r.oy = rays_o[n * 3 + 1]; r.oz = rays_o[n * 3 + 2];
-    r.dx = rays_d[n * 3 + 0]; r.dy = rays_d[n * 3 + 1]; r.dz = rays_d[n * 3 + 2];
-    r.rdx = 1 / r.dx; r.rdy = 1 / r.dy; r.rdz = 1 / r.dz;
-    return r;
-}
-
-// ---------------------------------------------------------------------------------------------
-// utilities
-// ---------------------------------------------------------------------------------------------
-// raymarching.cu:190-244
-__global__ void k_near_far_from_aabb(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
-                                     const float *__restrict__ aabb, uint32_t N, float min_near,
-                                     float *__restrict__ nears, float *__restrict__ fars) {
-#pragma clang fp contract(off)
-    const float a0 = aabb[0], a1 = aabb[1], a2 = aabb[2], a3 = aabb[3], a4 = aabb[4], a5 = aabb[5];
-    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
-        const RmRay r = rm_load_ray(rays_o, rays_d, n);
-        const float big = 3.402823466e+38f;
-        float near = (a0 - r.ox) * r.rdx, far = (a3 - r.ox) * r.rdx;
-        if (near > far) { const float c = near; near = far; far = c; }
-        float near_y = (a1 - r.oy) * r.rdy, far_y = (a4 - r.oy) * r.rdy;
-        if (near_y > far_y) { const float c = near_y; near_y = far_y; far_y = c; }
-        if (near > far_y || near_y > far) { nears[n] = big; fars[n] = big; continue; }
-        if (near_y > near) near = near_y;
-        if (far_y < far) far = far_y;
-        float near_z = (a2 - r.oz) * r.rdz, far_z = (a5 - r.oz) * r.rdz;
-        if (near_z > far_z) { const float c = near_z; near_z = far_z; far_z = c; }
-        if (near > far_z || near_z > far) { nears[n] = big; fars[n] = big; continue; }
-        if (near_z > near) near = near_z;
-        if (far_z < far) far = far_z;
-        if (near < min_near) near = min_near;
-        nears[n] = near;
-        fars[n] = far;
-    }
-}
-
-// raymarching.cu:313-325
-__global__ void k_morton3d(const int32_t *__restrict__ coords, uint32_t N, int32_t *__restrict__ indices) {
-    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x)
-        indices[n] = (int32_t)rm_morton3d((uint32_t)coords[n * 3], (uint32_t)coords[n * 3 + 1],
-                                          (uint32_t)coords[n * 3 + 2]);
-}
-
-// raymarching.cu:336-353
-__global__ void k_morton3d_invert(const int32_t *__restrict__ indices, uint32_t N, int32_t *__restrict__ coords) {
-    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
-        const int32_t ind = indices[n];
-        coords[n * 3 + 0] = (int32_t)rm_morton3d_invert((uint32_t)(ind >> 0));
-        coords[n * 3 + 1] = (int32_t)rm_morton3d_invert((uint32_t)(ind >> 1));
-        coords[n * 3 + 2] = (int32_t)rm_morton3d_invert((uint32_t)(ind >> 2));
-    }
-}
-
-// raymarching.cu:366-388.  One thread per output byte, 8 floats in as two 16-byte loads.
-__global__ void k_packbits(const float *__restrict__ grid, uint32_t N, float thresh, uint8_t *__restrict__ bitfield) {
-    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
-        const float4 a = reinterpret_cast<const float4 *>(grid)[(size_t)n * 2];
-        const float4 b = reinterpret_cast<const float4 *>(grid)[(size_t)n * 2 + 1];
-        uint32_t bits = 0;
-        bits |= (a.x > thresh) ? 1u : 0u;
-        bits |= (a.y > thresh) ? 2u : 0u;
-        bits |= (a.z > thresh) ? 4u : 0u;
-        bits |= (a.w > thresh) ? 8u : 0u;
-        bits |= (b.x > thresh) ? 16u : 0u;
-        bits |= (b.y > thresh) ? 32u : 0u;
-        bits |= (b.z > thresh) ? 64u : 0u;
-        bits |= (b.w > thresh) ? 128u : 0u;
-        bitfield[n] = (uint8_t)bits;
-    }
+// One sample of a thread-per-ray emit at the ray's walking pointers: position, direction (when asked for) and the leading
+// deltas columns -- float2 (dt, t_next - last_t), or all four for NDC.
+template <typename V>
+__device__ __forceinline__ void rm_store_sample(const RmRay &r, float x, float y, float z, V del, float *&pxyz, float *&pdir, float *&pdel) {
+    pxyz[0] = x; pxyz[1] = y; pxyz[2] = z;
+    if (pdir) { pdir[0] = r.dx; pdir[1] = r.dy; pdir[2] = r.dz; pdir += 3; }
+    reinterpret_cast<V *>(pdel)[0] = del;
+    pxyz += 3; pdel += 4;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -195,14 +116,10 @@ k_march_count(const float *__restrict__ rays_o, const float *__restrict__ rays_d
         const RmCfg c = rm_cfg(bound, dt_gamma, max_steps, C, H, grid);
         const RmRay r = rm_load_ray(rays_o, rays_d, n);
         const float far = fars[n];
-        float t = nears[n];
-        {
-#pragma clang fp contract(off)
-            const float noise = noises ? noises[n] : 0.0f;
-            t += rm_clamp(t * dt_gamma, c.dt_min, c.dt_max) * noise;   // :452
-        }
+        float t = rm_start_t(c, nears[n], noises ? noises[n] : 0.0f);
         float x, y, z, dt, tt;
         if (mask == nullptr) {
+            // NDC only: every other batch marches a wave per ray or records the mask (see nsr_march_rays_train)
             while (t < far && num_steps < max_steps) {
                 if (rm_probe(r, c, t, x, y, z, dt, tt)) {
                     num_steps++;
@@ -267,71 +184,49 @@ k_scan_block_sums(uint32_t *__restrict__ block_sums, uint32_t nblocks, int32_t *
         counter[1] += (int32_t)N;
     }
 }
+// (host launcher, declared in rm_util.h: the alive-ray compaction of raymarch_infer.hip scans with the same kernel)
+void rm_scan_block_sums(uint32_t *block_sums, uint32_t nblocks, int32_t *counter, uint32_t N, hipStream_t stream) {
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, stream, block_sums, nblocks, counter, N);
+}
 
-// pass 2 (raymarching.cu:505-588): offsets from the scan, then re-march and emit.
+// pass 2 for NDC (raymarching.cu:505-588): offsets from the scan, then re-march and emit.  The NDC deltas need the
+// previous sample's z, so this form probes the grid again where k_march_emit_mask only replays.
 __global__ void __launch_bounds__(RM_BLOCK)
-k_march_emit(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const float *__restrict__ z_hats,
-             const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps, int is_ndc,
-             uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float *__restrict__ nears,
-             const float *__restrict__ fars, const float *__restrict__ noises, const uint32_t *__restrict__ counts,
-             const uint32_t *__restrict__ block_bases, uint32_t ray_base, float *__restrict__ xyzs,
-             float *__restrict__ dirs, float *__restrict__ deltas, int32_t *__restrict__ rays) {
+k_march_emit_ndc(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const float *__restrict__ z_hats,
+                 const uint8_t *__restrict__ grid, float bound, float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C,
+                 uint32_t H, uint32_t M, const float *__restrict__ nears, const float *__restrict__ fars,
+                 const float *__restrict__ noises, const uint32_t *__restrict__ counts, const uint32_t *__restrict__ block_bases,
+                 float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas, int32_t *__restrict__ rays) {
     __shared__ uint32_t wave_sums[RM_BLOCK / 64];
     const uint32_t n = blockIdx.x * RM_BLOCK + threadIdx.x;
-    const uint32_t num_steps = n < N ? counts[n] : 0u;
-    uint32_t total;
-    const uint32_t point_index = block_bases[blockIdx.x] + rm_block_exclusive_scan(num_steps, wave_sums, total);
-    if (n >= N) return;
-    const uint32_t ray_index = ray_base + n;
-    rays[ray_index * 3 + 0] = (int32_t)n;
-    rays[ray_index * 3 + 1] = (int32_t)point_index;
-    rays[ray_index * 3 + 2] = (int32_t)num_steps;
-    if (num_steps == 0) return;
-    if (point_index + num_steps >= M) {          // :517
-        // dropped ray: the reference's buffers are zero-filled before the launch (raymarching.py:238-240), here they
-        // are torch.empty -- write the in-buffer part, so that no consumer bounded by min(counter[0], M) ever
-        // reads uninitialised positions (a NaN bit pattern would poison the weight gradients as 0 * NaN)
-        for (uint32_t i = point_index; i < min(point_index + num_steps, M); i++) {
-            xyzs[(size_t)i * 3 + 0] = 0.f; xyzs[(size_t)i * 3 + 1] = 0.f; xyzs[(size_t)i * 3 + 2] = 0.f;
-            if (dirs) { dirs[(size_t)i * 3 + 0] = 0.f; dirs[(size_t)i * 3 + 1] = 0.f; dirs[(size_t)i * 3 + 2] = 0.f; }
-            reinterpret_cast<float4 *>(deltas)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        return;
-    }
+    uint32_t point_index, num_steps;
+    if (!rm_thread_ray_begin(n, N, M, counts, block_bases, wave_sums, xyzs, dirs, deltas, rays, point_index, num_steps)) return;
 
     const RmCfg c = rm_cfg(bound, dt_gamma, max_steps, C, H, grid);
     const RmRay r = rm_load_ray(rays_o, rays_d, n);
     const float far = fars[n];
-    float t = nears[n];
-    {
-#pragma clang fp contract(off)
-        const float noise = noises ? noises[n] : 0.0f;
-        t += rm_clamp(t * dt_gamma, c.dt_min, c.dt_max) * noise;
-    }
+    float t = rm_start_t(c, nears[n], noises ? noises[n] : 0.0f);
     float *pxyz = xyzs + (size_t)point_index * 3;
     float *pdir = dirs ? dirs + (size_t)point_index * 3 : nullptr;
     float *pdel = deltas + (size_t)point_index * 4;
     uint32_t step = 0;
     float last_t = t;
-    float last_z = rm_clamp(r.oz + t * r.dz, -bound, bound);
+    float last_z;
+    {
+#pragma clang fp contract(off)
+        last_z = rm_clamp(r.oz + t * r.dz, -bound, bound);     // (contracted to an fma it is not the oracle's float)
+    }
     float x, y, z, dt, tt;
     while (t < far && step < num_steps) {
         if (rm_probe(r, c, t, x, y, z, dt, tt)) {
 #pragma clang fp contract(off)
-            pxyz[0] = x; pxyz[1] = y; pxyz[2] = z;
-            if (pdir) { pdir[0] = r.dx; pdir[1] = r.dy; pdir[2] = r.dz; pdir += 3; }
             t += dt;
-            if (is_ndc) {
-                const float new_z = rm_clamp(r.oz + t * r.dz, -bound, bound);
-                const float zh = z_hats[n];
-                reinterpret_cast<float4 *>(pdel)[0] = make_float4(dt, t - last_t, (2 / (new_z - 1) - 2 / (z - 1)) / zh,
-                                                                  (2 / (new_z - 1) - 2 / (last_z - 1)) / zh);
-                last_z = z;   // :570
-            } else {
-                reinterpret_cast<float2 *>(pdel)[0] = make_float2(dt, t - last_t);
-            }
+            const float new_z = rm_clamp(r.oz + t * r.dz, -bound, bound);
+            const float zh = z_hats[n];
+            rm_store_sample(r, x, y, z, make_float4(dt, t - last_t, (2 / (new_z - 1) - 2 / (z - 1)) / zh,
+                                                    (2 / (new_z - 1) - 2 / (last_z - 1)) / zh), pxyz, pdir, pdel);
+            last_z = z;   // :570
             last_t = t;
-            pxyz += 3; pdel += 4;
             step++;
         } else {
             rm_skip(c, t, tt);
@@ -340,7 +235,7 @@ k_march_emit(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
 }
 
 // pass 2 without probes: replays the t sequence and emits the elements k_march_count marked (see there).  Not for NDC
-// (its deltas need the previous sample's z, k_march_emit keeps that form).
+// (its deltas need the previous sample's z, k_march_emit_ndc keeps that form).
 __global__ void __launch_bounds__(RM_BLOCK)
 k_march_emit_mask(const float *__restrict__ rays_o, const float *__restrict__ rays_d, float bound, float dt_gamma,
                   uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float *__restrict__ nears,
@@ -349,30 +244,11 @@ k_march_emit_mask(const float *__restrict__ rays_o, const float *__restrict__ ra
                   float *__restrict__ deltas, int32_t *__restrict__ rays) {
     __shared__ uint32_t wave_sums[RM_BLOCK / 64];
     const uint32_t n = blockIdx.x * RM_BLOCK + threadIdx.x;
-    const uint32_t num_steps = n < N ? counts[n] : 0u;
-    uint32_t total;
-    const uint32_t point_index = block_bases[blockIdx.x] + rm_block_exclusive_scan(num_steps, wave_sums, total);
-    if (n >= N) return;
-    rays[n * 3 + 0] = (int32_t)n;
-    rays[n * 3 + 1] = (int32_t)point_index;
-    rays[n * 3 + 2] = (int32_t)num_steps;
-    if (num_steps == 0) return;
-    if (point_index + num_steps >= M) {          // :517, see k_march_emit
-        for (uint32_t i = point_index; i < min(point_index + num_steps, M); i++) {
-            xyzs[(size_t)i * 3 + 0] = 0.f; xyzs[(size_t)i * 3 + 1] = 0.f; xyzs[(size_t)i * 3 + 2] = 0.f;
-            if (dirs) { dirs[(size_t)i * 3 + 0] = 0.f; dirs[(size_t)i * 3 + 1] = 0.f; dirs[(size_t)i * 3 + 2] = 0.f; }
-            reinterpret_cast<float4 *>(deltas)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        return;
-    }
+    uint32_t point_index, num_steps;
+    if (!rm_thread_ray_begin(n, N, M, counts, block_bases, wave_sums, xyzs, dirs, deltas, rays, point_index, num_steps)) return;
     const RmCfg c = rm_cfg(bound, dt_gamma, max_steps, C, H, nullptr);
     const RmRay r = rm_load_ray(rays_o, rays_d, n);
-    float t = nears[n];
-    {
-#pragma clang fp contract(off)
-        const float noise = noises ? noises[n] : 0.0f;
-        t += rm_clamp(t * dt_gamma, c.dt_min, c.dt_max) * noise;
-    }
+    float t = rm_start_t(c, nears[n], noises ? noises[n] : 0.0f);
     float *pxyz = xyzs + (size_t)point_index * 3;
     float *pdir = dirs ? dirs + (size_t)point_index * 3 : nullptr;
     float *pdel = deltas + (size_t)point_index * 4;
@@ -381,21 +257,10 @@ k_march_emit_mask(const float *__restrict__ rays_o, const float *__restrict__ ra
     for (uint32_t w = 0; step < num_steps; w++) {
         uint32_t word = mask[(size_t)w * N + n];
         // Constant step (dt_gamma = 0) inside one binade: the word's 32 parameters are t, t_1 = t + dt and t_j = bits(t_1) +
-        // (j - 1) (bits(t_2) - bits(t_1)) -- the floats the 32 serial additions give (wpr_block_t has the argument) -- so only the
+        // (j - 1) (bits(t_2) - bits(t_1)) -- the floats the 32 serial additions give (rm_const_step has the argument) -- so only the
         // MARKED steps cost instructions.  Words that cross a binade keep the serial form.
-        bool closed = false;
-        uint32_t b1 = 0, cc = 0;
-        if (dt_gamma == 0.0f && t > 0.0f) {
-#pragma clang fp contract(off)
-            const float dt0 = rm_clamp(t * dt_gamma, c.dt_min, c.dt_max);
-            const float t1 = t + dt0, t2 = t1 + dt0;
-            b1 = __float_as_uint(t1);
-            const uint32_t b2 = __float_as_uint(t2);
-            cc = b2 - b1;
-            const uint32_t b32 = b1 + 31u * cc;
-            closed = b2 > b1 && (b1 >> 23) == (b32 >> 23) && cc < (1u << 23);
-        }
-        if (closed) {
+        uint32_t b1, cc;
+        if (rm_const_step(c, t, 32u, b1, cc)) {
             while (word != 0u && step < num_steps) {
 #pragma clang fp contract(off)
                 const uint32_t k = (uint32_t)__builtin_ctz(word);
@@ -403,13 +268,9 @@ k_march_emit_mask(const float *__restrict__ rays_o, const float *__restrict__ ra
                 const float tk = k == 0u ? t : __uint_as_float(b1 + (k - 1u) * cc);
                 const float dt = rm_clamp(tk * dt_gamma, c.dt_min, c.dt_max);
                 const float t_next = tk + dt;
-                pxyz[0] = rm_clamp(r.ox + tk * r.dx, -bound, bound);
-                pxyz[1] = rm_clamp(r.oy + tk * r.dy, -bound, bound);
-                pxyz[2] = rm_clamp(r.oz + tk * r.dz, -bound, bound);
-                if (pdir) { pdir[0] = r.dx; pdir[1] = r.dy; pdir[2] = r.dz; pdir += 3; }
-                reinterpret_cast<float2 *>(pdel)[0] = make_float2(dt, t_next - last_t);
+                rm_store_sample(r, rm_clamp(r.ox + tk * r.dx, -bound, bound), rm_clamp(r.oy + tk * r.dy, -bound, bound),
+                                rm_clamp(r.oz + tk * r.dz, -bound, bound), make_float2(dt, t_next - last_t), pxyz, pdir, pdel);
                 last_t = t_next;
-                pxyz += 3; pdel += 4;
                 step++;
             }
             t = __uint_as_float(b1 + 31u * cc);                  // t_32: the next word's first parameter
@@ -420,13 +281,9 @@ k_march_emit_mask(const float *__restrict__ rays_o, const float *__restrict__ ra
             const float dt = rm_clamp(t * dt_gamma, c.dt_min, c.dt_max);
             const float t_next = t + dt;
             if (word & 1u) {
-                pxyz[0] = rm_clamp(r.ox + t * r.dx, -bound, bound);
-                pxyz[1] = rm_clamp(r.oy + t * r.dy, -bound, bound);
-                pxyz[2] = rm_clamp(r.oz + t * r.dz, -bound, bound);
-                if (pdir) { pdir[0] = r.dx; pdir[1] = r.dy; pdir[2] = r.dz; pdir += 3; }
-                reinterpret_cast<float2 *>(pdel)[0] = make_float2(dt, t_next - last_t);
+                rm_store_sample(r, rm_clamp(r.ox + t * r.dx, -bound, bound), rm_clamp(r.oy + t * r.dy, -bound, bound),
+                                rm_clamp(r.oz + t * r.dz, -bound, bound), make_float2(dt, t_next - last_t), pxyz, pdir, pdel);
                 last_t = t_next;
-                pxyz += 3; pdel += 4;
                 step++;
             }
             t = t_next;
@@ -463,23 +320,12 @@ k_march_block_sums(const uint32_t *__restrict__ counts, uint32_t N, uint32_t *__
 __device__ __forceinline__ void wpr_block_t(const RmCfg &c, float dt_gamma, float t_block, uint32_t lane, float &my_t, float &t_next) {
     float tc = t_block;
     my_t = t_block;
-    bool closed = false;
-    if (dt_gamma == 0.0f && t_block > 0.0f) {
-        // Constant step (LLFF: dt_gamma = 0): t_{j+1} = fl(t_j + dt).  Inside one binade every t_j is a multiple of the
-        // binade's ulp u, so the rounded sum advances the BIT PATTERN by a constant c = dt / u rounded to an integer (ties
-        // to even make the very first step the only possible exception: after it the mantissa parity repeats).  Two real
-        // additions give t_1 and t_2, c = bits(t_2) - bits(t_1), and t_j = bits(t_1) + (j - 1) c for j = 1..64 -- the same
-        // floats as the 64 serial additions below, as long as t_1 .. t_64 share an exponent (else: the serial loop).
-#pragma clang fp contract(off)
-        const float dt0 = rm_clamp(t_block * dt_gamma, c.dt_min, c.dt_max);
-        const float t1 = t_block + dt0, t2 = t1 + dt0;
-        const uint32_t b1 = __float_as_uint(t1), b2 = __float_as_uint(t2), cc = b2 - b1;
-        const uint32_t b64 = b1 + 63u * cc;
-        if (b2 > b1 && (b1 >> 23) == (b64 >> 23) && cc < (1u << 23)) {
-            closed = true;
-            my_t = lane == 0 ? t_block : __uint_as_float(b1 + (lane - 1u) * cc);
-            tc = __uint_as_float(b64);
-        }
+    uint32_t b1, cc;
+    bool closed = false;        // (a flag and two ifs, not if / else: the shape whose instructions the timings here were taken with)
+    if (rm_const_step(c, t_block, 64u, b1, cc)) {
+        closed = true;
+        my_t = lane == 0 ? t_block : __uint_as_float(b1 + (lane - 1u) * cc);
+        tc = __uint_as_float(b1 + 63u * cc);
     }
     if (!closed) {
 #pragma clang fp contract(off)
@@ -489,6 +335,31 @@ __device__ __forceinline__ void wpr_block_t(const RmCfg &c, float dt_gamma, floa
         }
     }
     t_next = tc;
+}
+
+// Emits one block's samples: lane j holds parameter t_j with its position, step dt and t_after = t_j + dt (t += dt, :551);
+// sample_mask marks the sample lanes, `steps` counts the ray's samples up to and including this block's, last_t is t after
+// the previous sample's step (:530) and is carried on.  tl is the wave's 64 floats of LDS.
+__device__ __forceinline__ void wpr_emit_block(const RmRay &r, unsigned long long sample_mask, uint32_t lane, uint32_t steps,
+                                               uint32_t point_index, float x, float y, float z, float dt, float t_after, float *tl,
+                                               float &last_t, float *xyzs, float *dirs, float *deltas) {
+#pragma clang fp contract(off)
+    const bool mine = (sample_mask >> lane) & 1ull;
+    const uint32_t first_idx = steps - (uint32_t)__popcll(sample_mask);       // samples emitted before this block
+    const uint32_t before = (uint32_t)__popcll(sample_mask & ((1ull << lane) - 1ull));
+    __builtin_amdgcn_wave_barrier();
+    tl[lane] = t_after;
+    __builtin_amdgcn_wave_barrier();
+    // t after the previous sample's step: previous sample lane of this block, or the carried one
+    const unsigned long long below = sample_mask & ((1ull << lane) - 1ull);
+    const float prev_t = below ? tl[63 - __builtin_clzll(below)] : last_t;
+    if (mine) {
+        const size_t o = (size_t)point_index + first_idx + before;
+        xyzs[o * 3 + 0] = x; xyzs[o * 3 + 1] = y; xyzs[o * 3 + 2] = z;
+        if (dirs) { dirs[o * 3 + 0] = r.dx; dirs[o * 3 + 1] = r.dy; dirs[o * 3 + 2] = r.dz; }
+        reinterpret_cast<float2 *>(deltas + o * 4)[0] = make_float2(dt, t_after - prev_t);
+    }
+    last_t = tl[63 - __builtin_clzll(sample_mask)];
 }
 
 template <bool EMIT>
@@ -506,37 +377,9 @@ k_march_wpr(const float *__restrict__ rays_o, const float *__restrict__ rays_d, 
     const RmCfg c = rm_cfg(bound, dt_gamma, max_steps, C, H, grid);
     const RmRay r = rm_load_ray(rays_o, rays_d, n);
     const float far = fars[n];
-    float t_block = nears[n];
-    {
-#pragma clang fp contract(off)
-        const float noise = noises ? noises[n] : 0.0f;
-        t_block += rm_clamp(t_block * dt_gamma, c.dt_min, c.dt_max) * noise;   // :452
-    }
+    float t_block = rm_start_t(c, nears[n], noises ? noises[n] : 0.0f);
     uint32_t limit = max_steps, point_index = 0;
-    if (EMIT) {
-        // offsets: base of this ray's 256-ray block + the counts of the rays before it in the block
-        const uint32_t blk0 = (n / RM_BLOCK) * RM_BLOCK;
-        uint32_t part = 0;
-        for (uint32_t i = blk0 + lane; i < n; i += 64) part += counts[i];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
-        point_index = block_bases[n / RM_BLOCK] + part;
-        limit = counts[n];
-        if (lane == 0) {
-            rays[n * 3 + 0] = (int32_t)n;
-            rays[n * 3 + 1] = (int32_t)point_index;
-            rays[n * 3 + 2] = (int32_t)limit;
-        }
-        if (limit == 0) return;
-        if (point_index + limit >= M) {          // :517; zero the in-buffer part of a dropped ray (see k_march_emit)
-            for (uint32_t i = point_index + lane; i < min(point_index + limit, M); i += 64) {
-                xyzs[(size_t)i * 3 + 0] = 0.f; xyzs[(size_t)i * 3 + 1] = 0.f; xyzs[(size_t)i * 3 + 2] = 0.f;
-                if (dirs) { dirs[(size_t)i * 3 + 0] = 0.f; dirs[(size_t)i * 3 + 1] = 0.f; dirs[(size_t)i * 3 + 2] = 0.f; }
-                reinterpret_cast<float4 *>(deltas)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            return;
-        }
-    }
+    if (EMIT && !rm_wave_ray_begin(n, lane, M, counts, block_bases, xyzs, dirs, deltas, rays, point_index, limit)) return;
     uint32_t steps = 0;
     float carry_tt = -INFINITY;       // the walk enters a block at its first t >= carry_tt
     float last_t = t_block;           // :530, t after the previous sample's step
@@ -590,26 +433,8 @@ k_march_wpr(const float *__restrict__ rays_o, const float *__restrict__ rays_d, 
         if (!done && last < 64)
             carry_tt = ((occ_mask >> last) & 1ull) ? -INFINITY : __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tt), (int)last));
         // ---- emit this block's samples ----
-        if (EMIT && sample_mask) {
-#pragma clang fp contract(off)
-            const bool mine = (sample_mask >> lane) & 1ull;
-            const uint32_t before = (uint32_t)__popcll(sample_mask & ((1ull << lane) - 1ull));
-            const uint32_t first_idx = steps - (uint32_t)__popcll(sample_mask);       // samples emitted before this block
-            const float t_after = my_t + dt;                                            // t += dt, :551
-            __builtin_amdgcn_wave_barrier();
-            tl[lane] = t_after;
-            __builtin_amdgcn_wave_barrier();
-            // t after the previous sample's step: previous sample lane of this block, or the carried one
-            const unsigned long long below = sample_mask & ((1ull << lane) - 1ull);
-            const float prev_t = below ? tl[63 - __builtin_clzll(below)] : last_t;
-            if (mine) {
-                const size_t o = (size_t)point_index + first_idx + before;
-                xyzs[o * 3 + 0] = x; xyzs[o * 3 + 1] = y; xyzs[o * 3 + 2] = z;
-                if (dirs) { dirs[o * 3 + 0] = r.dx; dirs[o * 3 + 1] = r.dy; dirs[o * 3 + 2] = r.dz; }
-                reinterpret_cast<float2 *>(deltas + o * 4)[0] = make_float2(dt, t_after - prev_t);
-            }
-            last_t = tl[63 - __builtin_clzll(sample_mask)];
-        }
+        if (EMIT && sample_mask)
+            wpr_emit_block(r, sample_mask, lane, steps, point_index, x, y, z, dt, my_t + dt, tl, last_t, xyzs, dirs, deltas);
         __builtin_amdgcn_wave_barrier();
         if (!EMIT && slots != nullptr) {
             if (lane < 3) {
@@ -628,7 +453,7 @@ k_march_wpr(const float *__restrict__ rays_o, const float *__restrict__ rays_d, 
 
 // Emitting pass of the wave-per-ray march from the counting pass's records: no occupancy probe, no successor search, no chain
 // walk -- per recorded block with samples: the 64 parameters again (wpr_block_t), positions and step sizes of the marked lanes,
-// the same stores as k_march_wpr<true>.  Bit-identical output; 4 096-ray bf16 + graph step 1.09 -> 0.96 ms.
+// the stores of wpr_emit_block.  Bit-identical output; 4 096-ray bf16 + graph step 1.09 -> 0.96 ms.
 __global__ void __launch_bounds__(256)
 k_march_wpr_replay(const float *__restrict__ rays_o, const float *__restrict__ rays_d, float bound, float dt_gamma, uint32_t max_steps,
                    uint32_t N, uint32_t C, uint32_t H, uint32_t M, const uint32_t *__restrict__ counts,
@@ -641,27 +466,8 @@ k_march_wpr_replay(const float *__restrict__ rays_o, const float *__restrict__ r
     float *tl = t_lds[wave];
     const RmCfg c = rm_cfg(bound, dt_gamma, max_steps, C, H, nullptr);
     const RmRay r = rm_load_ray(rays_o, rays_d, n);
-    const uint32_t blk0 = (n / RM_BLOCK) * RM_BLOCK;
-    uint32_t part = 0;
-    for (uint32_t i = blk0 + lane; i < n; i += 64) part += counts[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
-    const uint32_t point_index = block_bases[n / RM_BLOCK] + part;
-    const uint32_t limit = counts[n];
-    if (lane == 0) {
-        rays[n * 3 + 0] = (int32_t)n;
-        rays[n * 3 + 1] = (int32_t)point_index;
-        rays[n * 3 + 2] = (int32_t)limit;
-    }
-    if (limit == 0) return;
-    if (point_index + limit >= M) {          // :517; zero the in-buffer part of a dropped ray (see k_march_emit)
-        for (uint32_t i = point_index + lane; i < min(point_index + limit, M); i += 64) {
-            xyzs[(size_t)i * 3 + 0] = 0.f; xyzs[(size_t)i * 3 + 1] = 0.f; xyzs[(size_t)i * 3 + 2] = 0.f;
-            if (dirs) { dirs[(size_t)i * 3 + 0] = 0.f; dirs[(size_t)i * 3 + 1] = 0.f; dirs[(size_t)i * 3 + 2] = 0.f; }
-            reinterpret_cast<float4 *>(deltas)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        return;
-    }
+    uint32_t point_index, limit;
+    if (!rm_wave_ray_begin(n, lane, M, counts, block_bases, xyzs, dirs, deltas, rays, point_index, limit)) return;
     const uint32_t nblk = min(slots[n], min(slot_cap, 64u));
     // lane b holds block b's record
     const uint32_t *rec = slots + (size_t)N + (size_t)n * slot_cap * 3;
@@ -686,244 +492,8 @@ k_march_wpr_replay(const float *__restrict__ rays_o, const float *__restrict__ r
             dt = rm_clamp(my_t * c.dt_gamma, c.dt_min, c.dt_max);
             t_after = my_t + dt;                                            // t += dt, :551
         }
-        const bool mine = (sample_mask >> lane) & 1ull;
-        const uint32_t before = (uint32_t)__popcll(sample_mask & ((1ull << lane) - 1ull));
-        const uint32_t first_idx = steps - (uint32_t)__popcll(sample_mask);
+        wpr_emit_block(r, sample_mask, lane, steps, point_index, x, y, z, dt, t_after, tl, last_t, xyzs, dirs, deltas);
         __builtin_amdgcn_wave_barrier();
-        tl[lane] = t_after;
-        __builtin_amdgcn_wave_barrier();
-        const unsigned long long below = sample_mask & ((1ull << lane) - 1ull);
-        const float prev_t = below ? tl[63 - __builtin_clzll(below)] : last_t;
-        if (mine) {
-            const size_t o = (size_t)point_index + first_idx + before;
-            xyzs[o * 3 + 0] = x; xyzs[o * 3 + 1] = y; xyzs[o * 3 + 2] = z;
-            if (dirs) { dirs[o * 3 + 0] = r.dx; dirs[o * 3 + 1] = r.dy; dirs[o * 3 + 2] = r.dz; }
-            float dprev;
-            {
-#pragma clang fp contract(off)
-                dprev = t_after - prev_t;
-            }
-            reinterpret_cast<float2 *>(deltas + o * 4)[0] = make_float2(dt, dprev);
-        }
-        last_t = tl[63 - __builtin_clzll(sample_mask)];
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// compositing: the training composite lives in composite.hip (wave per ray, lane per sample)
-// ---------------------------------------------------------------------------------------------
-#define RM_MAXC 16
-
-// Single-pass inference composite: the arithmetic of kernel_composite_rays (raymarching.cu:1133-1231)
-// -- T = 1 - weight_sum, stop test on T BEFORE the sample (:1206), absolute t starting at near --
-// applied to the compacted [offset, offset+count) samples of the training-style march instead of
-// up to 1024 host-driven march_rays / composite_rays iterations (renderer.py:266-285).
-template <int LPR>
-__global__ void __launch_bounds__(RM_BLOCK)
-k_composite_infer(const float *__restrict__ sigmas, const float *__restrict__ rgbs, const float *__restrict__ deltas,
-                  const int32_t *__restrict__ rays, const float *__restrict__ nears, uint32_t M, uint32_t N, uint32_t C,
-                  float T_thresh, float *__restrict__ weights_sum, float *__restrict__ depth, float *__restrict__ image) {
-    const uint32_t tid = blockIdx.x * RM_BLOCK + threadIdx.x;
-    const uint32_t n = tid / LPR, ch = tid % LPR;
-    if (n >= N) return;
-    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
-    const bool has_ch = ch < C;
-    float acc = 0.0f, ws = 0.0f, d = 0.0f;
-    if (!(num_steps == 0 || offset + num_steps >= M)) {
-        float t_phy = nears[index];
-        const float *s = sigmas + offset;
-        const float *rgb = rgbs + (size_t)offset * C + (has_ch ? ch : 0);
-        const float *dl = deltas + (size_t)offset * 4;
-        for (uint32_t step = 0; step < num_steps; step++) {
-            const float2 dd = *reinterpret_cast<const float2 *>(dl + step * 4);
-            const float alpha = 1.0f - __expf(-s[step] * dd.x);
-            const float T = 1 - ws;
-            const float weight = alpha * T;
-            ws += weight;
-            t_phy += dd.y;
-            d += weight * t_phy;
-            if (has_ch) acc += weight * rgb[(size_t)step * C];
-            if (T < T_thresh) break;   // :1206
-        }
-    }
-    if (ch == 0) {
-        weights_sum[index] = ws;
-        depth[index] = d;
-    }
-    if (has_ch) image[(size_t)index * C + ch] = acc;
-}
-
-// ---------------------------------------------------------------------------------------------
-// inference march / composite (raymarching.cu:1004-1120, 1133-1231)
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RM_BLOCK)
-k_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *__restrict__ rays_alive, const float *__restrict__ rays_t,
-             const float *__restrict__ rays_o, const float *__restrict__ rays_d, const float *__restrict__ z_hats,
-             float bound, float dt_gamma, uint32_t max_steps, int is_ndc, uint32_t C, uint32_t H,
-             const uint8_t *__restrict__ grid, const float *__restrict__ fars, float *__restrict__ xyzs,
-             float *__restrict__ dirs, float *__restrict__ deltas, const float *__restrict__ noises) {
-    const uint32_t n = blockIdx.x * RM_BLOCK + threadIdx.x;
-    if (n >= n_alive) return;
-    const int index = rays_alive[n];
-    const RmCfg c = rm_cfg(bound, dt_gamma, max_steps, C, H, grid);
-    const RmRay r = rm_load_ray(rays_o, rays_d, (uint32_t)index);
-    float *pxyz = xyzs + (size_t)n * n_step * 3;
-    float *pdir = dirs ? dirs + (size_t)n * n_step * 3 : nullptr;
-    float *pdel = deltas + (size_t)n * n_step * 4;
-    float t = rays_t[(size_t)index * (is_ndc ? 2 : 1)];
-    const float far = fars[index];
-    {
-#pragma clang fp contract(off)
-        const float noise = noises ? noises[n] : 0.0f;
-        t += rm_clamp(t * dt_gamma, c.dt_min, c.dt_max) * noise;   // :1053
-    }
-    uint32_t step = 0;
-    float last_t = t;
-    float last_z = rm_clamp(r.oz + t * r.dz, -bound, bound);
-    float x, y, z, dt, tt;
-    while (t < far && step < n_step) {
-        if (rm_probe(r, c, t, x, y, z, dt, tt)) {
-#pragma clang fp contract(off)
-            pxyz[0] = x; pxyz[1] = y; pxyz[2] = z;
-            if (pdir) { pdir[0] = r.dx; pdir[1] = r.dy; pdir[2] = r.dz; pdir += 3; }
-            t += dt;
-            pdel[0] = dt;
-            pdel[1] = t - last_t;
-            if (is_ndc) {
-                const float new_z = rm_clamp(r.oz + t * r.dz, -bound, bound);
-                const float zh = z_hats[index];
-                pdel[2] = (2 / (new_z - 1) - 2 / (z - 1)) / zh;
-                pdel[3] = (2 / (new_z - 1) - 2 / (last_z - 1)) / zh;
-                last_z = new_z;
-            }
-            last_t = t;
-            pxyz += 3; pdel += 4;
-            step++;
-        } else {
-            rm_skip(c, t, tt);
-        }
-    }
-    // The reference relies on the caller zero-filling deltas (raymarching.py:409-412) so that an
-    // unused tail reads delta == 0 (= "ray terminated", :1178).  Write the terminator here so the
-    // caller does not have to memset [n_alive*n_step, 4] floats per iteration.
-    for (; step < n_step; step++) {
-        pdel[0] = 0.0f;
-        pdel += 4;
-    }
-}
-
-__global__ void __launch_bounds__(RM_BLOCK)
-k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *__restrict__ rays_alive,
-                 float *__restrict__ rays_t, const float *__restrict__ sigmas, const float *__restrict__ rgbs,
-                 const float *__restrict__ deltas, uint32_t C, int is_ndc, float *__restrict__ weights_sum,
-                 float *__restrict__ depth, float *__restrict__ image) {
-    const uint32_t n = blockIdx.x * RM_BLOCK + threadIdx.x;
-    if (n >= n_alive) return;
-    const int index = rays_alive[n];
-    const float *s = sigmas + (size_t)n * n_step;
-    const float *rgb = rgbs + (size_t)n * n_step * C;
-    const float *dl = deltas + (size_t)n * n_step * 4;
-    float *rt = rays_t + (size_t)index * (is_ndc ? 2 : 1);
-    float *img = image + (size_t)index * C;
-    float t_rm = 0.0f, t_phy;
-    if (is_ndc) { t_rm = rt[0]; t_phy = rt[1]; } else { t_phy = rt[0]; }
-    float weight_sum = weights_sum[index];
-    float d = depth[index];
-    float acc[RM_MAXC];
-#pragma unroll
-    for (int i = 0; i < RM_MAXC; i++) acc[i] = (uint32_t)i < C ? img[i] : 0.0f;
-    uint32_t step = 0;
-    while (step < n_step) {
-        if (dl[0] == 0) break;   // :1178
-        const float alpha = 1.0f - __expf(-s[0] * (is_ndc ? dl[2] : dl[0]));
-        const float T = 1 - weight_sum;
-        const float weight = alpha * T;
-        weight_sum += weight;
-        if (is_ndc) { t_rm += dl[1]; t_phy += dl[3]; } else { t_phy += dl[1]; }
-        d += weight * t_phy;
-#pragma unroll
-        for (int i = 0; i < RM_MAXC; i++)
-            if ((uint32_t)i < C) acc[i] += weight * rgb[i];
-        if (T < T_thresh) break;   // :1206
-        s++; rgb += C; dl += 4; step++;
-    }
-    if (step < n_step) {
-        rays_alive[n] = -1;
-    } else {
-        if (is_ndc) { rt[0] = t_rm; rt[1] = t_phy; } else { rt[0] = t_phy; }
-    }
-    weights_sum[index] = weight_sum;
-    depth[index] = d;
-#pragma unroll
-    for (int i = 0; i < RM_MAXC; i++)
-        if ((uint32_t)i < C) img[i] = acc[i];
-}
-
-// ---------------------------------------------------------------------------------------------
-// alive-ray compaction (replaces rays_alive[rays_alive >= 0], renderer.py:284)
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RM_BLOCK)
-k_alive_count(const int32_t *__restrict__ rays_alive, uint32_t n_alive, uint32_t *__restrict__ block_sums) {
-    __shared__ uint32_t wave_sums[RM_BLOCK / 64];
-    const uint32_t n = blockIdx.x * RM_BLOCK + threadIdx.x;
-    const uint32_t keep = (n < n_alive && rays_alive[n] >= 0) ? 1u : 0u;
-    // one ballot per wave instead of a shuffle scan: popcount of the 64-bit mask
-    const unsigned long long mask = __ballot(keep);
-    if ((threadIdx.x & 63u) == 0) wave_sums[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (uint32_t w = 0; w < RM_BLOCK / 64; w++) t += wave_sums[w];
-        block_sums[blockIdx.x] = t;
-    }
-}
-
-__global__ void __launch_bounds__(RM_BLOCK)
-k_alive_write(const int32_t *__restrict__ rays_alive, uint32_t n_alive, const uint32_t *__restrict__ block_bases,
-              int32_t *__restrict__ out) {
-    __shared__ uint32_t wave_sums[RM_BLOCK / 64];
-    const uint32_t n = blockIdx.x * RM_BLOCK + threadIdx.x;
-    const int32_t v = n < n_alive ? rays_alive[n] : -1;
-    const bool keep = v >= 0;
-    const unsigned long long mask = __ballot(keep);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_sums[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    uint32_t base = block_bases[blockIdx.x];
-    for (uint32_t w = 0; w < wave; w++) base += wave_sums[w];
-    if (keep) out[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = v;
-}
-
-__global__ void k_store_scan_total(const int32_t *__restrict__ counter2, int32_t *__restrict__ n_out) {
-    n_out[0] = counter2[0];
-}
-
-// ---------------------------------------------------------------------------------------------
-// device ray generation (nerf_lib.py:69-142, common.py:139-147)
-// ---------------------------------------------------------------------------------------------
-__global__ void k_generate_rays(const float *__restrict__ pose, uint32_t w, uint32_t h, float fx, float fy, float cx,
-                                float cy, int camera_flip, const int32_t *__restrict__ pix, uint32_t N,
-                                float *__restrict__ rays_o, float *__restrict__ rays_d) {
-#pragma clang fp contract(off)
-    const float r00 = pose[0], r01 = pose[1], r02 = pose[2], tx = pose[3];
-    const float r10 = pose[4], r11 = pose[5], r12 = pose[6], ty = pose[7];
-    const float r20 = pose[8], r21 = pose[9], r22 = pose[10], tz = pose[11];
-    const float f0 = (camera_flip >> 2) & 1 ? -1.0f : 1.0f;   // nerf_lib.py:121, bit order [2,1,0]
-    const float f1 = (camera_flip >> 1) & 1 ? -1.0f : 1.0f;
-    const float f2 = (camera_flip >> 0) & 1 ? -1.0f : 1.0f;
-    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
-        const uint32_t p = pix ? (uint32_t)pix[n] : n;
-        const uint32_t py = p / w, px = p - py * w;
-        // np.linspace(0, w, 2w+1)[1::2] == x + 0.5 exactly in fp32 for w < 2^22
-        const float i = (float)px + 0.5f, j = (float)py + 0.5f;
-        const float d0 = ((i - cx) / fx) * f0, d1 = ((j - cy) / fy) * f1, d2 = f2;
-        const float wx = r00 * d0 + r01 * d1 + r02 * d2;
-        const float wy = r10 * d0 + r11 * d1 + r12 * d2;
-        const float wz = r20 * d0 + r21 * d1 + r22 * d2;
-        const float nrm = sqrtf(wx * wx + wy * wy + wz * wz);
-        rays_d[n * 3 + 0] = wx / nrm; rays_d[n * 3 + 1] = wy / nrm; rays_d[n * 3 + 2] = wz / nrm;
-        rays_o[n * 3 + 0] = tx; rays_o[n * 3 + 1] = ty; rays_o[n * 3 + 2] = tz;
     }
 }
 
@@ -931,50 +501,6 @@ __global__ void k_generate_rays(const float *__restrict__ pose, uint32_t w, uint
 // C ABI
 // ---------------------------------------------------------------------------------------------
 extern "C" {
-
-const char *nsr_status_string(int status) {
-    switch (status) {
-        case NSR_OK: return "ok";
-        case NSR_ERR_INVALID_ARG: return "invalid argument (null pointer, bad size or enum)";
-        case NSR_ERR_UNSUPPORTED: return "unsupported configuration for the gfx950 kernels";
-        case NSR_ERR_LAUNCH: return "HIP kernel launch failed";
-        default: return "unknown status";
-    }
-}
-int nsr_abi_version(void) { return 6; }
-const char *nsr_target_arch(void) { return "gfx950"; }
-
-int nsr_near_far_from_aabb(const float *rays_o, const float *rays_d, const float *aabb, uint32_t N, float min_near,
-                           float *nears, float *fars, nsr_stream_t stream) {
-    if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(rays_o); NSR_CHECK_PTR(rays_d); NSR_CHECK_PTR(aabb); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
-    hipLaunchKernelGGL(k_near_far_from_aabb, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d,
-                       aabb, N, min_near, nears, fars);
-    return nsr_launch_status();
-}
-
-int nsr_morton3d(const int32_t *coords, uint32_t N, int32_t *indices, nsr_stream_t stream) {
-    if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(coords); NSR_CHECK_PTR(indices);
-    hipLaunchKernelGGL(k_morton3d, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, coords, N, indices);
-    return nsr_launch_status();
-}
-
-int nsr_morton3d_invert(const int32_t *indices, uint32_t N, int32_t *coords, nsr_stream_t stream) {
-    if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(coords); NSR_CHECK_PTR(indices);
-    hipLaunchKernelGGL(k_morton3d_invert, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, indices, N, coords);
-    return nsr_launch_status();
-}
-
-int nsr_packbits(const float *grid, uint32_t N, float density_thresh, uint8_t *bitfield, nsr_stream_t stream) {
-    if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(grid); NSR_CHECK_PTR(bitfield);
-    if (((uintptr_t)grid & 15u) != 0) return NSR_ERR_INVALID_ARG;   // 16-byte loads
-    hipLaunchKernelGGL(k_packbits, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, grid, N, density_thresh,
-                       bitfield);
-    return nsr_launch_status();
-}
 
 // step-index capacity of the sample mask: t runs from near to far (<= the AABB diagonal 2 sqrt(3) bound) in steps of at
 // least dt_min = 2 sqrt(3) / max_steps, i.e. at most bound * max_steps additions; + slack for the rounding of the sums
@@ -1008,6 +534,11 @@ int nsr_march_rays_train(const float *rays_o, const float *rays_d, const float *
     const uint32_t nblocks = (N + RM_BLOCK - 1) / RM_BLOCK;
     uint32_t *counts = (uint32_t *)workspace;
     uint32_t *block_sums = counts + N;
+    // Which input reaches which kernels (all bit-identical to the sequential reference):
+    //   not NDC, N <= 20 480: k_march_wpr<false> counts and records, k_march_wpr_replay emits (k_march_wpr<true> when a ray can
+    //                         need more records than a wave has lanes)
+    //   not NDC, N >  20 480: k_march_count marks the samples in the mask, k_march_emit_mask replays it
+    //   NDC, every N:         k_march_count without the mask, k_march_emit_ndc marches again
     // small batches: one wave per ray (k_march_wpr), bit-identical results
     if (!is_ndc && N <= NSR_MARCH_WPR_MAX_RAYS) {
         const uint32_t wblocks = (N + 3) / 4;
@@ -1019,7 +550,7 @@ int nsr_march_rays_train(const float *rays_o, const float *rays_d, const float *
                            H, M, nears, fars, noises, counts, (const uint32_t *)nullptr, (float *)nullptr, (float *)nullptr,
                            (float *)nullptr, (int32_t *)nullptr, slots, slot_cap);
         hipLaunchKernelGGL(k_march_block_sums, dim3(nblocks), dim3(RM_BLOCK), 0, s, counts, N, block_sums);
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, nblocks, counter, N);
+        rm_scan_block_sums(block_sums, nblocks, counter, N, s);
         if (slots)
             hipLaunchKernelGGL(k_march_wpr_replay, dim3(wblocks), dim3(256), 0, s, rays_o, rays_d, bound, dt_gamma, max_steps, N, C, H, M,
                                counts, block_sums, slots, slot_cap, xyzs, dirs, deltas, rays);
@@ -1037,9 +568,9 @@ int nsr_march_rays_train(const float *rays_o, const float *rays_d, const float *
                        C, H, nears, fars, noises, counts, block_sums, mask, kcap);
     // the reference's ray slots start at the incoming counter[1]; only 0 is supported without a
     // host read (renderer.py:213-214 zeroes the counter before every call)
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, nblocks, counter, N);
+    rm_scan_block_sums(block_sums, nblocks, counter, N, s);
     // The replaying emit is bound by its stores: every lane appends 12 + 8 bytes at a time to its own ray's two runs, and with
-    // the ~30 waves per CU its 32 registers allow, more partially written lines are open than the L2 holds.  60 KB of (unused)
+    // the ~30 waves per CU its 41 registers allow, more partially written lines are open than the L2 holds.  60 KB of (unused)
     // dynamic LDS per workgroup keeps two workgroups per CU: 1.12-1.20 -> 0.87-1.09 ms on the bench frame (box to box); the
     // closed-form step of k_march_emit_mask takes another ~15 us at that occupancy, nothing at full occupancy.
     constexpr size_t emit_lds = 61440;
@@ -1047,88 +578,8 @@ int nsr_march_rays_train(const float *rays_o, const float *rays_d, const float *
         hipLaunchKernelGGL(k_march_emit_mask, dim3(nblocks), dim3(RM_BLOCK), emit_lds, s, rays_o, rays_d, bound, dt_gamma, max_steps, N, C,
                            H, M, nears, noises, counts, block_sums, mask, xyzs, dirs, deltas, rays);
     else
-        hipLaunchKernelGGL(k_march_emit, dim3(nblocks), dim3(RM_BLOCK), 0, s, rays_o, rays_d, z_hats, grid, bound, dt_gamma,
-                           max_steps, is_ndc, N, C, H, M, nears, fars, noises, counts, block_sums, 0u, xyzs, dirs, deltas, rays);
-    return nsr_launch_status();
-}
-
-int nsr_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t, const float *rays_o,
-                   const float *rays_d, const float *z_hats, float bound, float dt_gamma, uint32_t max_steps, int is_ndc,
-                   uint32_t C, uint32_t H, const uint8_t *grid, const float *nears, const float *fars, float *xyzs,
-                   float *dirs, float *deltas, const float *noises, nsr_stream_t stream) {
-    if (n_alive == 0 || n_step == 0) return NSR_OK;
-    NSR_CHECK_PTR(rays_alive); NSR_CHECK_PTR(rays_t); NSR_CHECK_PTR(rays_o); NSR_CHECK_PTR(rays_d); NSR_CHECK_PTR(grid);
-    NSR_CHECK_PTR(fars); NSR_CHECK_PTR(xyzs); NSR_CHECK_PTR(deltas);
-    (void)nears;
-    if (is_ndc && z_hats == nullptr) return NSR_ERR_INVALID_ARG;
-    if (max_steps == 0 || C == 0 || C > 8 || H == 0 || H > 1024) return NSR_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(k_march_rays, dim3(nsr_div_up(n_alive, RM_BLOCK)), dim3(RM_BLOCK), 0, (hipStream_t)stream, n_alive,
-                       n_step, rays_alive, rays_t, rays_o, rays_d, z_hats, bound, dt_gamma, max_steps, is_ndc, C, H, grid, fars,
-                       xyzs, dirs, deltas, noises);
-    return nsr_launch_status();
-}
-
-int nsr_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t *rays_alive, float *rays_t,
-                       const float *sigmas, const float *rgbs, const float *deltas, uint32_t C, int is_ndc,
-                       float *weights_sum, float *depth, float *image, nsr_stream_t stream) {
-    if (n_alive == 0 || n_step == 0) return NSR_OK;
-    NSR_CHECK_PTR(rays_alive); NSR_CHECK_PTR(rays_t); NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(rgbs); NSR_CHECK_PTR(deltas);
-    NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(depth); NSR_CHECK_PTR(image);
-    if (C == 0 || C > RM_MAXC) return NSR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_composite_rays, dim3(nsr_div_up(n_alive, RM_BLOCK)), dim3(RM_BLOCK), 0, (hipStream_t)stream, n_alive,
-                       n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, C, is_ndc, weights_sum, depth, image);
-    return nsr_launch_status();
-}
-
-int nsr_composite_rays_infer(const float *sigmas, const float *rgbs, const float *deltas, const int32_t *rays, const float *nears,
-                             uint32_t M, uint32_t N, uint32_t C, float T_thresh, float *weights_sum, float *depth, float *image,
-                             nsr_stream_t stream) {
-    if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(rgbs); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(nears);
-    NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(depth); NSR_CHECK_PTR(image);
-    if (C == 0 || C > RM_MAXC) return NSR_ERR_UNSUPPORTED;
-    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
-    hipStream_t hs = (hipStream_t)stream;
-#define NSR_CI(LPR)                                                                                                 \
-    hipLaunchKernelGGL((k_composite_infer<LPR>), dim3(nsr_div_up((uint64_t)N * LPR, RM_BLOCK)), dim3(RM_BLOCK), 0, hs, \
-                       sigmas, rgbs, deltas, rays, nears, M, N, C, T_thresh, weights_sum, depth, image)
-    if (C <= 4) NSR_CI(4); else if (C <= 8) NSR_CI(8); else NSR_CI(16);
-#undef NSR_CI
-    return nsr_launch_status();
-}
-
-uint64_t nsr_compact_alive_workspace_bytes(uint32_t n_alive) {
-    const uint64_t nblocks = (n_alive + RM_BLOCK - 1) / RM_BLOCK;
-    return (nblocks + 64) * sizeof(uint32_t);
-}
-
-int nsr_compact_alive(const int32_t *rays_alive, uint32_t n_alive, int32_t *out, int32_t *n_out, void *workspace,
-                      nsr_stream_t stream) {
-    NSR_CHECK_PTR(n_out);
-    hipStream_t s = (hipStream_t)stream;
-    if (n_alive == 0) {
-        return hipMemsetAsync(n_out, 0, sizeof(int32_t), s) == hipSuccess ? NSR_OK : NSR_ERR_LAUNCH;
-    }
-    NSR_CHECK_PTR(rays_alive); NSR_CHECK_PTR(out); NSR_CHECK_PTR(workspace);
-    const uint32_t nblocks = (n_alive + RM_BLOCK - 1) / RM_BLOCK;
-    uint32_t *block_sums = (uint32_t *)workspace;
-    int32_t *counter2 = (int32_t *)(block_sums + nblocks);   // scratch {total, unused}
-    if (hipMemsetAsync(counter2, 0, 2 * sizeof(int32_t), s) != hipSuccess) return NSR_ERR_LAUNCH;
-    hipLaunchKernelGGL(k_alive_count, dim3(nblocks), dim3(RM_BLOCK), 0, s, rays_alive, n_alive, block_sums);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, block_sums, nblocks, counter2, 0u);
-    hipLaunchKernelGGL(k_alive_write, dim3(nblocks), dim3(RM_BLOCK), 0, s, rays_alive, n_alive, block_sums, out);
-    hipLaunchKernelGGL(k_store_scan_total, dim3(1), dim3(1), 0, s, counter2, n_out);
-    return nsr_launch_status();
-}
-
-int nsr_generate_rays(const float *pose, uint32_t w, uint32_t h, float fx, float fy, float cx, float cy, int camera_flip,
-                      const int32_t *pix, uint32_t N, float *rays_o, float *rays_d, nsr_stream_t stream) {
-    if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(pose); NSR_CHECK_PTR(rays_o); NSR_CHECK_PTR(rays_d);
-    if (w == 0 || h == 0) return NSR_ERR_INVALID_ARG;
-    if (pix == nullptr && (uint64_t)N != (uint64_t)w * h) return NSR_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(k_generate_rays, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, pose, w, h, fx, fy, cx, cy,
-                       camera_flip, pix, N, rays_o, rays_d);
+        hipLaunchKernelGGL(k_march_emit_ndc, dim3(nblocks), dim3(RM_BLOCK), 0, s, rays_o, rays_d, z_hats, grid, bound, dt_gamma,
+                           max_steps, N, C, H, M, nears, fars, noises, counts, block_sums, xyzs, dirs, deltas, rays);
     return nsr_launch_status();
 }
 

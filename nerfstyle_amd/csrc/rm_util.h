@@ -1,5 +1,5 @@
-// Morton code and block-scan helpers shared by the ray-march (raymarch.hip) and occupancy-update
-// (occupancy.hip) kernels.
+// Morton code and block-scan helpers shared by the ray-march (rm_probe.h, raymarch.hip, raymarch_infer.hip, ray_util.hip)
+// and occupancy-update (occupancy.hip) kernels.
 #pragma once
 #include "nsr_common.h"
 
@@ -50,3 +50,7 @@ __device__ __forceinline__ uint32_t rm_block_exclusive_scan(uint32_t v, uint32_t
     return wave_prefix + incl - v;
 }
 
+// Launches the one-block exclusive scan of per-block totals (k_scan_block_sums, raymarch.hip) that turns them into block
+// bases: shared by the training march and the alive-ray compaction, and not part of the C ABI.
+__attribute__((visibility("hidden"))) void rm_scan_block_sums(uint32_t *block_sums, uint32_t nblocks, int32_t *counter, uint32_t N,
+                                                              hipStream_t stream);

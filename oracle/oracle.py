@@ -112,9 +112,10 @@ def packbits(grid, thresh):
 
 
 def march_rays_train(rays_o, rays_d, bound, bitfield, C, H, nears, fars, max_steps=1024,
-                     dt_gamma=0.0, M=None, align=-1, counter=None, want_dirs=True):
+                     dt_gamma=0.0, M=None, align=-1, counter=None, want_dirs=True, z_hats=None, is_ndc=False):
     """raymarching.py:174-288 (force_all_rays semantics: M = N * max_steps, perturb disabled
-    :247, slice to the emitted count padded to `align` :275-281) / raymarching.cu:410-599."""
+    :247, slice to the emitted count padded to `align` :275-281) / raymarching.cu:410-599.
+    is_ndc fills deltas[:, 2:] from the per-ray z_hats (:563-570)."""
     o, po = _f(rays_o)
     d, pd = _f(rays_d)
     g, pg = _u8(bitfield)
@@ -130,7 +131,9 @@ def march_rays_train(rays_o, rays_d, bound, bitfield, C, H, nears, fars, max_ste
     if counter is None:
         counter = np.zeros(2, np.int32)
     noises = np.zeros(N, np.float32)
-    lib().ora_march_rays_train(po, pd, None, pg, F(bound), F(dt_gamma), U(max_steps), I(0), U(N), U(C),
+    assert not is_ndc or z_hats is not None
+    zh, pzh = _f(z_hats) if is_ndc else (None, None)
+    lib().ora_march_rays_train(po, pd, pzh, pg, F(bound), F(dt_gamma), U(max_steps), I(int(bool(is_ndc))), U(N), U(C),
                                U(H), U(M), pne, pfa, xyzs.ctypes.data_as(c_f),
                                dirs.ctypes.data_as(c_f) if want_dirs else None,
                                deltas.ctypes.data_as(c_f), rays.ctypes.data_as(c_i),

@@ -63,6 +63,36 @@ def test_march_rays_train_bit_exact(O, dev, n_rays, max_steps, dt_gamma):
     assert rays_o[:, 2].sum() > 0
 
 
+@pytest.mark.parametrize('n_rays,max_steps,dt_gamma', [(4096, 1024, 0.), (24001, 1024, 0.), (22001, 1024, 1. / 256)])
+def test_march_rays_train_ndc_bit_exact(O, dev, n_rays, max_steps, dt_gamma):
+    """The NDC march (is_ndc: the re-marching emit at every batch size, deltas columns 2 and 3 from the sample's, the
+    next and the previous sample's z over the ray's z_hat, raymarching.cu:563-570) against the sequential oracle, bit for
+    bit, below and above the 20 480 rays that split the non-NDC paths.  z == 1 would make a column infinite and
+    inf - inf a NaN, which array_equal rejects whatever the kernel does: the seeds are ones where the oracle's deltas
+    are all finite, and that is asserted."""
+    from nerfstyle_amd import raymarching as R
+    grid, bits = small_scene()
+    ro, rd = room_rays(O, n_rays, seed=n_rays)
+    near, far = O.near_far_from_aabb(ro, rd, AABB, 0.2)
+    z_hats = np.random.default_rng(n_rays).uniform(0.5, 2.0, n_rays).astype(np.float32)
+    xo, do, dlo, rays_o, cnt_o = O.march_rays_train(ro, rd, 2.0, bits, 2, 128, near, far, max_steps, dt_gamma=dt_gamma, align=128,
+                                                    z_hats=z_hats, is_ndc=True)
+    assert np.isfinite(dlo).all()
+    assert rays_o[:, 2].sum() > 0 and np.abs(dlo[:, 2]).max() > 0 and np.abs(dlo[:, 3]).max() > 0
+    counter = torch.zeros(2, dtype=torch.int32, device=dev)
+    x, d, dl, rays = R.march_rays_train(T(ro, dev), T(rd, dev), T(z_hats, dev), 2.0, T(bits, dev), 2, 128, T(near, dev),
+                                        T(far, dev), counter, -1, False, 128, True, dt_gamma, max_steps, True)
+    assert np.array_equal(counter.cpu().numpy(), cnt_o)
+    assert np.array_equal(rays.cpu().numpy(), rays_o)
+    assert x.shape == xo.shape
+    assert np.array_equal(x.cpu().numpy(), xo)
+    dl = dl.cpu().numpy()
+    assert dl.shape == dlo.shape
+    for col in range(4):
+        assert np.array_equal(dl[:, col], dlo[:, col]), col
+    assert np.array_equal(d.cpu().numpy(), do)
+
+
 def test_march_overflow_drop_and_nosync(O, dev):
     """Capacity smaller than the emitted count: rays with offset+count >= M are dropped exactly like
     the reference (raymarching.cu:517) and the no-sync path agrees with the synchronising one."""
