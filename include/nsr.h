@@ -315,6 +315,21 @@ int nsr_sample_order(const float *xyzs, uint32_t M, const int32_t *m_dev, uint32
                      const float *bbox_min, const float *bbox_size, uint32_t *perm, void *workspace,
                      nsr_stream_t stream);
 
+/* Streaming inference render (renderer.py:237-293 as ONE launch per frame): occupancy march, fused field and the inference
+ * composite of nsr_composite_rays_infer in one kernel, with the ray state in registers.  No sample buffer and no capacity:
+ * no ray is ever dropped, and a ray that stopped (T < T_thresh) costs nothing further.  Samples, their order and the
+ * compositing arithmetic are those of nsr_march_rays_train (noises == NULL) + nsr_field_forward + nsr_composite_rays_infer.
+ * order: optional device [N] u32, the ray handled k-th (a permutation of 0..N-1; NULL = identity) -- outputs always land in
+ * the ray's own row.  weights_sum [N], depth [N], image [N, 3 + desc->num_classes] f32 are written, not accumulated; rays
+ * that miss the box (near == far == FLT_MAX) or meet no occupied cell get zeros.  stats: optional device u32[2] that is
+ * ACCUMULATED into: {samples shaded, rays finished}.  C, H: cascades and resolution of `grid` (nsr_march_rays_train's).
+ * No workspace, no host read, capture-safe.  is_ndc != 0, C > 16 or num_classes > 13 -> NSR_ERR_UNSUPPORTED. */
+int nsr_render_rays_infer(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *rays_o,
+                          const float *rays_d, const uint32_t *order, uint32_t N, const float *nears, const float *fars,
+                          const uint8_t *grid, float bound, float dt_gamma, uint32_t max_steps, int is_ndc, uint32_t C,
+                          uint32_t H, float T_thresh, float *weights_sum, float *depth, float *image, uint32_t *stats,
+                          nsr_stream_t stream);
+
 /* fp32 master tables -> f16 gather copy (the reference's `embeddings.to(torch.half)` under
  * autocast, grid.py:42-43).  n = number of scalars. */
 int nsr_cast_f32_to_f16(const float *src, void *dst, uint64_t n, nsr_stream_t stream);

@@ -71,6 +71,8 @@ SIGNATURES = {
     'nsr_mlp_forward': (i32, [vp, vp, u32, u32, u32, u32, u32, i32, i32, vp, vp]),
     'nsr_mlp_backward': (i32, [vp, vp, vp, vp, u32, u32, u32, u32, u32, i32, i32, vp, vp, vp]),
     'nsr_field_forward': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
+    'nsr_render_rays_infer': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, vp, vp, u32, vp, vp, vp, f32, f32, u32, i32, u32, u32,
+                                    f32, vp, vp, vp, vp, vp]),
     'nsr_field_backward': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     'nsr_field_backward_workspace_bytes': (u64, [u32, i32]),
     'nsr_sample_order_workspace_bytes': (u64, [u32]),

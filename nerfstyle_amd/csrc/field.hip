@@ -56,53 +56,15 @@ k_field_fwd(FieldArgs a) {
             fo[1] = xc;
         }
 
-        // ---- density net: 32 -> 64 -> 1 ----------------------------------------------------
-        f4v h[4];
-        s8v hb[2];
-        {
-            const s8v b1[1] = {xd};
-            mm_layer32<CD, 4, 1>(wl + FW_D1, lane, b1, h);
-            mm_pack64<CD, true, true>(h, hb);
-        }
-        f4v o[1];
-        mm_layer32<CD, 1, 2>(wl + FW_D2, lane, hb, o);
-        if (valid && g == 0) a.sigmas[m] = expf(o[0][0]) * a.density_scale;   // tcnn_nerf.py:55-60, renderer.py:225
+        const f4v o = field_density_net<CD>(wl, lane, xd);
+        if (valid && g == 0) a.sigmas[m] = expf(o[0]) * a.density_scale;   // tcnn_nerf.py:55-60, renderer.py:225
         if (SIGMA_ONLY) continue;
 
-        // ---- class net: 32 -> 64 -> nc (rows 3..) -----------------------------------------
-        f4v cls[1];
-        {
-            const s8v b1[1] = {xc};
-            mm_layer32<CD, 4, 1>(wl + FW_K1, lane, b1, h);
-            mm_pack64<CD, true, true>(h, hb);
-            mm_layer32<CD, 1, 2>(wl + FW_K2, lane, hb, cls);
-        }
-        // ---- color1 net: 32 -> 64 -> 16 ----------------------------------------------------
-        f4v c1[1];
-        {
-            const s8v b1[1] = {xc};
-            mm_layer32<CD, 4, 1>(wl + FW_C1A, lane, b1, h);
-            mm_pack64<CD, true, true>(h, hb);
-            mm_layer32<CD, 1, 2>(wl + FW_C1B, lane, hb, c1);
-        }
-        // ---- color2 net: 16 -> 64 -> 64 -> 3, sigmoid --------------------------------------
-        f4v rgb[1];
-        {
-            const s4v c1b = mm_round4<CD, false>(c1[0]);
-            mm_layer16<CD, 4>(wl + FW_R1, lane, c1b, h);
-            mm_pack64<CD, true, true>(h, hb);
-            mm_layer32<CD, 4, 2>(wl + FW_R2, lane, hb, h);
-            mm_pack64<CD, true, true>(h, hb);
-            mm_layer32<CD, 1, 2>(wl + FW_R3, lane, hb, rgb);
-        }
-        // ---- cat(rgb, classes): channel ch = 4g + e (style_nerf.py:141) ---------------------
+        f4v rgb, cls;
+        field_colour_nets<CD>(wl, lane, xc, rgb, cls);
         if (valid) {
             float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int ch = 4 * g + e;
-                v[e] = ch < 3 ? field_sigmoid(rgb[0][e]) : cls[0][e];
-            }
+            field_cat(g, rgb, cls, v);
             float *dst = a.rgbs + (size_t)m * a.C_ch;
             if (a.C_ch == 8) {
                 if (g < 2) reinterpret_cast<float4 *>(dst)[g] = make_float4(v[0], v[1], v[2], v[3]);

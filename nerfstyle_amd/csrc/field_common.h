@@ -1,4 +1,4 @@
-// Shared pieces of the fused field kernels (forward: field.hip, backward: field_bwd.hip).
+// Shared pieces of the fused field kernels (forward: field.hip, backward: field_bwd.hip, inference render: render_infer.hip).
 #pragma once
 #include <hip/hip_fp16.h>
 
@@ -245,6 +245,64 @@ __device__ __forceinline__ void field_encode(const NsrLevel *lds_lv, const TT *_
 }
 
 __device__ __forceinline__ float field_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// ---- the MLP chain of one 16-sample tile, in registers (k_field_fwd and k_render_infer run this one copy) -----------
+// density net: 32 -> 64 -> 1.  Row 0 of the returned tile is the logit: element 0 on the g == 0 lanes.
+template <int CD>
+__device__ __forceinline__ f4v field_density_net(const short *wl, int lane, s8v xd) {
+    f4v h[4];
+    s8v hb[2];
+    const s8v b1[1] = {xd};
+    mm_layer32<CD, 4, 1>(wl + FW_D1, lane, b1, h);
+    mm_pack64<CD, true, true>(h, hb);
+    f4v o[1];
+    mm_layer32<CD, 1, 2>(wl + FW_D2, lane, hb, o);
+    return o[0];
+}
+
+// class, color1 and color2 nets on the colour features: rgb rows 0..2 (before the sigmoid), class rows 3..3+nc-1
+template <int CD>
+__device__ __forceinline__ void field_colour_nets(const short *wl, int lane, s8v xc, f4v &rgb_out, f4v &cls_out) {
+    f4v h[4];
+    s8v hb[2];
+    // ---- class net: 32 -> 64 -> nc (rows 3..) -----------------------------------------
+    f4v cls[1];
+    {
+        const s8v b1[1] = {xc};
+        mm_layer32<CD, 4, 1>(wl + FW_K1, lane, b1, h);
+        mm_pack64<CD, true, true>(h, hb);
+        mm_layer32<CD, 1, 2>(wl + FW_K2, lane, hb, cls);
+    }
+    // ---- color1 net: 32 -> 64 -> 16 ----------------------------------------------------
+    f4v c1[1];
+    {
+        const s8v b1[1] = {xc};
+        mm_layer32<CD, 4, 1>(wl + FW_C1A, lane, b1, h);
+        mm_pack64<CD, true, true>(h, hb);
+        mm_layer32<CD, 1, 2>(wl + FW_C1B, lane, hb, c1);
+    }
+    // ---- color2 net: 16 -> 64 -> 64 -> 3, sigmoid --------------------------------------
+    f4v rgb[1];
+    {
+        const s4v c1b = mm_round4<CD, false>(c1[0]);
+        mm_layer16<CD, 4>(wl + FW_R1, lane, c1b, h);
+        mm_pack64<CD, true, true>(h, hb);
+        mm_layer32<CD, 4, 2>(wl + FW_R2, lane, hb, h);
+        mm_pack64<CD, true, true>(h, hb);
+        mm_layer32<CD, 1, 2>(wl + FW_R3, lane, hb, rgb);
+    }
+    rgb_out = rgb[0];
+    cls_out = cls[0];
+}
+
+// cat(rgb, classes): this lane's channels ch = 4g + e (style_nerf.py:141)
+__device__ __forceinline__ void field_cat(int g, f4v rgb, f4v cls, float (&v)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int ch = 4 * g + e;
+        v[e] = ch < 3 ? field_sigmoid(rgb[e]) : cls[e];
+    }
+}
 
 // XCD-aware logical block id: hardware deals blocks round-robin over the 8 XCDs, so blocks b and
 // b+8 share an L2.  Give each XCD one contiguous eighth of the tiles (neighbouring tiles =

@@ -1,0 +1,195 @@
+// Streaming inference render for gfx950: occupancy march -> hash encode -> density / colour / class MLPs on MFMA ->
+// inference composite, in ONE kernel per frame with no sample buffer (reference: renderer.py:237-293, up to max_steps
+// host iterations of march_rays / model / composite_rays; here: Renderer.render_test_fused).
+//
+// A wave owns 16 ray SLOTS.  Lane (s = lane & 15, g = lane >> 4) works on the current sample of slot s with the lane
+// layout of k_field_fwd (field.hip), so the encode output is the MFMA B fragment as it stands.  The ray's state is in
+// registers, replicated over the four g lanes of its slot: every lane of a slot runs the same serial march
+// (rm_probe.h: the positions are bit for bit those of every other march here), lane g accumulates channels 4g..4g+3 of
+// the pixel.  One iteration: every live slot advances to its next occupied sample, the wave shades the 16 samples, each
+// slot composites its own with the arithmetic of k_composite_infer (raymarch_infer.hip).  A ray that stopped (T <
+// T_thresh), reached `far` or took max_steps samples writes its pixel, and the slot takes the next ray of the wave's
+// contiguous piece of the work list (wave-uniform cursor + rank among the slots that ask): no atomics, no waiting on
+// another wave, nothing dropped.  Work is proportional to the samples that contribute: what lies behind the first
+// opaque surface is neither gathered nor shaded.
+#include "field_common.h"
+#include "rm_probe.h"
+
+struct RenderInferArgs {
+    FieldArgs f;                 // tables, params, bbox, density_scale, C_ch, level table (xyzs / sigmas / rgbs unused)
+    const float *rays_o, *rays_d;
+    const uint32_t *order;       // optional [N]: the ray handled k-th
+    const float *nears, *fars;
+    const uint8_t *grid;
+    uint32_t N, rays_per_wave;
+    float bound, dt_gamma;
+    uint32_t max_steps, C, H;
+    float T_thresh;
+    float *weights_sum, *depth, *image;
+    uint32_t *stats;             // optional {samples shaded, rays finished}
+};
+
+template <typename TT, int CD>
+__global__ void __launch_bounds__(256)
+k_render_infer(RenderInferArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    short *wl = reinterpret_cast<short *>(smem);
+    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + FW_TOTAL * 2);
+    field_build_fw<CD, false>(wl, a.f.params);
+    if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.f.lv[threadIdx.x];
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = lane & 15, g = lane >> 4;
+    const TT *tables = reinterpret_cast<const TT *>(a.f.tables);
+    const RmCfg c = rm_cfg(a.bound, a.dt_gamma, a.max_steps, a.C, a.H, a.grid);
+    // this wave's piece of the work list; neighbouring pieces (neighbouring pixels) go to one XCD's L2
+    const uint64_t w_first = ((uint64_t)field_logical_block() * 4 + wave) * a.rays_per_wave;
+    const uint32_t w_end = (uint32_t)min(w_first + a.rays_per_wave, (uint64_t)a.N);
+    uint32_t cursor = (uint32_t)min(w_first, (uint64_t)a.N);      // wave-uniform
+
+    // ---- slot state (the same in the four g lanes of a slot) ----
+    bool active = false, done = false;
+    uint32_t n = 0, steps = 0;
+    RmRay r = {};
+    float t = 0.f, last_t = 0.f, far = 0.f, t_phy = 0.f, ws = 0.f, d = 0.f;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t n_shaded = 0, n_finished = 0;                         // wave-uniform
+
+    for (;;) {
+        // ---- until every slot holds a sample or the list is used up: write finished rays, refill, march ----
+        bool got = false;
+        float x = 0.f, y = 0.f, z = 0.f, dt = 0.f, tt = 0.f;
+        for (;;) {
+            n_finished += (uint32_t)__popcll(__ballot(done) & 0xFFFFull);
+            if (done) {
+                if (g == 0) {
+                    a.weights_sum[n] = ws;
+                    a.depth[n] = d;
+                }
+                float *dst = a.image + (size_t)n * a.f.C_ch;
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    if ((uint32_t)(4 * g + e) < a.f.C_ch) dst[4 * g + e] = acc[e];
+                active = false;
+                done = false;
+            }
+            const uint32_t need = (uint32_t)(__ballot(!active) & 0xFFFFull);     // slots, from their g == 0 lanes
+            if (need != 0u && cursor < w_end) {
+                const uint32_t k = cursor + (uint32_t)__popc(need & ((1u << s) - 1u));
+                if (!active && k < w_end) {
+                    n = min(a.order ? a.order[k] : k, a.N - 1u);
+                    r = rm_load_ray(a.rays_o, a.rays_d, n);
+                    const float near = a.nears[n];
+                    far = a.fars[n];
+                    t = rm_start_t(c, near, 0.0f);
+                    last_t = t;              // raymarching.cu:530
+                    t_phy = near;            // :1163
+                    ws = 0.f; d = 0.f; steps = 0;
+                    acc[0] = acc[1] = acc[2] = acc[3] = 0.f;
+                    active = true;
+                }
+                cursor = min(cursor + (uint32_t)__popc(need), w_end);
+            }
+            if (active && !got) {
+                // the reference's serial loop (:484-498); a ray that misses the box has near == far == FLT_MAX
+                while (t < far && steps < a.max_steps) {
+                    if (rm_probe(r, c, t, x, y, z, dt, tt)) { got = true; break; }
+                    rm_skip(c, t, tt);
+                }
+                done = !got;
+            }
+            if (!(__ballot(done) != 0ull || (__ballot(!active) != 0ull && cursor < w_end))) break;
+        }
+        if (__ballot(active) == 0ull) break;       // nothing left in any slot (then the list is used up as well)
+        n_shaded += (uint32_t)__popcll(__ballot(got) & 0xFFFFull);
+
+        // ---- field of the 16 samples (k_field_fwd's body) ----
+        float u0 = 0.f, u1 = 0.f, u2 = 0.f;
+        if (got) {
+            u0 = field_unit(x, a.f.bmin[0], a.f.bsize[0]);
+            u1 = field_unit(y, a.f.bmin[1], a.f.bsize[1]);
+            u2 = field_unit(z, a.f.bmin[2], a.f.bsize[2]);
+        }
+        const bool live = got && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);
+        s8v xd, xc;
+        field_encode<TT, CD, false, true>(lds_lv, tables, u0, u1, u2, live, g, xd, xc, a.f.fast_levels);
+        const f4v o = field_density_net<CD>(wl, lane, xd);
+        f4v rgb, cls;
+        field_colour_nets<CD>(wl, lane, xc, rgb, cls);
+        float v[4];
+        field_cat(g, rgb, cls, v);
+        // sigma sits on the g == 0 lane of the slot
+        const float sigma = __shfl(expf(o[0]) * a.f.density_scale, s, 64);
+
+        // ---- composite this sample (k_composite_infer's arithmetic and order) ----
+        if (got) {
+            const float alpha = 1.0f - __expf(-sigma * dt);
+            const float T = 1 - ws;
+            const float weight = alpha * T;
+            ws += weight;
+            t += dt;                    // :551
+            t_phy += t - last_t;        // deltas[1] of the march
+            last_t = t;
+            steps++;
+            d += weight * t_phy;
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[e] += weight * v[e];
+            if (T < a.T_thresh) done = true;   // :1206: T before this sample, tested after accumulating it
+        }
+    }
+    if (a.stats != nullptr) {
+        if (lane == 0) atomicAdd(a.stats + 0, n_shaded);
+        if (lane == 1) atomicAdd(a.stats + 1, n_finished);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+template <typename TT, int CD>
+static int render_infer_launch(const RenderInferArgs &a, uint32_t nblocks, hipStream_t s) {
+    const size_t lds = FW_TOTAL * 2 + 16 * sizeof(NsrLevel);
+    hipLaunchKernelGGL((k_render_infer<TT, CD>), dim3(nblocks), dim3(256), lds, s, a);
+    return nsr_launch_status();
+}
+
+extern "C" {
+
+int nsr_render_rays_infer(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *rays_o,
+                          const float *rays_d, const uint32_t *order, uint32_t N, const float *nears, const float *fars,
+                          const uint8_t *grid, float bound, float dt_gamma, uint32_t max_steps, int is_ndc, uint32_t C, uint32_t H,
+                          float T_thresh, float *weights_sum, float *depth, float *image, uint32_t *stats, nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    if (is_ndc || C > 16) return NSR_ERR_UNSUPPORTED;
+    NSR_CHECK_PTR(desc); NSR_CHECK_PTR(tables); NSR_CHECK_PTR(mlp_params); NSR_CHECK_PTR(rays_o); NSR_CHECK_PTR(rays_d);
+    NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars); NSR_CHECK_PTR(grid); NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(depth);
+    NSR_CHECK_PTR(image);
+    if (max_steps == 0 || C == 0 || H == 0 || H > 1024 || !(bound > 0.0f)) return NSR_ERR_INVALID_ARG;
+    RenderInferArgs a;
+    uint32_t field_blocks;
+    const int st = field_fill_args(desc, a.f, N, field_blocks);      // num_classes > 13 -> NSR_ERR_UNSUPPORTED
+    if (st != NSR_OK) return st;
+    if ((uintptr_t)tables & 15u) return NSR_ERR_INVALID_ARG;
+    a.f.tables = tables; a.f.params = mlp_params; a.f.xyzs = nullptr; a.f.m_dev = nullptr; a.f.sigmas = nullptr;
+    a.f.rgbs = nullptr; a.f.feats = nullptr; a.f.perm = nullptr;
+    a.rays_o = rays_o; a.rays_d = rays_d; a.order = order; a.nears = nears; a.fars = fars; a.grid = grid;
+    a.N = N; a.bound = bound; a.dt_gamma = dt_gamma; a.max_steps = max_steps; a.C = C; a.H = H; a.T_thresh = T_thresh;
+    a.weights_sum = weights_sum; a.depth = depth; a.image = image; a.stats = stats;
+    // A wave's piece of the list: at least 64 rays (four turns of its 16 slots, so that the tail where slots run empty stays
+    // short against the piece), more when the frame has more than 2 048 workgroups' worth
+    constexpr uint32_t max_blocks = 2048;
+    uint32_t rpw = nsr_div_up(N, max_blocks * 4u);
+    if (rpw < 64u) rpw = 64u;
+    rpw = (rpw + 15u) & ~15u;
+    a.rays_per_wave = rpw;
+    const uint32_t nblocks = nsr_div_up(N, (uint64_t)rpw * 4u);
+    hipStream_t s = (hipStream_t)stream;
+    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_F16) return render_infer_launch<float, NSR_F16>(a, nblocks, s);
+    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_BF16) return render_infer_launch<float, NSR_BF16>(a, nblocks, s);
+    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_F16) return render_infer_launch<_Float16, NSR_F16>(a, nblocks, s);
+    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_BF16) return render_infer_launch<_Float16, NSR_BF16>(a, nblocks, s);
+    return NSR_ERR_UNSUPPORTED;
+}
+
+}   // extern "C"

@@ -10,11 +10,8 @@ from . import _lib as L
 from .common import Box2D, Intrinsics, RayBatch
 
 
-def pixel_ids(intr: Intrinsics, patch: Optional[Box2D] = None, precrop: float = 1., device=None):
-    """Row-major pixel ids (y * W + x) of the full frame / centre crop / patch, as the reference
-    slices x_coords / y_coords (nerf_lib.py:106-113).  Returns (ids int32 [w*h], w, h, dx, dy)."""
-    assert 0. <= precrop <= 1.
-    assert precrop >= 1. or patch is None, 'Using both precrop and patch is not supported'
+def pixel_window(intr: Intrinsics, patch: Optional[Box2D] = None, precrop: float = 1.):
+    """(w, h, dx, dy) of the full frame / centre crop / patch (nerf_lib.py:106-113)."""
     W, H = intr.size()
     w, h, dx, dy = W, H, 0, 0
     if precrop < 1.:
@@ -22,6 +19,16 @@ def pixel_ids(intr: Intrinsics, patch: Optional[Box2D] = None, precrop: float = 
         dx, dy = (W - w) // 2, (H - h) // 2
     if patch is not None:
         dx, dy, w, h = patch.x, patch.y, min(patch.w, W - patch.x), min(patch.h, H - patch.y)
+    return w, h, dx, dy
+
+
+def pixel_ids(intr: Intrinsics, patch: Optional[Box2D] = None, precrop: float = 1., device=None):
+    """Row-major pixel ids (y * W + x) of the full frame / centre crop / patch, as the reference
+    slices x_coords / y_coords (nerf_lib.py:106-113).  Returns (ids int32 [w*h], w, h, dx, dy)."""
+    assert 0. <= precrop <= 1.
+    assert precrop >= 1. or patch is None, 'Using both precrop and patch is not supported'
+    W, H = intr.size()
+    w, h, dx, dy = pixel_window(intr, patch, precrop)
     ys = torch.arange(dy, dy + h, device=device, dtype=torch.int32)
     xs = torch.arange(dx, dx + w, device=device, dtype=torch.int32)
     ids = (ys[:, None] * W + xs[None, :]).reshape(-1)

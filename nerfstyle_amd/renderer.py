@@ -18,7 +18,7 @@ import torch
 from . import raymarching
 from .common import Box2D, Intrinsics, RayBatch
 from .config import RendererConfig
-from .rays import generate_rays
+from .rays import generate_rays, pixel_window, tile_order
 from .style_nerf import StyleTCNerf
 
 STEP_CTR_SIZE = 16
@@ -47,6 +47,11 @@ class Renderer(torch.nn.Module):
         self.sort_min_rays = 90000       # any batch of at least this many rays ...
         self.sort_min_dense_rays = 16384  # ... or a DENSE pixel set (full frame / patch / crop: neighbouring pixels) of this many
         self._pinned_bitfield = None
+        # Inference through the streaming kernel (render_test_fused: march, field and composite in one launch, no sample
+        # buffer).  Opt-in; `reference_inference_loop` still wins.
+        self.fused_inference = False
+        self._infer_stats = None
+        self._tile_orders = {}
         self.aabb = torch.tensor([-bound, -bound, -bound, bound, bound, bound], dtype=torch.float32)
         self.cascade = 1 + ceil(log2(bound))
         grid_size = self.cfg.grid_size
@@ -276,6 +281,8 @@ class Renderer(torch.nn.Module):
         (render_test_loop), which the tests hold equal to this path."""
         if getattr(self, 'reference_inference_loop', False):
             return self.render_test_loop(rays, **kwargs)
+        if self.fused_inference:
+            return self.render_test_fused(rays, **kwargs)
         from . import _lib as L
         nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
         N = rays.origins.shape[0]
@@ -303,6 +310,49 @@ class Renderer(torch.nn.Module):
         image = image[:, :3] + (1 - weights_sum).unsqueeze(-1)
         depth = torch.clamp(depth - nears, min=0) / (fars - nears)
         return image, depth, classes
+
+    @torch.no_grad()
+    def render_test_fused(self, rays: RayBatch, dense_shape=None, **kwargs):
+        """renderer.py:237-293 as ONE launch (nsr_render_rays_infer): the march, the fused field and render_test's composite
+        in one kernel that keeps the ray state in registers.  Same samples, same order and same arithmetic as render_test,
+        but nothing here is sized by samples -- no capacity, so no dropped ray and no overflow fallback, no host read -- and
+        a ray that stopped early costs nothing further.  dense_shape = (w, h): the rays are the row-major pixels of a
+        w x h window, walked in 8 x 8 tiles so that the 16 rays a wave holds are neighbours; anything else in batch order."""
+        import ctypes
+        from . import _lib as L
+        nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
+        if self.cfg.use_ndc:
+            raise NotImplementedError('render_test_fused: NDC scenes march through render_test / render_test_loop')
+        N = rays.origins.shape[0]
+        dev = rays.origins.device
+        C = self.raymarch_channels
+        assert C == self.model.out_channels, 'the fused kernel composites the 3 + num_classes channels of the model'
+        order = None
+        if dense_shape is not None and dense_shape[0] * dense_shape[1] == N:
+            key = (int(dense_shape[0]), int(dense_shape[1]), str(dev))
+            order = self._tile_orders.get(key)
+            if order is None:
+                order = self._tile_orders[key] = tile_order(key[0], key[1]).to(torch.int32).to(dev)
+        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        image = torch.empty(N, C, dtype=torch.float32, device=dev)
+        stats = torch.zeros(2, dtype=torch.int32, device=dev)
+        desc = self.model._desc(self.cfg.density_scale)
+        L.check(L.lib().nsr_render_rays_infer(
+            ctypes.byref(desc), L.p(self.model._gather_tables()), L.p(self.model._mlp_flat()), L.p(rays.origins), L.p(rays.dirs),
+            L.p(order), N, L.p(nears), L.p(fars), L.p(self.march_bitfield), float(self.bound), 0., self.cfg.max_steps, 0,
+            self.cascade, self.cfg.grid_size, float(self.cfg.t_thresh), L.p(weights_sum), L.p(depth), L.p(image), L.p(stats),
+            L.stream()), 'render_rays_infer')
+        self._infer_stats = stats
+        classes = image[:, 3:]
+        image = image[:, :3] + (1 - weights_sum).unsqueeze(-1)
+        depth = torch.clamp(depth - nears, min=0) / (fars - nears)
+        return image, depth, classes
+
+    def last_infer_stats(self) -> Optional[torch.Tensor]:
+        """Device tensor int32 [2] of the last render_test_fused call -- (samples shaded, rays finished) -- without a
+        synchronisation; None before the first call."""
+        return self._infer_stats
 
     @torch.no_grad()
     def render_test_loop(self, rays: RayBatch, **kwargs):
@@ -408,7 +458,10 @@ class Renderer(torch.nn.Module):
         # a full frame, a patch or a centre crop is a dense pixel set: neighbouring rays share hash-table rows
         if dense is None:
             dense = pix_subset is None and num_rays is None
-        output['rgb_map'], output['trans_map'], output['classes'] = render_fn(rays, dense=dense)
+        extra = {}
+        if not training and self.fused_inference and dense and pix_subset is None and num_rays is None:
+            extra['dense_shape'] = pixel_window(self.intr, patch, precrop_frac)[:2]
+        output['rgb_map'], output['trans_map'], output['classes'] = render_fn(rays, dense=dense, **extra)
         return output
 
 
