@@ -90,6 +90,9 @@ __device__ __forceinline__ void cp_load_row(const float *__restrict__ rgbs, size
 template <int CT>
 __global__ void __launch_bounds__(CP_BLOCK)
 k_comp_fwd(CompArgs a) {
+    // no contraction: which products the compiler fuses into an fma differs between the instantiations, and the runtime-C
+    // kernel must give the bits of the compile-time-C one (a colour pointer's alignment must not change a result)
+#pragma clang fp contract(off)
     constexpr int NC = CT ? CT : CP_MAXC;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nwaves = gridDim.x * (CP_BLOCK / 64), gw = blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6);
@@ -153,6 +156,7 @@ k_comp_fwd(CompArgs a) {
 template <int CT>
 __global__ void __launch_bounds__(CP_BLOCK)
 k_comp_bwd(CompArgs a) {
+#pragma clang fp contract(off)                  // see k_comp_fwd
     constexpr int NC = CT ? CT : CP_MAXC;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nwaves = gridDim.x * (CP_BLOCK / 64), gw = blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6);

@@ -66,7 +66,11 @@ k_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *__restrict__ rays
     float t = rm_start_t(c, t_alive, noises ? noises[n] : 0.0f);   // :1053
     uint32_t step = 0;
     float last_t = t;
-    float last_z = rm_clamp(r.oz + t * r.dz, -bound, bound);
+    float last_z;
+    {
+#pragma clang fp contract(off)
+        last_z = rm_clamp(r.oz + t * r.dz, -bound, bound);     // (contracted to an fma it is not the oracle's float)
+    }
     float x, y, z, dt, tt;
     while (t < far && step < n_step) {
         if (rm_probe(r, c, t, x, y, z, dt, tt)) {

@@ -145,8 +145,9 @@ def march_rays_train(rays_o, rays_d, bound, bitfield, C, H, nears, fars, max_ste
     return xyzs[:m], dirs[:m], deltas[:m], rays, counter
 
 
-def composite_rays_train_forward(sigmas, rgbs, deltas, rays, T_thresh=1e-4):
-    """raymarching.py:291-325 / raymarching.cu:806-890"""
+def composite_rays_train_forward(sigmas, rgbs, deltas, rays, T_thresh=1e-4, is_ndc=False):
+    """raymarching.py:291-325 / raymarching.cu:806-890.  is_ndc reads alpha's step from deltas[:, 2] and
+    the depth's from deltas[:, 3] (:848, :854)."""
     s, ps = _f(sigmas)
     r, pr = _f(rgbs)
     dl, pdl = _f(deltas)
@@ -155,15 +156,15 @@ def composite_rays_train_forward(sigmas, rgbs, deltas, rays, T_thresh=1e-4):
     ws = np.empty(N, np.float32)
     depth = np.empty(N, np.float32)
     image = np.empty((N, C), np.float32)
-    lib().ora_composite_rays_train_forward(ps, pr, pdl, pry, U(M), U(N), U(C), F(T_thresh), I(0),
+    lib().ora_composite_rays_train_forward(ps, pr, pdl, pry, U(M), U(N), U(C), F(T_thresh), I(int(bool(is_ndc))),
                                            ws.ctypes.data_as(c_f), depth.ctypes.data_as(c_f),
                                            image.ctypes.data_as(c_f))
     return ws, depth, image
 
 
 def composite_rays_train_backward(grad_ws, grad_image, sigmas, rgbs, deltas, rays, ws, image,
-                                  T_thresh=1e-4):
-    """raymarching.py:327-347 / raymarching.cu:904-997"""
+                                  T_thresh=1e-4, is_ndc=False):
+    """raymarching.py:327-347 / raymarching.cu:904-997.  is_ndc: the step is deltas[:, 2] (:951, :972)."""
     gws, pgws = _f(grad_ws)
     gim, pgim = _f(grad_image)
     s, ps = _f(sigmas)
@@ -176,15 +177,16 @@ def composite_rays_train_backward(grad_ws, grad_image, sigmas, rgbs, deltas, ray
     gs = np.zeros(M, np.float32)
     gr = np.zeros((M, C), np.float32)
     buf = np.zeros((N, C), np.float32)
-    lib().ora_composite_rays_train_backward(pgws, pgim, ps, pr, pdl, pry, I(0), pw, pim, U(M), U(N), U(C),
-                                            F(T_thresh), gs.ctypes.data_as(c_f), gr.ctypes.data_as(c_f),
+    lib().ora_composite_rays_train_backward(pgws, pgim, ps, pr, pdl, pry, I(int(bool(is_ndc))), pw, pim, U(M), U(N),
+                                            U(C), F(T_thresh), gs.ctypes.data_as(c_f), gr.ctypes.data_as(c_f),
                                             buf.ctypes.data_as(c_f))
     return gs, gr
 
 
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, bitfield, C, H, nears, fars,
-               align=-1, max_steps=1024, dt_gamma=0.0):
-    """raymarching.py:357-424 / raymarching.cu:1004-1130"""
+               align=-1, max_steps=1024, dt_gamma=0.0, is_ndc=False, z_hats=None):
+    """raymarching.py:357-424 / raymarching.cu:1004-1130.  With is_ndc, rays_t is [N, 2] (the march reads column 0)
+    and deltas[:, 2:] are filled from the per-ray z_hats (:1094)."""
     ra, pra = _i(rays_alive)
     rt, prt = _f(rays_t)
     o, po = _f(rays_o)
@@ -199,25 +201,29 @@ def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, bitfi
     dirs = np.zeros((M, 3), np.float32)
     deltas = np.zeros((M, 4), np.float32)
     noises = np.zeros(n_alive, np.float32)
-    lib().ora_march_rays(U(n_alive), U(n_step), pra, prt, po, pd, None, F(bound), F(dt_gamma), U(max_steps),
-                         I(0), U(C), U(H), pg, pne, pfa, xyzs.ctypes.data_as(c_f),
+    assert not is_ndc or (z_hats is not None and rt.ndim == 2 and rt.shape[1] == 2)
+    zh, pzh = _f(z_hats) if is_ndc else (None, None)
+    lib().ora_march_rays(U(n_alive), U(n_step), pra, prt, po, pd, pzh, F(bound), F(dt_gamma), U(max_steps),
+                         I(int(bool(is_ndc))), U(C), U(H), pg, pne, pfa, xyzs.ctypes.data_as(c_f),
                          dirs.ctypes.data_as(c_f), deltas.ctypes.data_as(c_f), noises.ctypes.data_as(c_f))
     return xyzs, dirs, deltas
 
 
 def composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image,
-                   T_thresh=1e-2):
+                   T_thresh=1e-2, is_ndc=False):
     """raymarching.py:430-459 / raymarching.cu:1133-1240.  In-place on rays_alive, rays_t,
-    weights_sum, depth, image (must be C-contiguous arrays of the right dtype)."""
+    weights_sum, depth, image (must be C-contiguous arrays of the right dtype).  With is_ndc, rays_t is
+    [N, 2] (t of the march, physical t) and alpha / depth step by deltas[:, 2] / deltas[:, 3]."""
     assert rays_alive.dtype == np.int32 and rays_alive.flags.c_contiguous
     for a in (rays_t, weights_sum, depth, image):
         assert a.dtype == np.float32 and a.flags.c_contiguous
+    assert not is_ndc or (rays_t.ndim == 2 and rays_t.shape[1] == 2)
     s, ps = _f(sigmas)
     r, pr = _f(rgbs)
     dl, pdl = _f(deltas)
     C = r.shape[-1]
     lib().ora_composite_rays(U(n_alive), U(n_step), F(T_thresh), rays_alive.ctypes.data_as(c_i),
-                             rays_t.ctypes.data_as(c_f), ps, pr, pdl, U(C), I(0),
+                             rays_t.ctypes.data_as(c_f), ps, pr, pdl, U(C), I(int(bool(is_ndc))),
                              weights_sum.ctypes.data_as(c_f), depth.ctypes.data_as(c_f),
                              image.ctypes.data_as(c_f))
 

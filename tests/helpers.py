@@ -33,3 +33,82 @@ def rel_l2(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+# ---- deterministic edge rays for the training composite ----------------------------------------------
+EDGE_T_THRESH = 1e-4
+EDGE_LENGTHS = (1, 2, 63, 64, 65, 127, 128, 129, 200)
+EDGE_STOPS = (0, 13, 14, 62, 63, 64, 127, 128)      # + the ray's last sample + "never"
+EDGE_COL2, EDGE_COL3 = 1.7, 0.6                     # deltas[:, 2] = EDGE_COL2 * [:, 0], [:, 3] = EDGE_COL3 * [:, 1]
+
+
+def edge_rays(C, is_ndc=False, seed=0, replicas=4):
+    """Rays for the training composite whose early stop lands on a chosen sample, NumPy only (the CPU and the GPU
+    tests call this, so both judge the same arrays).  Returns (sigmas [M], rgbs [M, C], deltas [M, 4], rays [N, 3],
+    M, intended_stop [N]); deltas, rays and rgbs do not depend on is_ndc, sigmas do (and only rgbs depend on C).
+
+    Per replica, one ray per length in EDGE_LENGTHS and per stop sample in EDGE_STOPS + (length - 1) that the length
+    reaches, plus one ray per length that never stops.  A stop on sample S is built from the product
+    sigma * delta of the column the mode reads (0, or 2 with is_ndc), set in fp32:
+      * S >= 13: S - 13 samples of sigma = 0 (alpha exactly 0, T exactly 1), then sigma * delta = ln 2 from there to
+        the ray's end.  T is 2^-13 = 1.22e-4 after 13 of them and 2^-14 = 6.1e-5 after the 14th, which is sample S;
+      * S < 13: S samples of sigma = 0, sigma * delta = 20 on sample S (T = 2e-9), ln 2 behind it;
+      * never: sigma * delta = 0.02 on every sample (T >= e^-4 = 0.018 at 200 samples).
+    So with T_thresh = EDGE_T_THRESH every T of every ray, after any sample, is outside [0.9, 1.1] * T_thresh: no
+    association of the products (serial, or a wave scan) and no exp implementation can move a stop, and a comparison
+    of two implementations on these rays is free of threshold flips.  The stopping sample is the first one that gets
+    no gradient (it is accumulated forward); intended_stop holds its index within the ray, `steps` for a ray that
+    never stops, 0 for the ray with no samples and for the dropped one.
+
+    All four delta columns are positive and differ (column 0 uniform in [0.002, 0.006), column 1 = 1.3 x column 0,
+    columns 2 and 3 scaled by EDGE_COL2 / EDGE_COL3), so the other mode's column gives alpha 0.33 or 0.69 in place
+    of 0.5 and another stop.  Colours are uniform in [0, 1).  The rays are shuffled, `index` is a permutation, some
+    rays are followed by 1-5 slots that no ray owns, one ray has steps == 0, the last ray (one opaque sample) ends at
+    offset + steps == M and is dropped by the reference's rule (raymarching.cu:830), the ray before it ends at M - 1
+    and is kept."""
+    rng = np.random.default_rng(seed)
+    specs = []                                          # (length, stop | None)
+    for _ in range(replicas):
+        for L in EDGE_LENGTHS:
+            for S in sorted(set(s for s in EDGE_STOPS + (L - 1,) if s < L)):
+                specs.append((L, S))
+            specs.append((L, None))
+    specs = [specs[i] for i in rng.permutation(len(specs))]
+    specs.insert(len(specs) // 2, (0, None))            # the ray without samples
+    specs.append((1, 0))                                # the dropped ray
+    N = len(specs)
+    prods, offsets, stops, off = [], [], [], 0
+    for n, (L, S) in enumerate(specs):
+        offsets.append(off)
+        p = np.full(L, 0.02 if S is None else np.log(2.0))
+        if S is not None:
+            p[:S - 13 if S >= 13 else S] = 0.0
+            if S < 13:
+                p[S] = 20.0
+        prods.append(p)
+        stops.append(L if S is None else S)
+        off += L
+        if n % 3 == 1 and n < N - 2:                    # slots owned by no ray (never in front of the dropped ray)
+            pad = 1 + n % 5
+            prods.append(np.full(pad, 5.0))
+            off += pad
+    stops[-1] = 0                                       # dropped: no sample of it gets a gradient
+    M = off
+    prod = np.concatenate(prods)
+    deltas = np.empty((M, 4), np.float32)
+    deltas[:, 0] = rng.uniform(0.002, 0.006, M)
+    deltas[:, 1] = deltas[:, 0] * np.float32(1.3)
+    deltas[:, 2] = deltas[:, 0] * np.float32(EDGE_COL2)
+    deltas[:, 3] = deltas[:, 1] * np.float32(EDGE_COL3)
+    sigmas = (prod / deltas[:, 2 if is_ndc else 0].astype(np.float64)).astype(np.float32)
+    rays = np.stack([rng.permutation(N), offsets, [L for L, _ in specs]], 1).astype(np.int32)
+    rgbs = rng.random((M, C)).astype(np.float32)
+    return sigmas, rgbs, deltas, rays, M, np.asarray(stops, np.int64)
+
+
+def owned_slots(rays, M):
+    """bool [M]: sample slots inside some ray's [offset, offset + steps)"""
+    owned = np.zeros(M, bool)
+    for _, o, c in rays:
+        owned[o:o + c] = True
+    return owned

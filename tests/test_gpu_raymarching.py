@@ -150,6 +150,40 @@ def test_composite_train_forward_backward(O, dev, C):
     assert np.array_equal(gs == 0, gs_o == 0)
 
 
+@pytest.mark.parametrize('C', [8, 3, 11])
+def test_composite_train_forward_backward_ndc(O, dev, C):
+    """The same scene with is_ndc: alpha steps by deltas[:, 2] and the depth by deltas[:, 3] (raymarching.cu:848, :854,
+    :951, :972; the kernels load them as a float2 at deltas + 4 p + 2).  Those columns are the plain ones times 1.7 and
+    0.6, so a kernel on the wrong column lands on the is_ndc=False result, from which the right one is required to be
+    more than ten tolerances away."""
+    from nerfstyle_amd import raymarching as R
+    sig, rgb, deltas, rays, near, far = _composite_inputs(O, 3000, C, seed=C)
+    deltas = deltas.copy()
+    deltas[:, 2] = deltas[:, 0] * np.float32(1.7)
+    deltas[:, 3] = deltas[:, 1] * np.float32(0.6)
+    ws_o, d_o, im_o = O.composite_rays_train_forward(sig, rgb, deltas, rays, 1e-4, is_ndc=True)
+    s_t, r_t = T(sig, dev).requires_grad_(), T(rgb, dev).requires_grad_()
+    ws, depth, image = R.composite_rays_train(s_t, r_t, T(deltas, dev), T(rays, dev), 1e-4, True)
+    ws_g, d_g, im_g = ws.detach().cpu().numpy(), depth.detach().cpu().numpy(), image.detach().cpu().numpy()
+    assert np.abs(ws_g - ws_o).max() < 2e-5
+    assert np.abs(im_g - im_o).max() < 2e-5
+    assert np.abs(d_g - d_o).max() < 2e-4
+    rng = np.random.default_rng(1)
+    gws = rng.standard_normal(len(ws_o)).astype(np.float32)
+    gim = rng.standard_normal(im_o.shape).astype(np.float32)
+    (ws * T(gws, dev)).sum().add((image * T(gim, dev)).sum()).backward()
+    gs_o, gr_o = O.composite_rays_train_backward(gws, gim, sig, rgb, deltas, rays, ws_o, im_o, 1e-4, is_ndc=True)
+    gs, gr = s_t.grad.cpu().numpy(), r_t.grad.cpu().numpy()
+    assert np.abs(gr - gr_o).max() < 5e-5
+    assert np.abs(gs - gs_o).max() < 1e-4 * max(1.0, np.abs(gs_o).max())
+    assert np.array_equal(gs == 0, gs_o == 0)
+    # not the other mode's numbers
+    ws_p, d_p, im_p = O.composite_rays_train_forward(sig, rgb, deltas, rays, 1e-4)
+    gs_p, gr_p = O.composite_rays_train_backward(gws, gim, sig, rgb, deltas, rays, ws_p, im_p, 1e-4)
+    assert np.abs(ws_g - ws_p).max() > 2e-4 and np.abs(im_g - im_p).max() > 2e-4 and np.abs(d_g - d_p).max() > 2e-3
+    assert np.abs(gr - gr_p).max() > 5e-4 and np.abs(gs - gs_p).max() > 1e-3 * max(1.0, np.abs(gs_p).max())
+
+
 def test_composite_train_kernel_vs_reference_integrate_points_golden(O, dev, golden):
     """The HIP composite itself (nsr_composite_rays_train_forward, through the C ABI) against output of the REFERENCE:
     nerf_lib.integrate_points run on seeded [N, K = 64] inputs by tests/golden/make_goldens.py (ip_* fixtures).  With no early
@@ -309,6 +343,74 @@ def test_inference_march_composite_loop(O, dev):
         step += n_step
         it += 1
     assert it > 3
+
+
+@pytest.mark.parametrize('seed,dt_gamma', [(22, 0.), (29, 1. / 256)])
+def test_inference_march_composite_loop_ndc(O, dev, seed, dt_gamma):
+    """The same loop with is_ndc: rays_t is [N, 2] (t of the march, physical t), the march fills deltas[:, 2:] from the
+    sample's, the next and the previous z over the ray's z_hat (raymarching.cu:1094), bit for bit like the oracle in all
+    four columns -- the first sample's column 3 takes the z at the ray's incoming t, which only this path computes.
+    The composite steps alpha by column 2 and the physical t by column 3.  Raw NDC deltas change sign around z = 1, which
+    gives alpha outside [0, 1] and unbounded weights: the composite of both sides is fed one sanitised copy of the
+    oracle's deltas (|column 3|, |column 2| capped at 1).
+    The seeds are chosen on the CPU: the oracle's deltas are finite in every iteration (z == 1 makes a column infinite and
+    inf - inf a NaN, which array_equal rejects whatever the kernel does), and its alive sets do not change when T_thresh
+    moves by +-0.3 %, so that a last-bit difference in weights_sum (T = 1 - weights_sum, :1206) flips no flag."""
+    from nerfstyle_amd import raymarching as R
+    grid, bits = small_scene()
+    N, C = 1500, 8
+    ro, rd = room_rays(O, N, seed=seed)
+    near, far = O.near_far_from_aabb(ro, rd, AABB, 0.2)
+    z_hats = np.random.default_rng(seed).uniform(0.5, 2.0, N).astype(np.float32)
+
+    def fake_field(xyz):      # deterministic stand-in for the model, identical on both sides
+        s = (np.abs(np.sin(xyz.sum(1) * 3.1)) * 60).astype(np.float32)
+        c = np.stack([np.abs(np.cos(xyz[:, i % 3] * (i + 1))) for i in range(C)], 1).astype(np.float32)
+        return s, c
+
+    alive_o = np.arange(N, dtype=np.int32)
+    rt_o = np.stack([near, near], 1)
+    ws_o = np.zeros(N, np.float32); d_o = np.zeros(N, np.float32); im_o = np.zeros((N, C), np.float32)
+    alive = T(alive_o, dev); rt = T(rt_o, dev)
+    ws = torch.zeros(N, device=dev); dp = torch.zeros(N, device=dev); im = torch.zeros(N, C, device=dev)
+    bits_t, ro_t, rd_t, near_t, far_t, zh_t = T(bits, dev), T(ro, dev), T(rd, dev), T(near, dev), T(far, dev), T(z_hats, dev)
+    step, it, seen = 0, 0, np.zeros(2)
+    while step < 1024 and len(alive_o) > 0 and it < 40:
+        n_alive = len(alive_o)
+        n_step = max(min(N // n_alive, 8), 1)
+        xo, _, dlo = O.march_rays(n_alive, n_step, alive_o, rt_o, ro, rd, 2.0, bits, 2, 128, near, far, 128, 1024, dt_gamma,
+                                  is_ndc=True, z_hats=z_hats)
+        assert np.isfinite(dlo).all()
+        seen += np.abs(dlo[:, 2:]).max(0)
+        x, _, dl = R.march_rays(n_alive, n_step, alive, rt, ro_t, rd_t, zh_t, 2.0, bits_t, 2, 128, near_t, far_t, 128, False,
+                                dt_gamma, 1024, True)
+        assert np.array_equal(x.cpu().numpy(), xo)
+        dl = dl.cpu().numpy()
+        assert dl.shape == dlo.shape
+        for col in range(4):
+            assert np.array_equal(dl[:, col], dlo[:, col]), \
+                'iteration {}: deltas[:, {}] differs from the oracle in {} of {} emitted samples, {} of them first samples'.format(
+                    it, col, int((dl[:, col] != dlo[:, col]).sum()), int((dlo[:, 0] != 0).sum()),
+                    int((dl[::n_step, col] != dlo[::n_step, col]).sum()))
+        s, c = fake_field(xo)
+        dls = dlo.copy()
+        dls[:, 2] = np.minimum(np.abs(dls[:, 2]), 1)
+        dls[:, 3] = np.abs(dls[:, 3])
+        O.composite_rays(n_alive, n_step, alive_o, rt_o, s, c, dls, ws_o, d_o, im_o, 1e-4, is_ndc=True)
+        R.composite_rays(n_alive, n_step, alive, rt, T(s, dev), T(c, dev), T(dls, dev), True, ws, dp, im, 1e-4)
+        assert np.array_equal(alive.cpu().numpy()[:n_alive], alive_o)
+        assert np.abs(ws.cpu().numpy() - ws_o).max() < 2e-5 and np.abs(im.cpu().numpy() - im_o).max() < 2e-5
+        assert np.abs(dp.cpu().numpy() - d_o).max() < 2e-4
+        rt_g = rt.cpu().numpy()
+        assert np.allclose(rt_g[:, 0], rt_o[:, 0], atol=1e-6) and np.allclose(rt_g[:, 1], rt_o[:, 1], atol=1e-6)
+        out, n_out = R.compact_alive(alive, n_alive)
+        alive_o = alive_o[alive_o >= 0]
+        assert int(n_out.item()) == len(alive_o)
+        assert np.array_equal(out.cpu().numpy()[:len(alive_o)], alive_o)
+        alive = out[:len(alive_o)].contiguous()
+        step += n_step
+        it += 1
+    assert it > 3 and seen[0] > 0 and seen[1] > 0
 
 
 def test_generate_rays_kernel_vs_reference_golden(O, dev, golden):

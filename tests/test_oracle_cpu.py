@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import rel_l2, room_cameras, room_rays, small_scene
+from helpers import (EDGE_LENGTHS, EDGE_STOPS, EDGE_T_THRESH, edge_rays, owned_slots, rel_l2, room_cameras, room_rays,
+                     small_scene)
 
 
 # ---- goldens from the reference's importable Python ----------------------------------------------
@@ -184,6 +185,153 @@ def test_inference_composite_matches_train_composite(O):
     O.composite_rays(N, K, alive, rays_t, sig, rgb, deltas[:N * K], ws, depth, image, T_thresh=0.0)
     assert np.allclose(ws, ws_t, atol=1e-5) and np.allclose(image, im_t, atol=1e-5) and np.allclose(depth, d_t, atol=1e-5)
     assert np.all(alive >= 0) and np.allclose(rays_t[:, 0], K * 0.0034, atol=1e-5)
+
+
+# ---- the edge rays of tests/helpers.py and the oracle's NDC paths ----------------------------------------
+def _edge_T64(sig, deltas, rays, is_ndc):
+    """per ray: transmittance after every sample, recomputed in float64 from the float32 inputs"""
+    col = 2 if is_ndc else 0
+    out = []
+    for _, o, c in rays:
+        a = 1.0 - np.exp(-sig[o:o + c].astype(np.float64) * deltas[o:o + c, col].astype(np.float64))
+        out.append(np.cumprod(1.0 - a))
+    return out
+
+
+def test_edge_rays_layout():
+    sig, rgb, deltas, rays, M, stop = edge_rays(3)
+    N = len(rays)
+    assert 100 < N < 1000 and M < 65536 and sig.shape == (M,) and rgb.shape == (M, 3) and deltas.shape == (M, 4)
+    assert (deltas > 0).all() and (rgb >= 0).all() and (rgb < 1).all()
+    assert sorted(rays[:, 0]) == list(range(N))
+    for col, base, k in ((1, 0, 1.3), (2, 0, 1.7), (3, 1, 0.6)):                 # the columns differ in value
+        assert np.allclose(deltas[:, col], deltas[:, base] * k, rtol=1e-6) and (deltas[:, col] != deltas[:, base]).all()
+    # every length with every stop it reaches, its last sample, and no stop at all
+    have = set((int(c), int(s)) for (_, _, c), s in zip(rays[:-1], stop[:-1]))
+    for L in EDGE_LENGTHS:
+        for S in EDGE_STOPS + (L - 1,):
+            assert S >= L or (L, S) in have, (L, S)
+        assert (L, L) in have
+    assert (rays[:, 2] == 0).sum() == 1
+    # rays do not overlap, some slots belong to no ray, the last ray ends at M (dropped), the one before it at M - 1 (kept)
+    ends = rays[:, 1] + rays[:, 2]
+    assert (rays[1:, 1] >= ends[:-1]).all() and 0 < (~owned_slots(rays, M)).sum() < M // 10
+    assert ends[-1] == M and ends[-2] == M - 1 and rays[-2, 2] > 0
+    # the inputs of the two modes share everything but sigma
+    sig_n, rgb_n, deltas_n, rays_n, M_n, stop_n = edge_rays(3, is_ndc=True)
+    assert np.array_equal(rgb, rgb_n) and np.array_equal(deltas, deltas_n) and np.array_equal(rays, rays_n)
+    assert M == M_n and np.array_equal(stop, stop_n) and not np.array_equal(sig, sig_n)
+
+
+@pytest.mark.parametrize('is_ndc', [False, True])
+def test_edge_rays_threshold_margin(is_ndc):
+    """T / T_thresh is outside [0.9, 1.1] after every sample of every ray: the condition under which two
+    implementations cannot disagree on a stop."""
+    sig, _, deltas, rays, M, stop = edge_rays(3, is_ndc)
+    for (_, o, c), s, T in zip(rays, stop, _edge_T64(sig, deltas, rays, is_ndc)):
+        ratio = T / EDGE_T_THRESH
+        assert ((ratio < 0.9) | (ratio > 1.1)).all()
+        if o + c < M and c > 0:                           # ... and the first T under the threshold is the intended stop's
+            below = np.nonzero(ratio < 1)[0]
+            assert (below[0] if len(below) else c) == s
+
+
+@pytest.mark.parametrize('is_ndc', [False, True])
+def test_edge_rays_oracle_stops_where_intended(O, is_ndc):
+    C = 3
+    sig, rgb, deltas, rays, M, stop = edge_rays(C, is_ndc)
+    N = len(rays)
+    ws, depth, image = O.composite_rays_train_forward(sig, rgb, deltas, rays, EDGE_T_THRESH, is_ndc=is_ndc)
+    rng = np.random.default_rng(2)
+    gws, gim = rng.standard_normal(N).astype(np.float32), rng.standard_normal((N, C)).astype(np.float32)
+    gs, gr = O.composite_rays_train_backward(gws, gim, sig, rgb, deltas, rays, ws, image, EDGE_T_THRESH, is_ndc=is_ndc)
+    ca, ct = (2, 3) if is_ndc else (0, 1)
+    for (idx, o, c), s, T in zip(rays, stop, _edge_T64(sig, deltas, rays, is_ndc)):
+        if c == 0 or o + c >= M:
+            continue
+        # backward: the first sample without a gradient is the stopping sample, everything behind it is zero too
+        zero = np.nonzero(gs[o:o + c] == 0)[0]
+        assert (zero[0] if len(zero) else c) == s, (c, s)
+        assert (gs[o + s:o + c] == 0).all() and (gr[o + s:o + c] == 0).all() and (gs[o:o + s] != 0).all()
+        # forward: the sum runs up to and including the stopping sample (float64 recomputation; one sample more or
+        # less moves weights_sum by 2^-15 / 2^-14 on the rays that stop on a run of alpha = 0.5)
+        k = min(s + 1, c)
+        w = (np.concatenate([[1.0], T[:-1]]) - T)[:k]
+        assert abs(ws[idx] - w.sum()) < 1e-5
+        assert np.abs(image[idx] - (w[:, None] * rgb[o:o + k]).sum(0)).max() < 1e-5
+        assert abs(depth[idx] - (w * np.cumsum(deltas[o:o + k, ct].astype(np.float64))).sum()) < 1e-5
+    # the ray that ends at M is dropped, in the buffer or not; the one before it is kept
+    idx, o, c = rays[-1]
+    assert ws[idx] == 0 and depth[idx] == 0 and (image[idx] == 0).all() and gs[o] == 0 and (gr[o] == 0).all()
+    idx, o, c = rays[-2]
+    assert ws[idx] > 0 and depth[idx] > 0 and (image[idx] > 0).all() and gs[o] != 0
+    idx = rays[rays[:, 2] == 0][0, 0]
+    assert ws[idx] == 0 and depth[idx] == 0 and (image[idx] == 0).all()
+
+
+def test_oracle_ndc_wiring_composite(O):
+    """is_ndc reads columns (2, 3) where the default reads (0, 1): the same values there give the same bits, other
+    values other results -- training composite forward and backward, and the inference composite_rays."""
+    C = 4
+    sig, rgb, deltas, rays, M, _ = edge_rays(C)
+    N = len(rays)
+    rng = np.random.default_rng(4)
+    gws, gim = rng.standard_normal(N).astype(np.float32), rng.standard_normal((N, C)).astype(np.float32)
+    same = deltas.copy()
+    same[:, 2:] = same[:, :2]
+
+    def train(dl, is_ndc):
+        f = O.composite_rays_train_forward(sig, rgb, dl, rays, EDGE_T_THRESH, is_ndc=is_ndc)
+        return f + O.composite_rays_train_backward(gws, gim, sig, rgb, dl, rays, f[0], f[2], EDGE_T_THRESH, is_ndc=is_ndc)
+    base = train(deltas, False)
+    assert all(np.array_equal(a, b) for a, b in zip(base, train(same, True)))
+    assert all(np.array_equal(a, b) for a, b in zip(base, train(same, False)))        # columns 2, 3 are not read without it
+    assert all(not np.array_equal(a, b) for a, b in zip(base, train(deltas, True)))
+
+    n_alive, n_step = 96, 6
+    sg = (rng.random(n_alive * n_step) * 40).astype(np.float32)
+    cl = rng.random((n_alive * n_step, C)).astype(np.float32)
+    dl = rng.uniform(0.002, 0.006, (n_alive * n_step, 4)).astype(np.float32)
+    dl[5 * n_step + 3:6 * n_step, 0] = 0                     # a ray that ends inside the step (:1178)
+    dl_same = dl.copy()
+    dl_same[:, 2:] = dl_same[:, :2]
+    t0 = rng.uniform(0.2, 1.0, n_alive).astype(np.float32)
+
+    def infer(d, is_ndc):
+        alive = np.arange(n_alive, dtype=np.int32)[::-1].copy()
+        rt = np.stack([t0, t0], 1) if is_ndc else t0[:, None].copy()      # (written in place)
+        acc = [np.zeros(n_alive, np.float32), np.zeros(n_alive, np.float32), np.zeros((n_alive, C), np.float32)]
+        O.composite_rays(n_alive, n_step, alive, rt, sg, cl, d, acc[0], acc[1], acc[2], 1e-2, is_ndc=is_ndc)
+        return [alive, rt] + acc
+    base = infer(dl, False)
+    got = infer(dl_same, True)
+    assert (base[0] < 0).any() and (base[0] >= 0).any()
+    assert np.array_equal(got[0], base[0]) and all(np.array_equal(a, b) for a, b in zip(got[2:], base[2:]))
+    assert np.array_equal(got[1][:, 0], base[1][:, 0]) and np.array_equal(got[1][:, 1], base[1][:, 0])
+    other = infer(dl, True)
+    assert np.array_equal(other[1][:, 0], base[1][:, 0])     # the march's t steps by column 1 in both modes
+    assert not np.array_equal(other[1][:, 1], base[1][:, 0])
+    assert all(not np.array_equal(a, b) for a, b in zip(other[2:], base[2:]))
+
+
+def test_oracle_ndc_wiring_march_rays(O):
+    grid, bits = small_scene()
+    N, n_step = 300, 4
+    ro, rd = room_rays(O, N, seed=5)
+    near, far = O.near_far_from_aabb(ro, rd, np.array([-2, -2, -2, 2, 2, 2], np.float32), 0.2)
+    z_hats = np.random.default_rng(5).uniform(0.5, 2.0, N).astype(np.float32)
+    alive = np.arange(N, dtype=np.int32)
+    x0, d0, dl0 = O.march_rays(N, n_step, alive, near[:, None], ro, rd, 2.0, bits, 2, 128, near, far)
+    # column 1 of rays_t is not the march's: poison it
+    rt = np.ascontiguousarray(np.stack([near, np.full(N, np.nan, np.float32)], 1))
+    x1, d1, dl1 = O.march_rays(N, n_step, alive, rt, ro, rd, 2.0, bits, 2, 128, near, far, is_ndc=True, z_hats=z_hats)
+    assert np.array_equal(x0, x1) and np.array_equal(d0, d1) and np.array_equal(dl0[:, :2], dl1[:, :2])
+    emitted = dl0[:, 0] > 0
+    assert emitted.sum() > N and (dl0[:, 2:] == 0).all()
+    assert (dl1[emitted, 2] != 0).all() and (dl1[emitted, 3] != 0).all() and (dl1[~emitted, 2:] == 0).all()
+    # both columns scale with 1 / z_hat
+    _, _, dl2 = O.march_rays(N, n_step, alive, rt, ro, rd, 2.0, bits, 2, 128, near, far, is_ndc=True, z_hats=z_hats * 2)
+    assert np.allclose(dl2[emitted, 2:] * 2, dl1[emitted, 2:], rtol=1e-6)
 
 
 # ---- hash grid ---------------------------------------------------------------------------------------
