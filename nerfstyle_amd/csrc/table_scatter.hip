@@ -12,14 +12,24 @@
 // and a block touches only a handful of cells on every level: at most ceil(res_l / 1024) + 1 per axis.  So the wave
 // keeps, per level, a small LATTICE of corner gradients in LDS anchored at the cell of the block's origin (ceil(res / 1024)
 // + 2 corners per axis: for the reference's LLFF grid -- 16 levels, resolutions 16 .. 4096 -- 5^3 on the two finest levels,
-// 4^3 on the next two and 3^3 below, 702 float4 = 11 KB per wave; grids up to 6^3 per level and 960 slots in all are accepted).  Lane = (level l = lane >> 2,
-// y/z corner pair p = lane & 3) walks the samples in order and adds its two x corners' contributions with a plain LDS
-// read-modify-write: within a step the 64 lanes touch 128 different slots and steps are sequential, so no atomics are
-// needed; the lattice is addressed by cell coordinates, so nothing is hashed per sample.  When the walk enters a new
-// block every level re-anchors; a level whose anchor cell did not change (the coarse ones: a block is a fraction of
-// their cell) keeps accumulating, the others are flushed cooperatively, one merged record per corner a block touched
-// (tools/sorted_scatter_sim.py: ~6 records and ~3 atomic requests per sample on the bench scene against 29.7 / 19.3 of
-// the ray-order run tracker).
+// 4^3 on the next two and 3^3 below, 702 float4 = 11 KB per wave; grids up to 6^3 per level and 960 slots in all are
+// accepted).  Lane = (level l = lane >> 2, y/z corner pair p = lane & 3) walks the samples in order and adds its two x
+// corners' contributions with a plain LDS read-modify-write: within a step the 64 lanes touch 128 different slots and
+// steps are sequential, so no atomics are needed; the lattice is addressed by cell coordinates, so nothing is hashed per
+// sample.
+//
+// When the walk enters a new block every level re-anchors.  A level whose anchor cell did not change (the coarse ones: a
+// block is a fraction of their cell) keeps accumulating.  A level whose anchor moved by d <= S - 1 cells along +x ONLY --
+// the walk is in Morton order with x as bit 0, so this is the step from an x-even block to its +x neighbour, every
+// second block change where space is filled -- SHIFTS: the planes x < d leave the window and are flushed, the planes
+// x >= d are corners of the new lattice as well and move down by d inside the same LDS slots, where the new block's
+// samples join them before anything goes to memory.  Without that the shared face left as lonely rows (on the finest level
+// the anchor is a multiple of 4 cells: corners 0..3 of an x-row fill a 64-byte line of the gradient table, corner 4 is alone
+// in the next one) and came back one block later as part of a full line.  Every other move (y or z changed, a step
+// backwards, a step past the window) flushes the whole lattice, and so does the end of the wave's range.  A flush is
+// cooperative, one merged record per corner a block touched, and its atomic instructions carry whole x-rows, so the
+// corners of a row that share a line leave as one request (lat_flush_level).  Requests per sample on the bench frame,
+// model and counter: DESIGN.md, "(r4) requests per sample"; tools/sorted_scatter_sim.py is the model.
 #include "field_common.h"
 #include "table_scatter.h"
 
@@ -89,69 +99,83 @@ static bool lat_geometry(const NsrLevel *lv, LatGeom &g) {
     return ((total + 63u) & ~63u) <= (uint32_t)LAT_MAX_SLOTS;
 }
 
-// Flushes level l's lattice, anchored at cell (b0, b1, b2) -- wave-uniform arguments -- and clears it.
-// 64 slots per trip, three phases so that nothing is computed four times and every LDS round trip is shared:
-//   1. one lane per slot: read its float4, test it, and (touched slots only) compute the table row ONCE -> rows[lane];
-//   2. four groups of 16 slots, skipped when empty: lane (t = lane >> 2, i = lane & 3) reads component i of slot
-//      16q + t and its row and issues the atomic -- the four dwords of a row leave as ONE 16-byte request, x-neighbouring
-//      corners (consecutive slots) share their 64-byte line;
-//   3. the touched slots are cleared.
+// Flushes the planes x < xl of level l's lattice, anchored at cell (b0, b1, b2), and moves the planes x >= xl down to x - xl
+// (xl, like the anchor, is wave-uniform; xl == S: the whole lattice leaves and is cleared, nothing moves).
+// A trip covers four groups of 16 / S whole x-rows (S = 3: 15 slots per group, 4: 16, 5: 15, 6: 12; the other lanes idle), so
+// that no x-row is cut in two by an atomic instruction: the corners of a row are neighbours in the table (x is the index's
+// lowest term, hashed or dense) and share their 64-byte lines only inside ONE instruction.  Four phases, so that nothing is
+// computed four times and every LDS round trip is shared:
+//   1. one lane per slot: read its float4, test it, and (touched slots of the leaving planes only) compute the table row
+//      ONCE -> rows[lane];
+//   2. the four groups, skipped when empty: lane (t = lane >> 2, i = lane & 3) reads component i of the group's slot t and
+//      its row and issues the atomic -- the four dwords of a row leave as ONE 16-byte request;
+//   3. the touched slots are cleared;
+//   4. the touched slots of the staying planes are written back xl slots lower (same x-row, hence same trip; every lane
+//      still holds its slot's value from phase 1, and the LDS executes a wave's accesses in order).
 template <int S>
 __device__ __forceinline__ void lat_flush_level(float4 *__restrict__ lat4, uint32_t *__restrict__ rows, uint32_t b0, uint32_t b1, uint32_t b2,
-                                                const NsrLevel &lv, float *__restrict__ gt, int lane, bool td, bool tc) {
+                                                const NsrLevel &lv, float *__restrict__ gt, int lane, bool td, bool tc, uint32_t xl) {
     constexpr int NC = S * S * S;
+    constexpr int RS = (16 / S) * S;                                      // slots per 16-lane group: whole x-rows
     const int t = lane >> 2, i = lane & 3;
+    const int g = lane >> 4, j = lane & 15;
     const bool on = (i < 2) ? td : tc;
     const float *lf = reinterpret_cast<const float *>(lat4);
-#pragma unroll
-    for (int k0 = 0; k0 < NC; k0 += 64) {
-        const int k = k0 + lane;
+#pragma unroll 1
+    for (int k0 = 0; k0 < NC; k0 += 4 * RS) {
+        const int k = k0 + g * RS + j;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (k < NC) v = lat4[k];
+        if (j < RS && k < NC) v = lat4[k];
         const bool nz = seq_nonzero(v);
-        const unsigned long long m = __ballot(nz);
-        if (m == 0ull) continue;                                          // wave-uniform: nothing touched in these slots
+        if (__ballot(nz) == 0ull) continue;                               // wave-uniform: nothing touched in these slots
+        bool out = false;
         if (nz) {
             // k < 256: the divisions by S*S and S are 24-bit multiplies by 16-bit reciprocals (exact on this range); a 32-bit
             // integer multiply costs four issue slots on this machine and the scatter is issue bound
             constexpr uint32_t MZ = (65536u + S * S - 1u) / (S * S), MY = (65536u + S - 1u) / S;
             const uint32_t z = __umul24((uint32_t)k, MZ) >> 16, r = (uint32_t)k - __umul24(z, (uint32_t)(S * S));
             const uint32_t y = __umul24(r, MY) >> 16, x = r - __umul24(y, (uint32_t)S);
-            rows[lane] = lv.offset + lat_row(lv, b0 + x, b1 + y, b2 + z);
+            out = x < xl;
+            if (out) rows[lane] = lv.offset + lat_row(lv, b0 + x, b1 + y, b2 + z);
         }
+        const unsigned long long m = __ballot(out);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            if (k0 + 16 * q >= NC) break;
+            if (k0 + RS * q >= NC) break;
             if (((m >> (16 * q)) & 0xFFFFull) == 0ull) continue;          // wave-uniform
             const bool rec = (m >> (16 * q + t)) & 1ull;
             if (rec) {
-                const float val = lf[(k0 + 16 * q + t) * 4 + i];
+                const float val = lf[(k0 + RS * q + t) * 4 + i];
                 const uint32_t row = rows[16 * q + t];
                 if (on) atomicAdd(gt + (size_t)row * 4 + i, val);
             }
         }
         __builtin_amdgcn_wave_barrier();
         if (nz) lat4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        __builtin_amdgcn_wave_barrier();
+        if (nz && !out) lat4[k - (int)xl] = v;                            // x >= xl: never for a whole-lattice flush
     }
 }
 
 // The geometry of level fl comes from the LDS copy of the level table (pad_ = S | shift << 4 | base << 8): a read from the
 // kernel-argument segment here would be a vector-memory load, and waiting for it means waiting for every atomic in flight.
-__device__ __forceinline__ void lat_flush_dispatch(float4 *__restrict__ lat, int fl, const LatState &st,
+// xl_lane: the number of leaving x planes of the lane's own level (lat_flush_level's xl); the lanes of a level agree.
+__device__ __forceinline__ void lat_flush_dispatch(float4 *__restrict__ lat, int fl, const LatState &st, uint32_t xl_lane,
                                                    const NsrLevel *__restrict__ lds_lv, float *__restrict__ gt, int lane, bool td, bool tc) {
     const uint32_t o0 = (uint32_t)__builtin_amdgcn_readlane((int)st.b0, fl * 4);
     if (o0 == LAT_NONE) return;
     const uint32_t o1 = (uint32_t)__builtin_amdgcn_readlane((int)st.b1, fl * 4);
     const uint32_t o2 = (uint32_t)__builtin_amdgcn_readlane((int)st.b2, fl * 4);
+    const uint32_t xl = (uint32_t)__builtin_amdgcn_readlane((int)xl_lane, fl * 4);
     const NsrLevel flv = lds_lv[fl];
     float4 *lf = lat + (flv.pad_ >> 8);
     uint32_t *rows = reinterpret_cast<uint32_t *>(lat) - 64;                  // 64-entry row scratch in front of the lattices
     switch (flv.pad_ & 0xFu) {
-    case 3: lat_flush_level<3>(lf, rows, o0, o1, o2, flv, gt, lane, td, tc); break;
-    case 4: lat_flush_level<4>(lf, rows, o0, o1, o2, flv, gt, lane, td, tc); break;
-    case 5: lat_flush_level<5>(lf, rows, o0, o1, o2, flv, gt, lane, td, tc); break;
-    default: lat_flush_level<6>(lf, rows, o0, o1, o2, flv, gt, lane, td, tc); break;
+    case 3: lat_flush_level<3>(lf, rows, o0, o1, o2, flv, gt, lane, td, tc, xl); break;
+    case 4: lat_flush_level<4>(lf, rows, o0, o1, o2, flv, gt, lane, td, tc, xl); break;
+    case 5: lat_flush_level<5>(lf, rows, o0, o1, o2, flv, gt, lane, td, tc, xl); break;
+    default: lat_flush_level<6>(lf, rows, o0, o1, o2, flv, gt, lane, td, tc, xl); break;
     }
 }
 
@@ -275,11 +299,19 @@ k_table_scatter(TableScatterArgs a) {
                         nsr_grid_locate(o1, lv.resolution, 1, ff, n1);
                         nsr_grid_locate(o2, lv.resolution, 1, ff, n2);
                         const bool chg = (n0 != st.b0) | (n1 != st.b1) | (n2 != st.b2);
+                        // Shift-carry: the anchor moved along +x only and by less than the lattice is wide (in Morton order
+                        // with x as bit 0, the block after an x-even block is its +x neighbour whenever that one holds
+                        // samples): the planes x >= n0 - b0 are corners of the new lattice too -- they stay, moved down,
+                        // and only the planes that leave the window are flushed.  Anything else (y or z moved, a step
+                        // backwards or past the window, no anchor yet) flushes the whole lattice.
+                        const uint32_t dx = n0 - st.b0;
+                        const bool carry = (st.b0 != LAT_NONE) & (n1 == st.b1) & (n2 == st.b2) & (dx - 1u < S - 1u);
+                        const uint32_t xl = carry ? dx : S;
                         unsigned long long mm = __ballot(chg);
                         while (mm) {
                             const int fl = (int)(__builtin_ctzll(mm) >> 2);
                             mm &= ~(0xFull << (fl * 4));
-                            lat_flush_dispatch(lat, fl, st, lds_lv, gt, lane, td, tc);
+                            lat_flush_dispatch(lat, fl, st, xl, lds_lv, gt, lane, td, tc);
                         }
                         if (chg) { st.b0 = n0; st.b1 = n1; st.b2 = n2; bf0 = (float)n0; bf1 = (float)n1; bf2 = (float)n2; }
                     }
@@ -339,7 +371,7 @@ k_table_scatter(TableScatterArgs a) {
     // every level's lattice leaves
     __builtin_amdgcn_wave_barrier();
 #pragma unroll 1
-    for (int fl = 0; fl < 16; fl++) lat_flush_dispatch(lat, fl, st, lds_lv, gt, lane, td, tc);
+    for (int fl = 0; fl < 16; fl++) lat_flush_dispatch(lat, fl, st, S, lds_lv, gt, lane, td, tc);
 }
 
 bool nsr_table_scatter_supported(const NsrLevel *lv) {

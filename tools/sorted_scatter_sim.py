@@ -4,7 +4,18 @@ or (b) in Morton order of their finest-level cell with a per-wave, per-level LDS
 corner gradients of T^3 cells and is flushed (one record per touched corner) when the wave's sample stream leaves
 the tile.  Analysis tool only (uses oracle/ for marching); not imported by the product.
 
-usage: python tools/sorted_scatter_sim.py [patch_edge_px=96] [samples_per_wave=47000]"""
+usage: python tools/sorted_scatter_sim.py [patch_edge_px=96] [samples_per_wave=47000]
+
+`python tools/sorted_scatter_sim.py lattice [patch_edge_px=96] [x0=400] [y0=300] [samples_per_wave=2976]` models the shipped
+kernel instead (table_scatter.hip: 10-bit block keys, per-level lattices anchored at the block or block group, flushes of
+the touched corners 16 slots per atomic instruction) and counts 64-byte atomic requests per sample and level under
+  (a)  a re-anchor flushes the whole lattice (the kernel before the shift-carry), with the old 16-consecutive-slots
+       instruction groups and with groups of whole x-rows;
+  (b)  x-carry: an anchor that moved by 0 < d <= S - 1 cells along +x only flushes the planes x < d, the rest stays;
+  (c)  the same on whichever single axis moved.
+A wave walks `samples_per_wave` consecutive samples (the bench frame: 48.6 M samples over 16 384 waves = 186 tiles) and
+flushes everything at its end.  Not modelled: samples whose gradient is zero (they touch nothing), the rays outside
+the patch that share its blocks, and the order in which the memory side sees the requests."""
 import os
 import sys
 
@@ -62,7 +73,129 @@ def hash_row(cx, cy, cz, size, offset):
     return (idx % size).astype(np.int64) + offset
 
 
+def lat_corners(res, shift):
+    span, blocks = int(res) << shift, 1024
+    cells = span // blocks if span % blocks == 0 else span // blocks + 2
+    return cells + 1
+
+
+def lat_geometry(res):
+    """table_scatter.hip lat_geometry: (corners per axis, anchor group shift) per level"""
+    out = []
+    for r in res:
+        shift, S = 0, lat_corners(r, 0)
+        while shift < 10 and lat_corners(r, shift + 1) <= max(S, 3):
+            shift += 1
+        out.append((max(lat_corners(r, shift), S), shift))
+    return out
+
+
+def count_requests(masks, anchors, S, size, offset, rows_per_group):
+    """masks [n, S^3] bool (slot = (z * S + y) * S + x), anchors [n, 3]: requests when every event's flagged slots leave
+    `rows_per_group` x-rows (None: 16 consecutive slots) per atomic instruction; distinct 64-byte lines per instruction"""
+    if len(masks) == 0:
+        return 0
+    masks, anchors = np.asarray(masks), np.asarray(anchors, np.int64)
+    k = np.arange(S ** 3)
+    x, y, z = k % S, (k // S) % S, k // (S * S)
+    rows = hash_row(anchors[:, None, 0] + x[None], anchors[:, None, 1] + y[None], anchors[:, None, 2] + z[None], size, offset)
+    line = np.where(masks, rows >> 2, -1)
+    g = 16 if rows_per_group is None else rows_per_group * S
+    total = 0
+    for s0 in range(0, S ** 3, g):
+        sub = np.sort(line[:, s0:s0 + g], axis=1)
+        total += int(((np.diff(sub, axis=1) != 0) & (sub[:, 1:] >= 0)).sum() + (sub[:, 0] >= 0).sum())
+    return total
+
+
+def lattice_model(u, spw):
+    """requests per sample and level under the rules (a) old groups, (a) row groups, (b), (c)"""
+    pls = O.per_level_scale_from_cfg()
+    off = O.grid_offsets(16, pls, 16, 19)
+    res = [int(r) for r in O.grid_resolutions(16, O.grid_S(pls), 16)]
+    geom = lat_geometry(res)
+    M = len(u)
+    q = np.clip(np.floor(u * np.float32(1024)), 0, 1023).astype(np.int64)
+    order = np.argsort(morton3(np.maximum(q - 512, 0)), kind='stable')
+    u, q = u[order], q[order]
+    wave = np.arange(M) // spw
+    corners = np.array([[(i >> d) & 1 for d in range(3)] for i in range(8)], np.int64)
+    table = []
+    for l in range(16):
+        S, shift = geom[l]
+        NC, size, offset = S ** 3, int(off[l + 1] - off[l]), int(off[l])
+        o = ((q >> shift) << shift).astype(np.float32) * np.float32(1.0 / 1024)
+        anchor = np.minimum(np.floor(o * np.float32(res[l])), res[l] - 1).astype(np.int64)
+        rel = level_cells(u, res[l]) - anchor
+        direct = (rel > S - 2).any(1)                       # fp32 rounding: one cell past the lattice -> straight to the table
+        rel = np.minimum(rel, S - 2)
+        change = np.r_[True, (np.diff(anchor, axis=0) != 0).any(1) | (np.diff(wave) != 0)]
+        seg = np.cumsum(change) - 1
+        nseg = int(seg[-1]) + 1
+        touched = np.zeros((nseg, NC), bool)
+        cc = rel[:, None, :] + corners[None]
+        slot = (cc[:, :, 2] * S + cc[:, :, 1]) * S + cc[:, :, 0]
+        live = ~direct
+        touched[np.repeat(seg[live], 8), slot[live].reshape(-1)] = True
+        first = np.flatnonzero(change)
+        sa, sw = anchor[first], wave[first]
+        # 8 atomic instructions (two x corners x four components) of 4 lanes with different (y, z) rows each
+        extra = 32 * int(direct.sum())
+        row = {'S': S, 'shift': shift, 'direct': float(direct.mean())}
+        row['a_old'] = (count_requests(touched, sa, S, size, offset, None) + extra) / M
+        row['a_rows'] = (count_requests(touched, sa, S, size, offset, 16 // S) + extra) / M
+        for rule in ('b', 'c'):
+            ev_m, ev_a = [], []
+            T = np.zeros((S, S, S), bool)                   # [z, y, x]
+            for i in range(nseg):
+                if i > 0:
+                    d = sa[i] - sa[i - 1]
+                    ax = np.flatnonzero(d)
+                    carry = sw[i] == sw[i - 1] and len(ax) == 1 and 0 < d[ax[0]] <= S - 1 and (rule == 'c' or ax[0] == 0)
+                    if carry:
+                        a, n = 2 - int(ax[0]), int(d[ax[0]])   # array axis of the moving coordinate
+                        out = np.zeros_like(T)
+                        sl = [slice(None)] * 3
+                        sl[a] = slice(0, n)
+                        out[tuple(sl)] = T[tuple(sl)]
+                        T = np.roll(T, -n, axis=a)
+                        sl[a] = slice(S - n, S)
+                        T[tuple(sl)] = False
+                    else:
+                        out, T = T, np.zeros((S, S, S), bool)
+                    if out.any():
+                        ev_m.append(out.reshape(-1))
+                        ev_a.append(sa[i - 1])
+                T = T | touched[i].reshape(S, S, S)
+            ev_m.append(T.reshape(-1))
+            ev_a.append(sa[-1])
+            row[rule] = (count_requests(ev_m, ev_a, S, size, offset, 16 // S) + extra) / M
+        table.append(row)
+        print('level %2d res %4d S %d shift %d  segments/sample %.3f  (a) %.3f  (a, row groups) %.3f  (b) %.3f  (c) %.3f   direct %.1e'
+              % (l, res[l], S, shift, nseg / M, row['a_old'], row['a_rows'], row['b'], row['c'], row['direct']), flush=True)
+    return table
+
+
+def main_lattice(argv):
+    edge = int(argv[0]) if len(argv) > 0 else 96
+    x0, y0 = (int(argv[1]) if len(argv) > 1 else 400), (int(argv[2]) if len(argv) > 2 else 300)
+    spw = int(argv[3]) if len(argv) > 3 else 2976
+    xyz, _ = dense_patch_samples(edge, x0, y0)
+    u = O.encoder_inputs(xyz, 2.0).astype(np.float32)
+    print('rays', edge * edge, 'samples', len(u), 'per ray %.1f' % (len(u) / edge / edge), 'samples per wave', spw)
+    t = lattice_model(u, spw)
+    print('| level | res | S | (a) today | (a) whole x-rows per instruction | (b) x-carry | (c) any-axis carry |')
+    print('|---|---|---|---|---|---|---|')
+    for l, r in enumerate(t):
+        print('| %d | | %d | %.3f | %.3f | %.3f | %.3f |' % (l, r['S'], r['a_old'], r['a_rows'], r['b'], r['c']))
+    tot = {k: sum(r[k] for r in t) for k in ('a_old', 'a_rows', 'b', 'c')}
+    print('| all | | | %.2f | %.2f | %.2f | %.2f |' % (tot['a_old'], tot['a_rows'], tot['b'], tot['c']))
+    print('(c) takes a further %.1f %% of the requests (b) leaves' % (100 * (tot['b'] - tot['c']) / tot['b']))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'lattice':
+        return main_lattice(sys.argv[2:])
     edge = int(sys.argv[1]) if len(sys.argv) > 1 else 96
     spw = int(sys.argv[2]) if len(sys.argv) > 2 else 47000
     xyz, rays = dense_patch_samples(edge, int(sys.argv[3]) if len(sys.argv) > 3 else 0, int(sys.argv[4]) if len(sys.argv) > 4 else 0)
