@@ -75,24 +75,66 @@ __device__ __forceinline__ void field_build_bw(short *lds, const float *__restri
 // is compiled with -mllvm --amdgpu-mfma-vgpr-form: every other MFMA (forward recompute, dgrad, the identity transposes) then
 // writes straight to VGPRs.  Left to its heuristics the compiler gives ALL MFMAs of a kernel that needs AGPRs an AGPR
 // destination and copies each transient result back (396 v_accvgpr_read per 16-sample tile, 22 % of the loop).
-// The s_nop covers the VALU-write -> MFMA-read distance the hazard recogniser cannot see through the asm; the operands
-// always come from a VALU rounding step (mm_round4), never directly from another MFMA.
 // ASM: the GOUT instantiations (this pinning); the tracker ones keep the compiler's own choice (see k_field_bwd).
-template <int CD, bool ASM>
-__device__ __forceinline__ void field_wgrad_mfma(f4v &acc, s4v a, s4v b) {
-    if constexpr (ASM) {
-        if (CD == NSR_F16) asm("s_nop 1\n\tv_mfma_f32_16x16x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-        else asm("s_nop 1\n\tv_mfma_f32_16x16x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-    } else {
-        acc = MM<CD>::k16(a, b, acc);
-    }
+//
+// The assembly is issued in hazard-complete blocks of four MFMAs on four DIFFERENT accumulators (field_wgrad_mfma4).  The
+// compiler neither sees nor pads what is inside an asm statement, so each block carries what the gfx950 ISA asks of it:
+//   head: a VALU write of a VGPR needs 2 wait states before an MFMA reads it as SrcA / SrcB (CDNA3 / CDNA4 ISA guide,
+//         "Manually Inserted Wait States": VALU write VGPR -> v_mfma* read).  The operands come from the transposes'
+//         packed conversions, which the compiler may place directly in front of the block: one `s_nop 1`, once per block,
+//         whatever the distance (the previous form paid it in front of every MFMA);
+//   body: MFMAs with different destinations and read-only A / B need no wait between them, and an accumulator's own chain
+//         (the same instruction taking the previous result whole as SrcC, from the previous tile's block) is interlocked
+//         by the hardware: 0 wait states;
+//   tail: nothing but such a chain reads an accumulator inside the sample loop.  Their first other reader is the
+//         reduction after the loop, which sits behind field_wgrad_settle.
+// The statements are volatile: they stay in program order among themselves, so each accumulator sees its tiles in the
+// order the samples are walked.
+template <int CD>
+__device__ __forceinline__ void field_wgrad_mfma4(f4v &c0, f4v &c1, f4v &c2, f4v &c3, s4v a0, s4v b0, s4v a1, s4v b1, s4v a2,
+                                                  s4v b2, s4v a3, s4v b3) {
+    if (CD == NSR_F16)
+        asm volatile("s_nop 1\n\t"
+                     "v_mfma_f32_16x16x16_f16 %0, %4, %5, %0\n\t"
+                     "v_mfma_f32_16x16x16_f16 %1, %6, %7, %1\n\t"
+                     "v_mfma_f32_16x16x16_f16 %2, %8, %9, %2\n\t"
+                     "v_mfma_f32_16x16x16_f16 %3, %10, %11, %3"
+                     : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3)
+                     : "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(a2), "v"(b2), "v"(a3), "v"(b3));
+    else
+        asm volatile("s_nop 1\n\t"
+                     "v_mfma_f32_16x16x16_bf16 %0, %4, %5, %0\n\t"
+                     "v_mfma_f32_16x16x16_bf16 %1, %6, %7, %1\n\t"
+                     "v_mfma_f32_16x16x16_bf16 %2, %8, %9, %2\n\t"
+                     "v_mfma_f32_16x16x16_bf16 %3, %10, %11, %3"
+                     : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3)
+                     : "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(a2), "v"(b2), "v"(a3), "v"(b3));
+}
+// Behind the last block of the launch: an MFMA's result needs up to 18 wait states (the longest, 16-pass, form) before
+// anything but its own accumulate chain may read it; the compiler, which does not know that the blocks hold MFMAs, pads
+// nothing in front of the reduction's v_accvgpr_read.
+template <int NT>
+__device__ __forceinline__ void field_wgrad_settle(f4v (&acc)[NT]) {
+    static_assert(NT % 4 == 0, "accumulators come in blocks of four");
+#pragma unroll
+    for (int k = 0; k < NT; k += 4)
+        asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[k]), "+a"(acc[k + 1]), "+a"(acc[k + 2]), "+a"(acc[k + 3]));
 }
 template <int CD, bool ASM, int NG, int NA>
 __device__ __forceinline__ void field_wgrad(f4v (&acc)[NG * NA], const s4v (&Gt)[NG], const s4v (&At)[NA]) {
+    if constexpr (ASM) {
+        // tile j = ot * NA + it; four consecutive tiles per block
+        static_assert((NG * NA) % 4 == 0, "accumulators come in blocks of four");
 #pragma unroll
-    for (int ot = 0; ot < NG; ot++) {
+        for (int j = 0; j < NG * NA; j += 4)
+            field_wgrad_mfma4<CD>(acc[j], acc[j + 1], acc[j + 2], acc[j + 3], Gt[j / NA], At[j % NA], Gt[(j + 1) / NA],
+                                  At[(j + 1) % NA], Gt[(j + 2) / NA], At[(j + 2) % NA], Gt[(j + 3) / NA], At[(j + 3) % NA]);
+    } else {
 #pragma unroll
-        for (int it = 0; it < NA; it++) field_wgrad_mfma<CD, ASM>(acc[ot * NA + it], Gt[ot], At[it]);
+        for (int ot = 0; ot < NG; ot++) {
+#pragma unroll
+            for (int it = 0; it < NA; it++) acc[ot * NA + it] = MM<CD>::k16(Gt[ot], At[it], acc[ot * NA + it]);
+        }
     }
 }
 
@@ -129,40 +171,65 @@ __device__ __forceinline__ void field_tr4(const s8v (&x)[2], s4v ident, s4v (&ou
     out[3] = mm_transpose16<CD>(mm_hi(x[1]), ident);
 }
 
+// GOUT: the four 16x16 blocks of a 64-row activation / gradient pair (+ one extra K = 16 block) as ONE transpose pipeline
+constexpr int TR_DEPTH = 4;      // identity MFMAs in flight (mm_transpose16_n); every step more costs the kernel a register quad
+template <int CD>
+__device__ __forceinline__ void field_tr4p(const s8v (&x)[2], s4v ident, s4v (&out)[4]) {
+    const s4v in[4] = {mm_lo(x[0]), mm_hi(x[0]), mm_lo(x[1]), mm_hi(x[1])};
+    mm_transpose16_n<CD, 4, TR_DEPTH>(in, ident, out);
+}
+template <int CD>
+__device__ __forceinline__ void field_tr5p(const s8v (&x)[2], s4v y, s4v ident, s4v (&out)[4], s4v (&yt)[1]) {
+    const s4v in[5] = {mm_lo(x[0]), mm_hi(x[0]), mm_lo(x[1]), mm_hi(x[1]), y};
+    s4v o[5];
+    mm_transpose16_n<CD, 5, TR_DEPTH>(in, ident, o);
+    out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3]; yt[0] = o[4];
+}
+
 // 4 gradient tiles -> masked by the forward activation -> two K=32 B fragments
 template <int CD, bool PKMASK>
 __device__ __forceinline__ void field_mask_pack(const f4v (&gacc)[4], const s8v (&act)[2], s8v (&out)[2]) {
     if constexpr (PKMASK) {
         // Round first, mask afterwards on the packed 16-bit pairs: (act > 0 as a signed 16-bit pattern) -> all-ones / zero by
-        // max(act, 0), negate, arithmetic shift -- three packed instructions per PAIR instead of a compare and a select per
-        // element, and one packed conversion per pair.  Same bits: a masked element is +0 either way, the others are rounded
-        // alike (round to nearest even).  The mask is inline asm: the compiler turns the same arithmetic back into compares and
-        // selects.
+        // a saturating negate and an arithmetic shift -- two packed instructions per PAIR instead of a compare and a select
+        // per element, and one packed conversion per pair.  Same bits: a masked element is +0 either way, the others are
+        // rounded alike (round to nearest even).  (The saturation matters for 0x8000 alone, whose plain negate is itself;
+        // until round 5 the chain was max(act, 0), negate, shift: the same mask for all 65 536 patterns, checked one by
+        // one on the CPU, DESIGN.md "(r5)".)  The mask is inline asm: the compiler turns the same arithmetic back into
+        // compares and selects.  One statement per fragment, negates first and shifts behind them: the compiler pads one
+        // wait state between an asm statement and the first VALU instruction that reads its outputs, and with a
+        // statement per pair that was one no-op per pair.
 #pragma unroll
         for (int t = 0; t < 2; t++) {
             const uint4 a4 = __builtin_bit_cast(uint4, act[t]);
-            const uint32_t ap[4] = {a4.x, a4.y, a4.z, a4.w};
-            uint32_t o[4];
+            uint32_t gp[4], m[4];
 #pragma unroll
             for (int p = 0; p < 4; p++) {                       // pair p of this fragment: elements 2p, 2p + 1
                 const f4v &g = gacc[2 * t + (p >> 1)];
                 const int e = 2 * (p & 1);
                 // (the conversion is left to the compiler: it reads MFMA results, and only the compiler knows how many wait
                 // states that read needs -- an inline-asm conversion here returned stale accumulators in one instantiation)
-                uint32_t gp, m;
                 if (CD == NSR_F16) {
                     typedef _Float16 hh2 __attribute__((ext_vector_type(2)));
                     const hh2 hp = {(_Float16)g[e], (_Float16)g[e + 1]};
-                    gp = __builtin_bit_cast(uint32_t, hp);
+                    gp[p] = __builtin_bit_cast(uint32_t, hp);
                 } else {
                     typedef __bf16 bb2 __attribute__((ext_vector_type(2)));
                     const bb2 bp = {(__bf16)g[e], (__bf16)g[e + 1]};
-                    gp = __builtin_bit_cast(uint32_t, bp);
+                    gp[p] = __builtin_bit_cast(uint32_t, bp);
                 }
-                asm("v_pk_max_i16 %0, %1, 0\n\tv_pk_sub_i16 %0, 0, %0\n\tv_pk_ashrrev_i16 %0, 15, %0 op_sel_hi:[0,1]" : "=&v"(m) : "v"(ap[p]));
-                o[p] = gp & m;
             }
-            out[t] = __builtin_bit_cast(s8v, make_uint4(o[0], o[1], o[2], o[3]));
+            asm("v_pk_sub_i16 %0, 0, %4 clamp\n\t"
+                "v_pk_sub_i16 %1, 0, %5 clamp\n\t"
+                "v_pk_sub_i16 %2, 0, %6 clamp\n\t"
+                "v_pk_sub_i16 %3, 0, %7 clamp\n\t"
+                "v_pk_ashrrev_i16 %0, 15, %0 op_sel_hi:[0,1]\n\t"
+                "v_pk_ashrrev_i16 %1, 15, %1 op_sel_hi:[0,1]\n\t"
+                "v_pk_ashrrev_i16 %2, 15, %2 op_sel_hi:[0,1]\n\t"
+                "v_pk_ashrrev_i16 %3, 15, %3 op_sel_hi:[0,1]"
+                : "=&v"(m[0]), "=&v"(m[1]), "=&v"(m[2]), "=&v"(m[3])
+                : "v"(a4.x), "v"(a4.y), "v"(a4.z), "v"(a4.w));
+            out[t] = __builtin_bit_cast(s8v, make_uint4(gp[0] & m[0], gp[1] & m[1], gp[2] & m[2], gp[3] & m[3]));
         }
     } else {
         out[0] = mm_cat(mm_round4<CD, false>(mm_relu_mask(gacc[0], mm_lo(act[0]))),
@@ -550,7 +617,10 @@ k_field_bwd(FieldBwdArgs b) {
         //   GOUT:    straight order; ReLU on packed halves (13.5 -> 13.0 ms); the next tile's inputs requested right after
         //            this tile's first layer, with `cur` waited for at the loop top (13.2 -> 11.7 ms); weight-fragment reads
         //            queued ahead of the MFMA stream (11.7 -> 10.7 ms); the backward's ReLU masks on packed 16-bit pairs
-        //            (1412 -> 1304 instructions per tile, 10.6 -> 10.0 ms).  An 8-deep queue for the two 8-fragment
+        //            (1412 -> 1304 instructions per tile, 10.6 -> 10.0 ms); the wgrad operand transposes as pipelines of four
+        //            identity MFMAs in flight, the wgrad MFMAs in blocks of four with one wait-state pad, the mask chain one
+        //            instruction shorter (1254 -> 1114 instructions, 158 -> 59 no-ops per tile, 10.43 -> 9.56 ms; DESIGN.md
+        //            "(r5)").  An 8-deep queue for the two 8-fragment
         //            layers: no change.  The wgrad operand transposes through LDS (ds_write_b64 + ds_read_b64_tr_b16, 49 per
         //            tile) instead of an MFMA with the identity + re-rounding: 1304 -> 1240 instructions per tile and the
         //            same time (21.4 vs 21.5 ms for the pair) -- the LDS round trips cost what the MFMAs did.
@@ -639,64 +709,65 @@ k_field_bwd(FieldBwdArgs b) {
                 mm_queue16<4>(wq16, wt + BW_C1BT, lane);
                 gc1 = mm_round4<CD, false>(t1[0]);
                 // wgrads of r3, r2, r1
-                s4v hr2t[4], hr1t[4], g2t[4], g1t[4];
-                field_tr4<CD>(hr2, ident, hr2t);
-                field_tr4<CD>(g2, ident, g2t);
-                const s4v dyrt[1] = {mm_transpose16<CD>(dyr, ident)};
+                // (every block is transposed right in front of the wgrad that consumes it: the transposed copies are then
+                // live for one layer only, which is where the pipeline's extra register quads come from)
+                s4v hr2t[4], hr1t[4], g2t[4], g1t[4], dyrt[1], c1t[1];
+                field_tr5p<CD>(hr2, dyr, ident, hr2t, dyrt);
                 field_wgrad<CD, GOUT>(w_r3, dyrt, hr2t);
-                field_tr4<CD>(hr1, ident, hr1t);
+                field_tr4p<CD>(g2, ident, g2t);
+                field_tr4p<CD>(hr1, ident, hr1t);
                 field_wgrad<CD, GOUT>(w_r2, g2t, hr1t);
-                field_tr4<CD>(g1, ident, g1t);
-                const s4v c1t[1] = {mm_transpose16<CD>(c1b, ident)};
+                field_tr5p<CD>(g1, c1b, ident, g1t, c1t);
                 field_wgrad<CD, GOUT>(w_r1, g1t, c1t);
             }
             // transposed encoder features (shared by the color1 / class / density wgrads)
             s4v xct[2], xdt[2];
-            field_tr2<CD>(xc, ident, xct);
-            field_tr2<CD>(xd, ident, xdt);
+            {
+                const s8v xcd[2] = {xc[0], xd[0]};
+                s4v xt[4];
+                field_tr4p<CD>(xcd, ident, xt);
+                xct[0] = xt[0]; xct[1] = xt[1]; xdt[0] = xt[2]; xdt[1] = xt[3];
+            }
 
             // ================= color1: 32 -> 64 -> 16, and class: 32 -> 64 -> nc ==================
             {
                 s8v gh[2];
-                s4v ght[4], hct[4];
+                s4v ght[4], hct[4], gc1t[1];
                 mm_layer16_q<CD, 4>(wq16, gc1, h);
                 mm_queue32<4>(wq, wt + BW_C1AT, lane);
                 field_mask_pack<CD, GOUT>(h, hc, gh);
                 mm_layer32_q<CD, 2, 2>(wq, wt + BW_C1AT, lane, gh, gxc);
                 mm_queue16<4>(wq16, wt + BW_K2T, lane);
-                field_tr4<CD>(hc, ident, hct);
-                const s4v gc1t[1] = {mm_transpose16<CD>(gc1, ident)};
+                field_tr5p<CD>(hc, gc1, ident, hct, gc1t);
                 field_wgrad<CD, GOUT>(w_c1b, gc1t, hct);
-                field_tr4<CD>(gh, ident, ght);
+                field_tr4p<CD>(gh, ident, ght);
                 field_wgrad<CD, GOUT>(w_c1a, ght, xct);
             }
             {
                 s8v gh[2];
-                s4v ght[4], hkt[4];
+                s4v ght[4], hkt[4], dykt[1];
                 mm_layer16_q<CD, 4>(wq16, dyk, h);
                 mm_queue32<4>(wq, wt + BW_K1T, lane);
                 field_mask_pack<CD, GOUT>(h, hk, gh);
                 mm_layer32_q<CD, 2, 2, true>(wq, wt + BW_K1T, lane, gh, gxc);
                 mm_queue16<4>(wq16, wt + BW_D2T, lane);
-                field_tr4<CD>(hk, ident, hkt);
-                const s4v dykt[1] = {mm_transpose16<CD>(dyk, ident)};
+                field_tr5p<CD>(hk, dyk, ident, hkt, dykt);
                 field_wgrad<CD, GOUT>(w_k2, dykt, hkt);
-                field_tr4<CD>(gh, ident, ght);
+                field_tr4p<CD>(gh, ident, ght);
                 field_wgrad<CD, GOUT>(w_k1, ght, xct);
             }
             // ================= density: 32 -> 64 -> 1 =============================================
             {
                 s8v gh[2];
-                s4v ght[4], hdt[4];
+                s4v ght[4], hdt[4], dydt[1];
                 mm_layer16_q<CD, 4>(wq16, dyd, h);
                 mm_queue32<4>(wq, wt + BW_D1T, lane);
                 field_mask_pack<CD, GOUT>(h, hd, gh);
                 mm_layer32_q<CD, 2, 2>(wq, wt + BW_D1T, lane, gh, gxd);
                 mm_queue32<4>(wq, wl + FW_D1, lane);          // the next tile's first layer
-                field_tr4<CD>(hd, ident, hdt);
-                const s4v dydt[1] = {mm_transpose16<CD>(dyd, ident)};
+                field_tr5p<CD>(hd, dyd, ident, hdt, dydt);
                 field_wgrad<CD, GOUT>(w_d2, dydt, hdt);
-                field_tr4<CD>(gh, ident, ght);
+                field_tr4p<CD>(gh, ident, ght);
                 field_wgrad<CD, GOUT>(w_d1, ght, xdt);
             }
         } else {
@@ -864,6 +935,11 @@ k_field_bwd(FieldBwdArgs b) {
         if (GOUT) { idx_cur = idx_next; idx_next = idx_nn; }
     }
     if (GOUT) gout_store();
+    if constexpr (GOUT) {
+        field_wgrad_settle(w_r3); field_wgrad_settle(w_r2); field_wgrad_settle(w_r1); field_wgrad_settle(w_c1b);
+        field_wgrad_settle(w_c1a); field_wgrad_settle(w_k2); field_wgrad_settle(w_k1); field_wgrad_settle(w_d2);
+        field_wgrad_settle(w_d1);
+    }
     if (!GOUT && (td || tc)) {
         // close the runs still open in registers
         if (q.tail - q.head > SCQ_CAP - 128) scq_pace(q, gt1, lane, td, tc, 16, false);
@@ -951,7 +1027,7 @@ static int field_bwd_launch_variant(const FieldBwdArgs &b, int table_dtype, int 
 }
 
 // The GOUT instantiations live in their own translation unit (field_bwd_gout.hip): they are compiled with the
-// accumulators pinned to AGPRs by inline assembly (field_wgrad_mfma) and every other MFMA in VGPR form
+// accumulators pinned to AGPRs by inline assembly (field_wgrad_mfma4) and every other MFMA in VGPR form
 // (-mllvm --amdgpu-mfma-vgpr-form: 1816 -> 1435 instructions per tile, 14.4 -> 13.5 ms);
 // the tracker instantiations keep the compiler's own choice -- the same treatment made them slower (49 -> 52 ms: their
 // paced atomic drains are tuned to the old schedule).

@@ -258,6 +258,30 @@ __device__ __forceinline__ s4v mm_transpose16(s4v z, s4v ident) {
     const f4v t = MM<CD>::k16(z, ident, zero);
     return mm_round4<CD, false>(t);
 }
+// N transposes as one pipeline, DEPTH identity MFMAs in flight on distinct destination quads: the two conversions of
+// transpose i are issued behind the MFMA of transpose i + DEPTH - 1, pinned like mm_layer32_q's ring.  One at a time
+// (mm_transpose16) each MFMA is followed by the full MFMA-write -> VALU-read wait as no-ops and then by its conversions,
+// with nothing overlapped -- and at one wave per SIMD nothing else fills that time.  Same values: the same MFMA and the
+// same rounding per block.  Costs DEPTH - 1 register quads over the single form.
+template <int CD, int N, int DEPTH>
+__device__ __forceinline__ void mm_transpose16_n(const s4v (&z)[N], s4v ident, s4v (&out)[N]) {
+    constexpr int D = DEPTH < N ? DEPTH : N;
+    const f4v zero = {0.f, 0.f, 0.f, 0.f};
+    f4v t[N];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < N; i++) t[i] = MM<CD>::k16(z[i], ident, zero);
+#pragma unroll
+    for (int i = 0; i < N; i++) out[i] = mm_round4<CD, false>(t[i]);
+#pragma unroll
+    for (int i = 0; i < D; i++) __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);          // MFMA
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);                                  // VALU: the two packed conversions
+        if (i + D < N) __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
 template <int CD>
 __device__ __forceinline__ s4v mm_identity_frag(int lane) {
     s4v r;
