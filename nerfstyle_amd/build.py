@@ -16,7 +16,7 @@ ARCH = 'gfx950'
 SOURCES = ['raymarch.hip', 'raymarch_infer.hip', 'ray_util.hip', 'composite.hip', 'occupancy.hip', 'sample_order.hip', 'gridenc.hip', 'field.hip', 'render_infer.hip', 'field_bwd.hip', 'field_bwd_gout.hip', 'table_scatter.hip', 'mlp.hip',
            'optim.hip', 'matting.hip']
 # MFMA destinations in VGPRs (no AGPR round trip for results that VALU code consumes next): the forwards, and the GOUT backward,
-# whose 240 weight-gradient accumulators are pinned to AGPRs by inline assembly instead (field_bwd.h)
+# whose 240 weight-gradient accumulators are pinned to AGPRs by inline assembly instead (field_bwd_gout.hip)
 EXTRA_FLAGS = {'field.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'render_infer.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'field_bwd_gout.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form']}

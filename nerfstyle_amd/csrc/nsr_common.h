@@ -98,4 +98,21 @@ __device__ __forceinline__ void nsr_grid_locate(float x, uint32_t resolution, in
     cell = (uint32_t)c;
     frac = p - c;
 }
+
+// Launches kernel K with `lds` bytes of dynamic LDS, for kernels that want more than the default limit: the limit is raised
+// to `lds_max` once per device and kernel (idempotent, so a race is harmless).  Later calls are then free of non-stream API
+// calls, e.g. while the caller captures a hipGraph.
+template <auto K, typename Args>
+static int nsr_launch_lds(size_t lds_max, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &args) {
+    static bool attr_set[64] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (!attr_set[dev & 63]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess)
+            return NSR_ERR_LAUNCH;
+        attr_set[dev & 63] = true;
+    }
+    hipLaunchKernelGGL(K, grid, block, lds, s, args);
+    return nsr_launch_status();
+}
 #endif

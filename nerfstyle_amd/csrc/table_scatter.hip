@@ -395,14 +395,6 @@ int nsr_table_scatter_launch(const NsrLevel *levels, const float *bmin, const fl
     for (int i = 0; i < 3; i++) { a.bmin[i] = bmin[i]; a.bsize[i] = bsize[i]; }
     a.td = td; a.tc = tc;
     const size_t lds = 16 * sizeof(NsrLevel) + (TS_THREADS / 64) * ts_wave_bytes(a.lat_slots);
-    static bool attr_set[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_set[dev & 63]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_table_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, 65536) != hipSuccess)
-            return NSR_ERR_LAUNCH;
-        attr_set[dev & 63] = true;
-    }
     if (lds > 65536) return NSR_ERR_UNSUPPORTED;
     // 16 workgroups per CU (4 096 in all), although only 3-4 are resident at a time: the cost of a run of tiles depends on
     // how often its samples change block, and with one workgroup per resident slot the slowest run decides the launch
@@ -411,6 +403,5 @@ int nsr_table_scatter_launch(const NsrLevel *levels, const float *bmin, const fl
     const uint32_t ntiles = (M + 15) / 16;
     if (nblocks > (ntiles + 3) / 4) nblocks = (ntiles + 3) / 4;
     if (nblocks == 0) nblocks = 1;
-    hipLaunchKernelGGL(k_table_scatter, dim3(nblocks), dim3(TS_THREADS), lds, s, a);
-    return nsr_launch_status();
+    return nsr_launch_lds<k_table_scatter>(65536, dim3(nblocks), dim3(TS_THREADS), lds, s, a);
 }

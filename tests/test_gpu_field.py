@@ -264,8 +264,8 @@ def test_field_backward(O, dev, dt, table_dtype):
 @pytest.mark.parametrize('min_res,sorted_walk', [(16, False), (2, False), (16, True), (2, True)])
 def test_field_backward_run_tracker_on_ray_structured_samples(O, dev, min_res, sorted_walk):
     """The backward's scatter keeps the open run of every (level, corner) in registers along CONSECUTIVE
-    samples and hands runs over when a sample moves one cell along one axis (field_bwd.hip,
-    field_scatter_seq).  Random points never exercise that, so: samples marching along rays with steps from
+    samples and hands runs over when a sample moves one cell along one axis (k_field_bwd_tracker,
+    field_scatter_seq in field_bwd.hip).  Random points never exercise that, so: samples marching along rays with steps from
     far below a fine cell to several coarse cells, axis-aligned rays in both directions (pure x / y / z
     hand-overs), samples that stand still, samples outside the box in between (dead lanes), ray ends in
     the middle of 16-sample tiles.  min_res = 2 makes the coarsest levels dense (use_hash = 0) and not a

@@ -1,8 +1,8 @@
 """The gradients-out ("GOUT") field backward against the fused run-tracker backward, region by region.
 
 Every case runs StyleTCNerf forward (saved features) + backward twice on the same parameters and inputs: with a
-`nsr_sample_order` permutation (k_field_bwd<.., GOUT = true>, whose weight-gradient MFMAs are inline-assembly blocks
-on AGPR accumulators, + k_table_scatter) and without (the tracker translation unit: builtin MFMAs only).  Both feed
+`nsr_sample_order` permutation (k_field_bwd_gout, whose weight-gradient MFMAs are inline-assembly blocks
+on AGPR accumulators, + k_table_scatter) and without (k_field_bwd_tracker: builtin MFMAs only).  Both feed
 every MFMA the same operands; what differs is the order of the fp32 sums (the walk order of the samples, and with it
 which wave accumulates which tile).  The gradient arena is compared PER REGION, not as one norm:
 
