@@ -318,7 +318,8 @@ int nsr_sample_order(const float *xyzs, uint32_t M, const int32_t *m_dev, uint32
 /* Streaming inference render (renderer.py:237-293 as ONE launch per frame): occupancy march, fused field and the inference
  * composite of nsr_composite_rays_infer in one kernel, with the ray state in registers.  No sample buffer and no capacity:
  * no ray is ever dropped, and a ray that stopped (T < T_thresh) costs nothing further.  Samples, their order and the
- * compositing arithmetic are those of nsr_march_rays_train (noises == NULL) + nsr_field_forward + nsr_composite_rays_infer.
+ * compositing arithmetic are those of nsr_march_rays_train (noises == NULL) + nsr_field_forward + nsr_composite_rays_infer
+ * (raymarching.cu:1133-1231); it is nsr_render_rays_stream below with NSR_STREAM_INFER and no optional output.
  * order: optional device [N] u32, the ray handled k-th (a permutation of 0..N-1; NULL = identity) -- outputs always land in
  * the ray's own row.  weights_sum [N], depth [N], image [N, 3 + desc->num_classes] f32 are written, not accumulated; rays
  * that miss the box (near == far == FLT_MAX) or meet no occupied cell get zeros.  stats: optional device u32[2] that is
@@ -329,6 +330,31 @@ int nsr_render_rays_infer(const nsr_field_desc *desc, const void *tables, const 
                           const uint8_t *grid, float bound, float dt_gamma, uint32_t max_steps, int is_ndc, uint32_t C,
                           uint32_t H, float T_thresh, float *weights_sum, float *depth, float *image, uint32_t *stats,
                           nsr_stream_t stream);
+
+/* The streaming render with a choice of composite, and render_train's epilogue in the write-out.  One kernel, no sample
+ * buffer, no capacity; the march, the samples and their order are nsr_render_rays_infer's (no NDC).
+ *   NSR_STREAM_INFER  composite of nsr_composite_rays_infer (raymarching.cu:1133-1231): T = 1 - weights_sum, the stop test sees T
+ *                     in front of the sample, the depth parameter starts at `near`.  With every optional output NULL this IS
+ *                     nsr_render_rays_infer.
+ *   NSR_STREAM_TRAIN  composite of nsr_composite_rays_train_forward (raymarching.cu:806-879): T is a running product, the ray
+ *                     stops when T < T_thresh AFTER a sample, the depth parameter starts at 0.  Equal to nsr_march_rays_train
+ *                     (noises == NULL) + nsr_field_forward + nsr_render_train_forward up to the summation order of that
+ *                     kernel's wave scans -- except that nothing is ever dropped: the buffered path zeroes a ray whose samples
+ *                     do not fit (offset + count >= M), this one has no M.
+ * weights_sum [N], depth [N], image [N, 3 + num_classes]: the raw composite, always written.
+ * rgb_map [N,3], depth_norm [N], classes [N, num_classes]: optional, renderer.py:229-233 -- image[:, :3] + (1 - weights_sum),
+ * max(depth - near, 0) / (far - near), image[:, 3:].  All NULL, or rgb_map and depth_norm given and classes given exactly when
+ * num_classes != 0; anything else -> NSR_ERR_INVALID_ARG.  A ray that misses the box has near == far == FLT_MAX: rgb_map 1,
+ * classes 0, depth_norm 0 / 0, as nsr_render_train_forward gives.
+ * n_composited: optional device [N] i32, the samples accumulated for each ray (their sum is what this call adds to stats[0]).
+ * stats, order, C, H and the remaining contract as nsr_render_rays_infer.  composite outside the enum -> NSR_ERR_INVALID_ARG;
+ * C > 16 or num_classes > 13 -> NSR_ERR_UNSUPPORTED. */
+enum nsr_stream_composite { NSR_STREAM_INFER = 0, NSR_STREAM_TRAIN = 1 };
+int nsr_render_rays_stream(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *rays_o,
+                           const float *rays_d, const uint32_t *order, uint32_t N, const float *nears, const float *fars,
+                           const uint8_t *grid, float bound, float dt_gamma, uint32_t max_steps, uint32_t C, uint32_t H,
+                           float T_thresh, int composite, float *weights_sum, float *depth, float *image, float *rgb_map,
+                           float *depth_norm, float *classes, int32_t *n_composited, uint32_t *stats, nsr_stream_t stream);
 
 /* fp32 master tables -> f16 gather copy (the reference's `embeddings.to(torch.half)` under
  * autocast, grid.py:42-43).  n = number of scalars. */

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, 'libnsr_hip.so')
 
 NSR_F32, NSR_F16, NSR_BF16 = 0, 1, 2
 NSR_ACT_NONE, NSR_ACT_SIGMOID = 0, 1
+NSR_STREAM_INFER, NSR_STREAM_TRAIN = 0, 1
 ABI_VERSION = 6
 
 _DT = {torch.float32: NSR_F32, torch.float16: NSR_F16, torch.bfloat16: NSR_BF16}
@@ -73,6 +74,8 @@ SIGNATURES = {
     'nsr_field_forward': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
     'nsr_render_rays_infer': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, vp, vp, u32, vp, vp, vp, f32, f32, u32, i32, u32, u32,
                                     f32, vp, vp, vp, vp, vp]),
+    'nsr_render_rays_stream': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, vp, vp, u32, vp, vp, vp, f32, f32, u32, u32, u32, f32,
+                                     i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'nsr_field_backward': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     'nsr_field_backward_workspace_bytes': (u64, [u32, i32]),
     'nsr_sample_order_workspace_bytes': (u64, [u32]),

@@ -50,6 +50,9 @@ class Renderer(torch.nn.Module):
         # Inference through the streaming kernel (render_test_fused: march, field and composite in one launch, no sample
         # buffer).  Opt-in; `reference_inference_loop` still wins.
         self.fused_inference = False
+        # The no-grad training render through the same kernel with the TRAINING composite (render_train_fused): what pass 1
+        # of the deferred stylisation iteration and validation renders ask for.  Opt-in; unmeasured on the GPU so far.
+        self.fused_nograd_train = False
         self._infer_stats = None
         self._tile_orders = {}
         self.aabb = torch.tensor([-bound, -bound, -bound, bound, bound, bound], dtype=torch.float32)
@@ -203,7 +206,11 @@ class Renderer(torch.nn.Module):
 
     def render_train(self, rays: RayBatch, **kwargs):
         """renderer.py:196-235 -> (image [N,3], depth [N], classes [N,nc]).  Three stages that graph.GraphedPatchBackward
-        also drives one by one: march (sync-free), optional spatial order of the samples, shade (field + composite)."""
+        also drives one by one: march (sync-free), optional spatial order of the samples, shade (field + composite).
+        With `fused_nograd_train` set and autograd off the call is render_train_fused instead (non-NDC, all model channels)."""
+        if (self.fused_nograd_train and not torch.is_grad_enabled() and not self.cfg.use_ndc
+                and self.raymarch_channels == self.model.out_channels):
+            return self.render_train_fused(rays, dense_shape=kwargs.get('dense_shape'))
         if self.occupancy_update_due():
             self.update_state()
         mt = self.march_train(rays)
@@ -327,12 +334,7 @@ class Renderer(torch.nn.Module):
         dev = rays.origins.device
         C = self.raymarch_channels
         assert C == self.model.out_channels, 'the fused kernel composites the 3 + num_classes channels of the model'
-        order = None
-        if dense_shape is not None and dense_shape[0] * dense_shape[1] == N:
-            key = (int(dense_shape[0]), int(dense_shape[1]), str(dev))
-            order = self._tile_orders.get(key)
-            if order is None:
-                order = self._tile_orders[key] = tile_order(key[0], key[1]).to(torch.int32).to(dev)
+        order = self._tile_order(dense_shape, N, dev)
         weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
         depth = torch.empty(N, dtype=torch.float32, device=dev)
         image = torch.empty(N, C, dtype=torch.float32, device=dev)
@@ -349,9 +351,64 @@ class Renderer(torch.nn.Module):
         depth = torch.clamp(depth - nears, min=0) / (fars - nears)
         return image, depth, classes
 
+    def _tile_order(self, dense_shape, N, dev):
+        """The cached 8 x 8-tile work list of a w x h window (None when the rays are not such a window)."""
+        if dense_shape is None or dense_shape[0] * dense_shape[1] != N:
+            return None
+        key = (int(dense_shape[0]), int(dense_shape[1]), str(dev))
+        order = self._tile_orders.get(key)
+        if order is None:
+            order = self._tile_orders[key] = tile_order(key[0], key[1]).to(torch.int32).to(dev)
+        return order
+
+    @torch.no_grad()
+    def render_train_fused(self, rays: RayBatch, dense_shape=None):
+        """render_train without autograd as ONE launch (nsr_render_rays_stream, NSR_STREAM_TRAIN): the march, the fused field,
+        the TRAINING composite (running product, stop test after the sample, depth parameter from 0) and the epilogue of
+        renderer.py:229-233 in the streaming kernel -> (image [N,3], depth [N], classes [N,nc]) as the kernel wrote them.
+        Memory is proportional to the rays: no sample buffer, no capacity, and therefore the one difference from render_train:
+        that path zeroes the rays whose samples do not fit its buffer (last_call_overflowed), this one never drops a ray.
+        The occupancy bookkeeping is render_train's (update_state when due, local_step, the step-counter ring), except that
+        the ring slot receives (samples SHADED, N): what lies behind the point where a ray stopped is not counted, where the
+        march of render_train counts every emitted sample.  dense_shape: as for render_test_fused."""
+        import ctypes
+        from . import _lib as L
+        if self.cfg.use_ndc:
+            raise NotImplementedError('render_train_fused: NDC scenes render through the buffered render_train')
+        if self.occupancy_update_due():
+            self.update_state()
+        nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
+        N = rays.origins.shape[0]
+        dev = rays.origins.device
+        C = self.raymarch_channels
+        assert C == self.model.out_channels, 'the fused kernel composites the 3 + num_classes channels of the model'
+        if self.update_occ:
+            stats = self.step_counter[self.local_step % STEP_CTR_SIZE]
+            stats.zero_()
+            self.local_step += 1
+        else:
+            stats = torch.zeros(2, dtype=torch.int32, device=dev)
+        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
+        depth_raw = torch.empty(N, dtype=torch.float32, device=dev)
+        image_raw = torch.empty(N, C, dtype=torch.float32, device=dev)
+        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        classes = torch.empty(N, C - 3, dtype=torch.float32, device=dev)
+        desc = self.model._desc(self.cfg.density_scale)
+        L.check(L.lib().nsr_render_rays_stream(
+            ctypes.byref(desc), L.p(self.model._gather_tables()), L.p(self.model._mlp_flat()), L.p(rays.origins), L.p(rays.dirs),
+            L.p(self._tile_order(dense_shape, N, dev)), N, L.p(nears), L.p(fars), L.p(self.march_bitfield), float(self.bound), 0.,
+            self.cfg.max_steps, self.cascade, self.cfg.grid_size, float(self.cfg.t_thresh), L.NSR_STREAM_TRAIN, L.p(weights_sum),
+            L.p(depth_raw), L.p(image_raw), L.p(image), L.p(depth), L.p(classes) if C > 3 else None, None, L.p(stats),
+            L.stream()), 'render_rays_stream')
+        self._infer_stats = stats
+        # nothing is ever dropped: last_call_overflowed() answers False
+        self._last_counter, self._last_capacity = stats, N * self.cfg.max_steps + 1
+        return image, depth, classes
+
     def last_infer_stats(self) -> Optional[torch.Tensor]:
-        """Device tensor int32 [2] of the last render_test_fused call -- (samples shaded, rays finished) -- without a
-        synchronisation; None before the first call."""
+        """Device tensor int32 [2] of the last render_test_fused / render_train_fused call -- (samples shaded, rays finished)
+        -- without a synchronisation; None before the first call."""
         return self._infer_stats
 
     @torch.no_grad()
@@ -459,7 +516,8 @@ class Renderer(torch.nn.Module):
         if dense is None:
             dense = pix_subset is None and num_rays is None
         extra = {}
-        if not training and self.fused_inference and dense and pix_subset is None and num_rays is None:
+        fused = self.fused_nograd_train and not torch.is_grad_enabled() if training else self.fused_inference
+        if fused and dense and pix_subset is None and num_rays is None:
             extra['dense_shape'] = pixel_window(self.intr, patch, precrop_frac)[:2]
         output['rgb_map'], output['trans_map'], output['classes'] = render_fn(rays, dense=dense, **extra)
         return output

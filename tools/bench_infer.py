@@ -1,6 +1,6 @@
 """Times a full-frame inference render (render.py:97 path: Renderer.render(pose) -> render_test), the same frame through the
-training path without gradients, and through the streaming kernel (render_test_fused); prints ms, peak memory over the call
-and samples shaded / samples emitted, and the PSNR between the paths.
+training path without gradients, and through the streaming kernel with either composite (render_test_fused,
+render_train_fused); prints ms, peak memory over the call and samples shaded / samples emitted, and the PSNR between the paths.
 
     python tools/bench_infer.py [scale] [--density-scale S] [--cap K] [--reps R]
 
@@ -37,8 +37,10 @@ pose = torch.tensor(poses[0], device=dev)
 print('density_scale {}  buffered paths: {} samples per ray'.format(args.density_scale, args.cap))
 imgs = {}
 emitted = None
-for name, training, fused in (('render_test', False, False), ('render_train(no_grad)', True, False), ('render_test_fused', False, True)):
-    r.fused_inference = fused
+for name, training, fused in (('render_test', False, False), ('render_train(no_grad)', True, False), ('render_test_fused', False, True),
+                              ('render_train_fused(no_grad)', True, True)):
+    r.fused_inference = fused and not training
+    r.fused_nograd_train = fused and training
     with torch.no_grad():
         out = r.render(pose, None, training=training)
         torch.cuda.synchronize()
@@ -51,7 +53,7 @@ for name, training, fused in (('render_test', False, False), ('render_train(no_g
     ms = (time.perf_counter() - t0) / args.reps * 1e3
     peak = torch.cuda.max_memory_allocated() - before
     note = ''
-    if training:
+    if training and not fused:
         emitted = int(r._last_counter[0])
         note = '  emitted {} samples{}'.format(emitted, ' (buffer overflowed: rays dropped)' if emitted >= r._last_capacity else '')
     elif fused:
@@ -68,6 +70,9 @@ def psnr(a, b):
     return -10 * np.log10(max(float(((a - b) ** 2).mean()), 1e-12))
 
 
+print('PSNR(render_train vs render_train_fused) = {:.1f} dB, max |diff| {:.2e}'.format(
+    psnr(imgs['render_train(no_grad)'], imgs['render_train_fused(no_grad)']),
+    float((imgs['render_train(no_grad)'] - imgs['render_train_fused(no_grad)']).abs().max())))
 print('PSNR(render_test vs render_train) = {:.1f} dB'.format(psnr(imgs['render_test'], imgs['render_train(no_grad)'])))
 print('PSNR(render_test vs render_test_fused) = {:.1f} dB, max |diff| {:.2e}'.format(
     psnr(imgs['render_test'], imgs['render_test_fused']), float((imgs['render_test'] - imgs['render_test_fused']).abs().max())))
