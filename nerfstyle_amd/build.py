@@ -20,7 +20,7 @@ SOURCES = ['raymarch.hip', 'raymarch_infer.hip', 'ray_util.hip', 'composite.hip'
 EXTRA_FLAGS = {'field.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'render_infer.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'field_bwd_gout.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form']}
-HEADERS = ['nsr_common.h', 'rm_util.h', 'rm_probe.h', 'table_scatter.h', 'mfma_tiles.h', 'field_common.h', 'field_bwd.h',
+HEADERS = ['nsr_common.h', 'rm_util.h', 'rm_probe.h', 'table_scatter.h', 'lattice.h', 'mfma_tiles.h', 'field_common.h', 'field_bwd.h',
            os.path.join('..', '..', 'include', 'nsr.h')]
 FLAGS = ['-O3', '-fPIC', '-std=c++17', '--offload-arch=' + ARCH, '-Wall', '-Wno-unused-function']
 

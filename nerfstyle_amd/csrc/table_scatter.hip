@@ -31,6 +31,7 @@
 // corners of a row that share a line leave as one request (lat_flush_level).  Requests per sample on the bench frame,
 // model and counter: DESIGN.md, "(r4) requests per sample"; tools/sorted_scatter_sim.py is the model.
 #include "field_common.h"
+#include "lattice.h"
 #include "table_scatter.h"
 
 
@@ -38,66 +39,14 @@ __device__ __forceinline__ bool seq_nonzero(const float4 &v) {
     return ((__float_as_uint(v.x) | __float_as_uint(v.y) | __float_as_uint(v.z) | __float_as_uint(v.w)) << 1) != 0u;
 }
 
-// nsr_grid_row for style 0 with the cheap cases taken out (the level is wave-uniform here): a power-of-two table is
-// masked, a dense level needs neither 32-bit multiplies (index < 2^19) nor the modulo (index < (res + 1)^3 <= size).
-__device__ __forceinline__ uint32_t lat_row(const NsrLevel &lv, uint32_t x, uint32_t y, uint32_t z) {
-    if (lv.use_hash) {
-        const uint32_t index = x ^ (y * 2654435761u) ^ (z * 805459861u);
-        if ((lv.size & (lv.size - 1u)) == 0u) return index & (lv.size - 1u);
-        const uint32_t t = __umulhi(lv.magic, index);
-        const uint32_t q = (t + ((index - t) >> lv.sh1)) >> lv.sh2;
-        return index - q * lv.size;
-    }
-    return __umul24(x, lv.mul[0]) + __umul24(y, lv.mul[1]) + __umul24(z, lv.mul[2]);
-}
-
-struct LatGeom {
-    uint16_t base[16];      // first slot of the level's lattice
-    uint8_t S[16];          // corners per axis
-    uint8_t shift[16];      // the level's lattice is anchored at the origin of the 2^shift-block group the walk is in
-};
 constexpr int TS_THREADS = 256;     // measured on the bench frame: 64 -> 35.6 ms, 128 -> 30.6, 256 -> 29.4 (A + B)
 // float4 slots per wave, from the 64 KB of LDS a workgroup may ask for: level table + per wave (256 B + 16 B per slot), the
 // slot count rounded up to 64 (4 waves: 960).  nsr_table_scatter_supported() and the launch share THIS bound, so a grid is
 // rejected before anything is launched or never (round 2 rejected totals of 961..1024 after the MLP backward had run)
 constexpr int LAT_MAX_SLOTS = (int)(((65536 - 16 * sizeof(NsrLevel)) / (TS_THREADS / 64) - 256) / 16 / 64 * 64);
-constexpr int LAT_KEY_BITS = 10;                     // must match nsr_sample_order's quantisation
-constexpr uint32_t LAT_NONE = 0xFFFFFFFFu;
 struct LatState {
     uint32_t b0, b1, b2;     // anchor cell of this lane's level (LAT_NONE: nothing accumulated yet)
 };
-
-// corners per axis of a lattice that covers every cell a group of 2^shift blocks (each 1/1024 wide) can touch on a level:
-// the group spans e = res * 2^shift / 1024 cells, i.e. at most floor(e) + 2 of them (exactly e when the cells tile it)
-static uint32_t lat_corners(uint32_t res, uint32_t shift) {
-    const uint64_t span = (uint64_t)res << shift, blocks = 1u << LAT_KEY_BITS;
-    const uint32_t cells = (span % blocks == 0) ? (uint32_t)(span / blocks) : (uint32_t)(span / blocks) + 2u;
-    return cells + 1u;
-}
-
-// Host: lattice geometry.  The walk is in Morton order of the blocks, so the 8 (64, ...) blocks of an aligned group follow
-// one another; a level whose cells are larger than a block is anchored at the GROUP's origin as long as that costs no
-// lattice slots (a group narrower than a cell still touches at most 2 cells per axis: 3^3 corners) -- its lattice then
-// survives the block changes inside the group and is flushed that much less often (bench frame, backward pair: 23.5 ->
-// 22.3 ms).  Levels finer than that keep the block as their anchor: paying a 4^3 lattice for a group of two on the levels
-// with cells of 1 - 2 blocks was measured and lost (22.7 ms: more slots to scan per flush, more LDS).
-static bool lat_geometry(const NsrLevel *lv, LatGeom &g) {
-    uint32_t total = 0;
-    for (int l = 0; l < 16; l++) {
-        const uint32_t res = lv[l].resolution;
-        uint32_t shift = 0, S = lat_corners(res, 0);
-        while (shift < (uint32_t)LAT_KEY_BITS && lat_corners(res, shift + 1) <= (S > 3u ? S : 3u)) shift++;   // free
-        // (letting the 1, 2 or 3 finest levels pay a larger lattice for a group of 2^3 blocks: bench frame, backward pair
-        // 22.14, 22.09, 22.91 ms against 22.2 -- nothing to gain)
-        S = lat_corners(res, shift) > S ? lat_corners(res, shift) : S;
-        if (S < 2u || S > 6u) return false;
-        g.S[l] = (uint8_t)S;
-        g.shift[l] = (uint8_t)shift;
-        g.base[l] = (uint16_t)total;
-        total += S * S * S;
-    }
-    return ((total + 63u) & ~63u) <= (uint32_t)LAT_MAX_SLOTS;
-}
 
 // Flushes the planes x < xl of level l's lattice, anchored at cell (b0, b1, b2), and moves the planes x >= xl down to x - xl
 // (xl, like the anchor, is wave-uniform; xl == S: the whole lattice leaves and is cleared, nothing moves).
@@ -376,14 +325,14 @@ k_table_scatter(TableScatterArgs a) {
 
 bool nsr_table_scatter_supported(const NsrLevel *lv) {
     LatGeom g;
-    return lat_geometry(lv, g);
+    return lat_geometry(lv, g, (uint32_t)LAT_MAX_SLOTS);
 }
 
 int nsr_table_scatter_launch(const NsrLevel *levels, const float *bmin, const float *bsize, const float *xyzs, const uint32_t *perm,
                              const int32_t *m_dev, uint32_t M, const void *gin, float *grad_tables, int td, int tc, hipStream_t s) {
     TableScatterArgs a;
     LatGeom g;
-    if (!lat_geometry(levels, g)) return NSR_ERR_UNSUPPORTED;
+    if (!lat_geometry(levels, g, (uint32_t)LAT_MAX_SLOTS)) return NSR_ERR_UNSUPPORTED;
     uint32_t total = 0;
     for (int l = 0; l < 16; l++) {
         a.lv[l] = levels[l];

@@ -15,7 +15,14 @@ the touched corners 16 slots per atomic instruction) and counts 64-byte atomic r
   (c)  the same on whichever single axis moved.
 A wave walks `samples_per_wave` consecutive samples (the bench frame: 48.6 M samples over 16 384 waves = 186 tiles) and
 flushes everything at its end.  Not modelled: samples whose gradient is zero (they touch nothing), the rays outside
-the patch that share its blocks, and the order in which the memory side sees the requests."""
+the patch that share its blocks, and the order in which the memory side sees the requests.
+
+`python tools/sorted_scatter_sim.py gather [patch_edge_px=64] [tile_stride=4] [tiles_per_workgroup=1483]` models the forward's
+lattice gather (field.hip, k_field_fwd_lat) with the same geometry on a 5 x 3 grid of dense patches over the frame: a wave
+takes every `tile_stride`-th 16-sample tile of its workgroup's run, anchors every level at the block (group) of the tile's
+first sample and refills a level's S^3 lattice of table rows when that anchor differs from the one it holds.  Per level and in
+all: (a) rows fetched by fills per sample, (b) the share of (sample, level) pairs whose cell lies inside the lattice, (c) fills
+per tile."""
 import os
 import sys
 
@@ -193,7 +200,60 @@ def main_lattice(argv):
     print('(c) takes a further %.1f %% of the requests (b) leaves' % (100 * (tot['b'] - tot['c']) / tot['b']))
 
 
+def gather_model(u, stride, tpb):
+    """per level: [rows fetched by fills, (sample, level) pairs inside the lattice, fills], and the tile count"""
+    pls = O.per_level_scale_from_cfg()
+    res = [int(r) for r in O.grid_resolutions(16, O.grid_S(pls), 16)]
+    geom = lat_geometry(res)
+    M = len(u)
+    q = np.clip(np.floor(u * np.float32(1024)), 0, 1023).astype(np.int64)
+    order = np.argsort(morton3(np.maximum(q - 512, 0)), kind='stable')
+    u, q = u[order], q[order]
+    nt = (M + 15) // 16
+    tile_of = np.arange(M) // 16
+    first = np.arange(nt) * 16                                  # every marched sample is live
+    # the tile a wave handled before tile t: t - stride inside the same workgroup run, none at its start
+    t = np.arange(nt)
+    prev = np.where((t % tpb) >= stride, t - stride, -1)
+    out = np.zeros((16, 3))
+    for l in range(16):
+        S, shift = geom[l]
+        o = ((q[first] >> shift) << shift).astype(np.float32) * np.float32(1.0 / 1024)
+        anchor = np.minimum(np.floor(o * np.float32(res[l])), res[l] - 1).astype(np.int64)       # [nt, 3]
+        fill = (prev < 0) | (anchor != anchor[np.maximum(prev, 0)]).any(1)
+        rel = level_cells(u, res[l]) - anchor[tile_of]
+        inside = ((rel >= 0) & (rel < S - 1)).all(1)
+        out[l] = [fill.sum() * S ** 3, inside.sum(), fill.sum()]
+    return out, nt, M, geom, res
+
+
+def main_gather(argv):
+    edge = int(argv[0]) if len(argv) > 0 else 64
+    stride = int(argv[1]) if len(argv) > 1 else 4
+    tpb = int(argv[2]) if len(argv) > 2 else 1483
+    tot, ntiles, samples, geom, res = np.zeros((16, 3)), 0, 0, None, None
+    for j in range(3):
+        for i in range(5):
+            xyz, _ = dense_patch_samples(edge, (1008 - edge) * i // 4, (756 - edge) * j // 2)
+            if len(xyz) < 16:
+                continue
+            t, nt, M, geom, res = gather_model(O.encoder_inputs(xyz, 2.0).astype(np.float32), stride, tpb)
+            tot, ntiles, samples = tot + t, ntiles + nt, samples + M
+    print('patches of %d^2 rays, %d samples, %d tiles, tile stride %d, %d tiles per workgroup' % (edge, samples, ntiles, stride, tpb))
+    print('| level | res | S | shift | (a) rows fetched by fills / sample | (b) inside the lattice | (c) fills / tile |')
+    print('|---|---|---|---|---|---|---|')
+    for l in range(16):
+        print('| %d | %d | %d | %d | %.3f | %.4f | %.4f |' % (l, res[l], geom[l][0], geom[l][1], tot[l, 0] / samples, tot[l, 1] / samples,
+                                                            tot[l, 2] / ntiles))
+    for name, lv in (('0-7', range(8)), ('8-11', range(8, 12)), ('12-15', range(12, 16)), ('all', range(16))):
+        lv = list(lv)
+        print('| %s | | | | %.3f | %.4f | %.4f |' % (name, tot[lv, 0].sum() / samples, tot[lv, 1].sum() / samples / len(lv),
+                                                   tot[lv, 2].sum() / ntiles))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'gather':
+        return main_gather(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == 'lattice':
         return main_lattice(sys.argv[2:])
     edge = int(sys.argv[1]) if len(sys.argv) > 1 else 96
