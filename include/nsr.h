@@ -203,7 +203,8 @@ int nsr_grid_resolutions(uint32_t L, float S, uint32_t H, uint32_t *res_out);
  * offsets HOST [L+1] i32 (the reference passes a device tensor; it is 17 ints);
  * outputs of emb_dtype: layout [L,B,C] when out_blc == 0 (the reference kernel's) or
  * [B,L*C] when out_blc != 0 (what grid.py:58 returns after its permute+reshape copy).
- * calc_grad_inputs is not supported (never true on this path) -> NSR_ERR_UNSUPPORTED.
+ * calc_grad_inputs != 0 -> NSR_ERR_UNSUPPORTED: no dy_dx buffer is written here; the input gradient comes from
+ * nsr_grid_encode_input_backward, which recomputes the partials.
  * C in {1,2,4,8} like the reference; L <= 32. */
 int nsr_grid_encode_forward(const float *inputs, const void *embeddings, int emb_dtype,
                             const int32_t *offsets, void *outputs, uint32_t B, uint32_t D, uint32_t C,
@@ -218,6 +219,17 @@ int nsr_grid_encode_backward(const void *grad, int grad_dtype, const float *inpu
                              const int32_t *offsets, float *grad_embeddings, uint32_t B, uint32_t D,
                              uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
                              int align_corners, uint32_t style, int grad_blc, nsr_stream_t stream);
+
+/* replaces the calc_grad_inputs half of the reference (dy_dx of gridencoder.cu:189-234 + kernel_input_backward :331-357)
+ * without a dy_dx [B, L*D*C] buffer: one thread per sample recomputes the partials from the table and writes
+ * grad_inputs [B,3] f32 = sum over levels (ascending) and channels of grad * d output / d input.  No atomics: two calls give
+ * the same bits.  grad of grad_dtype (NSR_F32|NSR_F16) in the layout grad_blc selects, embeddings of emb_dtype
+ * (NSR_F32|NSR_F16), offsets HOST [L+1]; rows whose input is outside [0,1] (gridencoder.cu:121-130) or NaN get zeros.
+ * D != 3 -> NSR_ERR_UNSUPPORTED; C in {1,2,4,8}; L <= 32. */
+int nsr_grid_encode_input_backward(const void *grad, int grad_dtype, const float *inputs, const void *embeddings,
+                                   int emb_dtype, const int32_t *offsets, float *grad_inputs, uint32_t B, uint32_t D,
+                                   uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners,
+                                   uint32_t style, int grad_blc, nsr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * tcnn.Network replacement: bias-free fully fused MLP on MFMA
@@ -277,6 +289,17 @@ typedef struct nsr_field_desc {
 int nsr_field_forward(const nsr_field_desc *desc, const void *tables, const float *mlp_params,
                       const float *xyzs, uint32_t M, const int32_t *m_dev, float *sigmas, float *rgbs,
                       void *feats, const uint32_t *perm, nsr_stream_t stream);
+
+/* Density and its gradient with respect to the world position, forward mode, one launch (csrc/field_normal.hip): the
+ * density encoder's features and their three spatial tangents go through the density net together; nothing is saved, no
+ * atomics.  Reads the density half of `tables` only.  sigmas [M] f32 or NULL: bit-identical to nsr_field_forward with
+ * rgbs == NULL.  grads [M,3] f32 = density_scale * exp(clamp(logit,-15,15)) * d logit / d x (the trunc_exp rule of the
+ * backward); with normalize != 0 the unit normal -grad / max(|grad|, 1e-20) instead (a zero gradient stays a zero vector).
+ * Samples whose position is NaN or encodes outside [0,1] get the forward's sigma and a zero gradient; slots at or past
+ * *m_dev keep their sigma and get a zero gradient.  Capture-safe, no host read.  L != 16 -> NSR_ERR_UNSUPPORTED. */
+int nsr_field_density_gradient(const nsr_field_desc *desc, const void *tables, const float *mlp_params,
+                               const float *xyzs, uint32_t M, const int32_t *m_dev, float *sigmas, float *grads,
+                               int normalize, nsr_stream_t stream);
 
 /* grad_sigmas [M], grad_rgbs [M,3+nc] f32.  Recomputes the forward (nothing saved), then
  * back-propagates: trunc_exp' = exp(clamp(logit,-15,15)) (tcnn_nerf.py:62-66), sigmoid', ReLU

@@ -68,10 +68,13 @@ SIGNATURES = {
                                       i32, u32, i32, u32, i32, vp]),
     'nsr_grid_encode_backward': (i32, [vp, i32, vp, ctypes.POINTER(ctypes.c_int32), vp, u32, u32, u32, u32, f32, u32,
                                        u32, i32, u32, i32, vp]),
+    'nsr_grid_encode_input_backward': (i32, [vp, i32, vp, vp, i32, ctypes.POINTER(ctypes.c_int32), vp, u32, u32, u32, u32, f32,
+                                             u32, u32, i32, u32, i32, vp]),
     'nsr_mlp_param_count': (u32, [u32, u32, u32, u32]),
     'nsr_mlp_forward': (i32, [vp, vp, u32, u32, u32, u32, u32, i32, i32, vp, vp]),
     'nsr_mlp_backward': (i32, [vp, vp, vp, vp, u32, u32, u32, u32, u32, i32, i32, vp, vp, vp]),
     'nsr_field_forward': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]),
+    'nsr_field_density_gradient': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, i32, vp]),
     'nsr_render_rays_infer': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, vp, vp, u32, vp, vp, vp, f32, f32, u32, i32, u32, u32,
                                     f32, vp, vp, vp, vp, vp]),
     'nsr_render_rays_stream': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, vp, vp, u32, vp, vp, vp, f32, f32, u32, u32, u32, f32,

@@ -104,6 +104,62 @@ k_grid_bwd(const T *__restrict__ grad, const float *__restrict__ inputs, float *
     }
 }
 
+// Input gradient (the reference: dy_dx written by the forward, gridencoder.cu:189-234, reduced by kernel_input_backward,
+// :331-357).  Here nothing is stored: one thread per sample recomputes the partials of every level from the table and forms
+// grad_inputs[b, d] = sum over levels and channels of grad * dy/dx, levels in ascending order -- no atomics, so two runs are
+// bit-identical.  Inputs outside [0,1] (:121-130) and NaN give zeros.
+template <typename T, typename TG, int C>
+__global__ void __launch_bounds__(256)
+k_grid_input_bwd(const TG *__restrict__ grad, const float *__restrict__ inputs, const T *__restrict__ grid,
+                 float *__restrict__ grad_inputs, uint32_t B, uint32_t L, NsrLevels levels, int align_corners, uint32_t style,
+                 int grad_blc) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float x0 = inputs[(size_t)b * 3 + 0], x1 = inputs[(size_t)b * 3 + 1], x2 = inputs[(size_t)b * 3 + 2];
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (x0 >= 0 && x0 <= 1 && x1 >= 0 && x1 <= 1 && x2 >= 0 && x2 <= 1) {
+        for (uint32_t level = 0; level < L; level++) {
+            const NsrLevel lv = levels.lv[level];
+            const TG *gp = grad_blc ? grad + ((size_t)b * L + level) * C : grad + ((size_t)level * B + b) * C;
+            const float scale = (float)(lv.resolution - (align_corners ? 0u : 1u));
+            float f[3];
+            uint32_t g[3];
+            nsr_grid_locate(x0, lv.resolution, align_corners, f[0], g[0]);
+            nsr_grid_locate(x1, lv.resolution, align_corners, f[1], g[1]);
+            nsr_grid_locate(x2, lv.resolution, align_corners, f[2], g[2]);
+            const T *tab = grid + (size_t)lv.offset * C;
+            // sum over channels of grad * row, per corner (idx bit d = the upper corner on axis d)
+            float gv[8];
+#pragma unroll
+            for (uint32_t idx = 0; idx < 8; idx++) {
+                const uint32_t row = nsr_grid_row(lv, g[0] + (idx & 1u), g[1] + ((idx >> 1) & 1u), g[2] + (idx >> 2), style);
+                float t = 0.0f;
+#pragma unroll
+                for (int ch = 0; ch < C; ch++) t += GeIO<TG>::ld(gp + ch) * GeIO<T>::ld(tab + (size_t)row * C + ch);
+                gv[idx] = t;
+            }
+#pragma unroll
+            for (uint32_t gd = 0; gd < 3; gd++) {
+                const uint32_t d0 = gd == 0 ? 1u : 0u, d1 = gd == 2 ? 1u : 2u;     // the two other axes, ascending (:206-216)
+                float r = 0.0f;
+#pragma unroll
+                for (uint32_t idx = 0; idx < 4; idx++) {
+                    const uint32_t b0 = idx & 1u, b1 = idx >> 1;
+                    float w = scale;
+                    w *= b0 ? f[d0] : 1 - f[d0];
+                    w *= b1 ? f[d1] : 1 - f[d1];
+                    const uint32_t left = (b0 << d0) | (b1 << d1);
+                    r += w * (gv[left | (1u << gd)] - gv[left]);
+                }
+                acc[gd] += r;
+            }
+        }
+    }
+    grad_inputs[(size_t)b * 3 + 0] = acc[0];
+    grad_inputs[(size_t)b * 3 + 1] = acc[1];
+    grad_inputs[(size_t)b * 3 + 2] = acc[2];
+}
+
 __global__ void k_cast_f32_f16(const float *__restrict__ src, _Float16 *__restrict__ dst, uint64_t n) {
     // 8 scalars per thread per step: two 16-byte loads, one 16-byte store
     const uint64_t n8 = n / 8;
@@ -147,6 +203,20 @@ static int launch_bwd(const void *grad, const float *inputs, float *gg, uint32_t
     return nsr_launch_status();
 }
 
+template <typename T, typename TG>
+static int launch_input_bwd(const void *grad, const float *inputs, const void *emb, float *gi, uint32_t B, uint32_t C, uint32_t L,
+                            const NsrLevels &lv, int align_corners, uint32_t style, int grad_blc, hipStream_t s) {
+    const dim3 grid(nsr_div_up(B, 256)), block(256);
+    switch (C) {
+        case 1: hipLaunchKernelGGL((k_grid_input_bwd<T, TG, 1>), grid, block, 0, s, (const TG *)grad, inputs, (const T *)emb, gi, B, L, lv, align_corners, style, grad_blc); break;
+        case 2: hipLaunchKernelGGL((k_grid_input_bwd<T, TG, 2>), grid, block, 0, s, (const TG *)grad, inputs, (const T *)emb, gi, B, L, lv, align_corners, style, grad_blc); break;
+        case 4: hipLaunchKernelGGL((k_grid_input_bwd<T, TG, 4>), grid, block, 0, s, (const TG *)grad, inputs, (const T *)emb, gi, B, L, lv, align_corners, style, grad_blc); break;
+        case 8: hipLaunchKernelGGL((k_grid_input_bwd<T, TG, 8>), grid, block, 0, s, (const TG *)grad, inputs, (const T *)emb, gi, B, L, lv, align_corners, style, grad_blc); break;
+        default: return NSR_ERR_UNSUPPORTED;
+    }
+    return nsr_launch_status();
+}
+
 extern "C" {
 
 int nsr_grid_resolutions(uint32_t L, float S, uint32_t H, uint32_t *res_out) {
@@ -180,6 +250,24 @@ int nsr_grid_encode_backward(const void *grad, int grad_dtype, const float *inpu
     nsr_fill_levels(&lv, offsets, L, S, H, gridtype);
     if (grad_dtype == NSR_F32) return launch_bwd<float>(grad, inputs, grad_embeddings, B, C, L, lv, align_corners, style, grad_blc, (hipStream_t)stream);
     if (grad_dtype == NSR_F16) return launch_bwd<_Float16>(grad, inputs, grad_embeddings, B, C, L, lv, align_corners, style, grad_blc, (hipStream_t)stream);
+    return NSR_ERR_UNSUPPORTED;
+}
+
+int nsr_grid_encode_input_backward(const void *grad, int grad_dtype, const float *inputs, const void *embeddings, int emb_dtype,
+                                   const int32_t *offsets, float *grad_inputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                   float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t style, int grad_blc,
+                                   nsr_stream_t stream) {
+    if (B == 0) return NSR_OK;
+    if (D != 3) return NSR_ERR_UNSUPPORTED;
+    NSR_CHECK_PTR(grad); NSR_CHECK_PTR(inputs); NSR_CHECK_PTR(embeddings); NSR_CHECK_PTR(offsets); NSR_CHECK_PTR(grad_inputs);
+    if (L == 0 || L > NSR_MAX_LEVELS || gridtype > 1) return NSR_ERR_INVALID_ARG;
+    NsrLevels lv;
+    nsr_fill_levels(&lv, offsets, L, S, H, gridtype);
+    hipStream_t s = (hipStream_t)stream;
+    if (emb_dtype == NSR_F32 && grad_dtype == NSR_F32) return launch_input_bwd<float, float>(grad, inputs, embeddings, grad_inputs, B, C, L, lv, align_corners, style, grad_blc, s);
+    if (emb_dtype == NSR_F32 && grad_dtype == NSR_F16) return launch_input_bwd<float, _Float16>(grad, inputs, embeddings, grad_inputs, B, C, L, lv, align_corners, style, grad_blc, s);
+    if (emb_dtype == NSR_F16 && grad_dtype == NSR_F32) return launch_input_bwd<_Float16, float>(grad, inputs, embeddings, grad_inputs, B, C, L, lv, align_corners, style, grad_blc, s);
+    if (emb_dtype == NSR_F16 && grad_dtype == NSR_F16) return launch_input_bwd<_Float16, _Float16>(grad, inputs, embeddings, grad_inputs, B, C, L, lv, align_corners, style, grad_blc, s);
     return NSR_ERR_UNSUPPORTED;
 }
 

@@ -2,10 +2,11 @@
 with the same constructor, parameters (`embeddings`, buffer `offsets`) and `forward(inputs,
 bound=1, style=0)`; `grid_encode` with the same argument list as grid.py:19-25.
 
-Backed by nsr_grid_encode_forward / nsr_grid_encode_backward.  Differences from the reference
-(all documented in include/nsr.h): outputs are written directly as [B, L*C] (no permute copy),
-the backward accumulates in fp32 whatever the table type, calc_grad_inputs is unsupported (it is
-never requested on this path: positions never require grad).
+Backed by nsr_grid_encode_forward / nsr_grid_encode_backward / nsr_grid_encode_input_backward.
+Differences from the reference (all documented in include/nsr.h): outputs are written directly as
+[B, L*C] (no permute copy), the backward accumulates in fp32 whatever the table type, and with
+calc_grad_inputs the forward writes no dy_dx [B, L*D*C] buffer: it saves the table it gathered
+from and the backward recomputes the partials (fp32, deterministic).
 """
 import ctypes
 
@@ -30,8 +31,7 @@ class _grid_encode(Function):
                 calc_grad_inputs=False, gridtype=0, align_corners=False, style=0):
         """grid.py:19-66.  inputs [B,3] float in [0,1]; embeddings [rows,C]; offsets [L+1] int
         (any device: it is 17 ints and is read on the host).  Returns [B, L*C]."""
-        if calc_grad_inputs:
-            raise RuntimeError('grid_encode: calc_grad_inputs is not supported (never used on this path)')
+        ctx.in_dtype = inputs.dtype
         inputs = inputs.detach().to(torch.float32).contiguous()
         B, D = inputs.shape
         Lv = offsets.shape[0] - 1
@@ -47,7 +47,9 @@ class _grid_encode(Function):
         L.check(L.lib().nsr_grid_encode_forward(
             L.p(inputs), L.p(emb), L.dt(emb.dtype), off_p, L.p(outputs), B, D, C, Lv, S, H, 0, int(gridtype),
             int(bool(align_corners)), int(style), 1, L.stream()), 'grid_encode_forward')
-        ctx.save_for_backward(inputs)
+        # calc_grad_inputs (grid.py:48-49 allocates dy_dx here): keep the table the forward gathered from instead
+        ctx.save_for_backward(inputs, emb if calc_grad_inputs else None)
+        ctx.calc_grad_inputs = bool(calc_grad_inputs)
         ctx.off_np = off_np
         ctx.dims = [B, D, C, Lv, S, H, gridtype, emb.shape[0]]
         ctx.align_corners = align_corners
@@ -58,7 +60,7 @@ class _grid_encode(Function):
     @staticmethod
     def backward(ctx, grad):
         """grid.py:68-97"""
-        (inputs,) = ctx.saved_tensors
+        inputs, emb = ctx.saved_tensors
         B, D, C, Lv, S, H, gridtype, rows = ctx.dims
         grad = grad.contiguous()
         if grad.dtype not in (torch.float32, torch.float16):
@@ -68,7 +70,14 @@ class _grid_encode(Function):
         L.check(L.lib().nsr_grid_encode_backward(
             L.p(grad), L.dt(grad.dtype), L.p(inputs), off_p, L.p(grad_embeddings), B, D, C, Lv, S, H, int(gridtype),
             int(bool(ctx.align_corners)), int(ctx.style), 1, L.stream()), 'grid_encode_backward')
-        return None, grad_embeddings.to(ctx.emb_dtype), None, None, None, None, None, None, None
+        grad_inputs = None
+        if ctx.calc_grad_inputs:                                                             # grid.py:84-95
+            grad_inputs = torch.empty(B, D, dtype=torch.float32, device=inputs.device)
+            L.check(L.lib().nsr_grid_encode_input_backward(
+                L.p(grad), L.dt(grad.dtype), L.p(inputs), L.p(emb), L.dt(emb.dtype), off_p, L.p(grad_inputs), B, D, C, Lv, S, H,
+                int(gridtype), int(bool(ctx.align_corners)), int(ctx.style), 1, L.stream()), 'grid_encode_input_backward')
+            grad_inputs = grad_inputs.to(ctx.in_dtype)
+        return grad_inputs, grad_embeddings.to(ctx.emb_dtype), None, None, None, None, None, None, None
 
 
 grid_encode = _grid_encode.apply
@@ -123,5 +132,5 @@ class GridEncoder(nn.Module):
         prefix_shape = list(inputs.shape[:-1])
         inputs = inputs.view(-1, self.input_dim)
         outputs = grid_encode(inputs, self.embeddings, self.offsets, self.per_level_scale, self.base_resolution,
-                              False, self.gridtype_id, self.align_corners, style)
+                              inputs.requires_grad, self.gridtype_id, self.align_corners, style)
         return outputs.view(prefix_shape + [self.output_dim])

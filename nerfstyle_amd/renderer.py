@@ -266,6 +266,36 @@ class Renderer(torch.nn.Module):
                                                  self.cfg.t_thresh)
         return image, depth, classes
 
+    @torch.no_grad()
+    def render_normals(self, rays: RayBatch) -> Dict[str, torch.Tensor]:
+        """Geometry of the reconstruction: {'normal_map' [N,3], 'weights_sum' [N], 'depth' [N]}.  The buffered march of
+        render_train (so NDC scenes are allowed), the analytic unit normal -grad sigma / |grad sigma| of every sample
+        (StyleTCNerf.density_gradient) and the training composite with the normals as a 3-channel colour.
+        normal_map = sum_i w_i n_i is NOT renormalised: its length is at most weights_sum, and shorter where the normals
+        along a ray disagree; rays that miss the box get zeros.  depth is render_train's.  No occupancy bookkeeping: no
+        update_state, and local_step and the step-counter ring stay as they are."""
+        from . import _lib as L
+        keep = (self.update_occ, getattr(self, '_last_counter', None), getattr(self, '_last_capacity', None))
+        self.update_occ = False                      # march_train then counts into a counter of its own
+        try:
+            mt = self.march_train(rays)
+        finally:
+            self.update_occ, self._last_counter, self._last_capacity = keep
+        sigmas, normals = self.model.density_gradient(mt['xyzs'], m_dev=mt['counter'], density_scale=self.cfg.density_scale,
+                                                      normalize=True)
+        N, M = mt['N'], mt['M']
+        dev = sigmas.device
+        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
+        depth_raw = torch.empty(N, dtype=torch.float32, device=dev)
+        normal_map = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        with_bg = torch.empty(N, 3, dtype=torch.float32, device=dev)      # the composite's white-background image: unused
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        L.check(L.lib().nsr_render_train_forward(
+            L.p(sigmas), L.p(normals), L.p(mt['deltas']), L.p(mt['rays_info']), L.p(mt['nears']), L.p(mt['fars']), M, N, 3,
+            float(self.cfg.t_thresh), L.p(weights_sum), L.p(depth_raw), L.p(normal_map), L.p(with_bg), L.p(depth), None,
+            L.stream()), 'render_train_forward')
+        return {'normal_map': normal_map, 'weights_sum': weights_sum, 'depth': depth}
+
     def _use_spatial_order(self, n_rays: int, dense: bool) -> bool:
         if getattr(self.model, '_spatial_scatter_unsupported', False):
             return False                 # learnt from a backward that fell back (style_nerf._field.backward)

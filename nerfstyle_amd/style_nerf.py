@@ -340,6 +340,25 @@ class StyleTCNerf(nn.Module):
         want_feats = bool(self.save_features and torch.is_grad_enabled() and self.arena.requires_grad and not sigma_only)
         return _field.apply(pts, self.arena, self, sigma_only, m_dev, density_scale, want_feats, perm)
 
+    @torch.no_grad()
+    def density_gradient(self, pts, m_dev=None, density_scale=1.0, normalize=False):
+        """(sigmas [M], grads [M,3]): the density and its gradient with respect to the world position, one fused launch in
+        forward mode (nsr_field_density_gradient).  normalize: the unit normal -grad / |grad| instead (zero where the
+        gradient is zero).  Positions outside the box or NaN, and slots at or past m_dev, get a zero gradient (the latter keep
+        an unwritten sigma, as in `field`).  NO-GRAD ONLY: neither output is attached to the autograd graph -- a loss on
+        them (Eikonal, normal consistency) would need a second-order backward through the fused kernels, which does not exist."""
+        pts = pts.detach().reshape(-1, 3).to(torch.float32).contiguous()
+        M = pts.shape[0]
+        sigmas = torch.empty(M, dtype=torch.float32, device=pts.device)
+        grads = torch.empty(M, 3, dtype=torch.float32, device=pts.device)
+        desc = self._desc(density_scale)
+        tables = self._gather_tables()
+        with profiling.timed('field_density_grad'):
+            L.check(L.lib().nsr_field_density_gradient(ctypes.byref(desc), L.p(tables), L.p(self._mlp_flat()), L.p(pts), M,
+                                                       L.p(m_dev), L.p(sigmas), L.p(grads), int(bool(normalize)), L.stream()),
+                    'field_density_gradient')
+        return sigmas, grads
+
     def sample_order(self, xyzs, m_dev=None, sort_prefix=None, out=None):
         """nsr_sample_order: Morton-order permutation of the samples [M,3] (int32 tensor [M], a uint32 bit pattern;
         written into `out` when given)."""
