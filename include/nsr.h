@@ -323,6 +323,37 @@ int nsr_field_backward(const nsr_field_desc *desc, const void *tables, const flo
  * workspace: nsr_field_backward_workspace_bytes(M, with_perm) bytes, 16-byte aligned (0 / NULL without perm). */
 uint64_t nsr_field_backward_workspace_bytes(uint32_t M, int with_perm);
 
+/* ------------------------------------------------------------------------------------------
+ * View-dependent colour (networks/style_nerf.py with use_dir = True): color2's input is cat(color1 output [16], degree-4
+ * spherical harmonics of the viewing direction [16]), its first layer 64 x 32.
+ * ------------------------------------------------------------------------------------------
+ * The encoding follows tiny-cuda-nn's SphericalHarmonics (the reference feeds (d + 1) / 2, the encoder maps back with
+ * 2u - 1 in fp32): 16 coefficients in tiny-cuda-nn's order and sign convention, written down from general knowledge of it --
+ * parity with a tiny-cuda-nn build is UNPINNED, like the MLPs'.  Inside the field the coefficients are rounded to the compute
+ * type where they enter the MFMA (the MLP contract); nsr_sh_encode returns them in fp32.
+ * mlp_params / grad_mlp of the *_dirs entry points hold nsr_field_mlp_param_count(1) = 16384 floats: the 15360 of the plain
+ * entry points at the same offsets, then color2's SH columns as a row-major [64,16] block (column j of it is column 16 + j
+ * of the reference-shaped first layer).
+ * dirs [M,3] f32 follows the sample buffers' conventions: indexed through perm like xyzs, slots at or past *m_dev ignored.
+ * Everything else is as in nsr_field_forward / nsr_field_backward; sigmas and the class channels are bit-identical to
+ * theirs.  rgbs == NULL (sigma only) never reads dirs. */
+uint32_t nsr_field_mlp_param_count(int with_dirs);
+/* Host only: 1 when a full (rgbs != NULL) forward of this descriptor with / without perm and directions runs the lattice-gather
+ * kernel (16-bit tables, perm given, lattices that fit a quarter of a CU's LDS), 0 when it runs the plain gather kernel. */
+int nsr_field_forward_uses_lattice(const nsr_field_desc *desc, int with_perm, int with_dirs);
+/* dirs [M,3] f32 -> out [M,16] f32 (16-byte aligned). */
+int nsr_sh_encode(const float *dirs, uint32_t M, float *out, nsr_stream_t stream);
+int nsr_field_forward_dirs(const nsr_field_desc *desc, const void *tables, const float *mlp_params,
+                           const float *xyzs, uint32_t M, const int32_t *m_dev, float *sigmas, float *rgbs,
+                           void *feats, const uint32_t *perm, const float *dirs, nsr_stream_t stream);
+/* The recomputed forward runs the K = 32 first layer; the SH columns' weight gradient (four more accumulator tiles, skipped
+ * with the others when grad_mlp == NULL) lands at grad_mlp + 15360.  No gradient with respect to dirs is produced. */
+int nsr_field_backward_dirs(const nsr_field_desc *desc, const void *tables, const float *mlp_params,
+                            const float *xyzs, uint32_t M, const int32_t *m_dev, const float *grad_sigmas,
+                            const float *grad_rgbs, float *grad_tables, float *grad_mlp,
+                            int train_density_table, int train_color_table, const void *feats,
+                            const uint32_t *perm, void *workspace, const float *dirs, nsr_stream_t stream);
+
 /* Spatial processing order of marched samples (no reference counterpart; see csrc/sample_order.hip): perm [M] u32 =
  * indices of the first min(m_dev[0], M) samples in Morton order of their encoder input (10 bits per axis, stable: ray
  * order inside a 4^3-finest-cell block), followed by the remaining slots in identity order.  sort_prefix <= M caps the

@@ -81,6 +81,11 @@ SIGNATURES = {
                                      i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'nsr_field_backward': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     'nsr_field_backward_workspace_bytes': (u64, [u32, i32]),
+    'nsr_field_mlp_param_count': (u32, [i32]),
+    'nsr_field_forward_uses_lattice': (i32, [ctypes.POINTER(FieldDesc), i32, i32]),
+    'nsr_sh_encode': (i32, [vp, u32, vp, vp]),
+    'nsr_field_forward_dirs': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+    'nsr_field_backward_dirs': (i32, [ctypes.POINTER(FieldDesc), vp, vp, vp, u32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     'nsr_sample_order_workspace_bytes': (u64, [u32]),
     'nsr_sample_order': (i32, [vp, u32, vp, u32, ctypes.POINTER(f32), ctypes.POINTER(f32), vp, vp, vp]),
     'nsr_cast_f32_to_f16': (i32, [vp, vp, u64, vp]),
@@ -112,7 +117,12 @@ def lib():
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback.'.format(LIB_PATH))
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)   # AttributeError if the library does not export it
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                # (the ABI version alone does not catch a library built before symbols were ADDED at the same version)
+                raise RuntimeError('libnsr_hip.so at {} is stale: it does not export {}; rebuild with `python -m '
+                                   'nerfstyle_amd.build`'.format(LIB_PATH, name)) from None
             fn.restype = res
             fn.argtypes = args
         if L.nsr_abi_version() != ABI_VERSION:

@@ -30,13 +30,16 @@ __device__ __forceinline__ void field_store_channels(const FieldArgs &a, uint32_
     }
 }
 
-template <typename TT, int CD, bool SIGMA_ONLY>
+// DIRS (nsr_field_forward_dirs): `dirs` [M,3] are the samples' viewing directions, indexed like xyzs; lane (s, g) evaluates
+// SH coefficients 4g..4g+3 of sample s (the four g lanes load one address: one request) for color2's K = 32 first layer.
+template <typename TT, int CD, bool SIGMA_ONLY, bool DIRS = false>
 __global__ void __launch_bounds__(256)
-k_field_fwd(FieldArgs a) {
+k_field_fwd(FieldArgsOf<DIRS> a) {
+    const float *const dirs = field_dirs_of(a);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     short *wl = reinterpret_cast<short *>(smem);
-    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + (SIGMA_ONLY ? FW_SIGMA_TOTAL : FW_TOTAL) * 2);
-    field_build_fw<CD, SIGMA_ONLY>(wl, a.params);
+    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + (SIGMA_ONLY ? FW_SIGMA_TOTAL : FW_IMAGE<DIRS>) * 2);
+    field_build_fw<CD, SIGMA_ONLY, DIRS>(wl, a.params);
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
     __syncthreads();
 
@@ -77,7 +80,8 @@ k_field_fwd(FieldArgs a) {
         if (SIGMA_ONLY) continue;
 
         f4v rgb, cls;
-        field_colour_nets<CD>(wl, lane, xc, rgb, cls);
+        if constexpr (DIRS) field_colour_nets<CD, true>(wl, lane, xc, rgb, cls, field_sh_frag<CD>(dirs, m, valid, g));
+        else field_colour_nets<CD>(wl, lane, xc, rgb, cls);
         if (valid) field_store_channels(a, m, g, rgb, cls);
     }
 }
@@ -98,7 +102,10 @@ k_field_fwd(FieldArgs a) {
 // keep the gather.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t FWD_LAT_LEVELS = 0x00FFu;
-constexpr int FWD_LAT_ANCHOR_BYTES = 16 * sizeof(uint4);      // per wave, in front of its lattices
+// anchors per wave, in front of its lattices: one per level, or with directions one per level of FWD_LAT_LEVELS only -- the 512 B
+// that brings the 2 KB larger weight image back to four workgroups per CU (40 960 B exactly on the default grid)
+template <bool DIRS> constexpr int FWD_LAT_ANCHORS = DIRS ? 8 : 16;
+static_assert((FWD_LAT_LEVELS >> 8) == 0, "with directions only levels 0..7 have an anchor");
 
 typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) u2v lds_row;        // one 8-byte table row in a lattice
@@ -110,6 +117,7 @@ struct FieldLatArgs {
 
 // Re-anchors the levels of FWD_LAT_LEVELS at the group of block `key` and fills the lattices whose anchor moved.
 // lds_lv[l].pad_ = S | shift << 4 | first slot << 8.
+template <int NANCH>
 __device__ __forceinline__ void field_lat_refill(const NsrLevel *lds_lv, const uint2 *__restrict__ tables, uint4 *anch, uint2 *lat,
                                                  uint32_t key, int lane) {
     const uint32_t kmask = (1u << LAT_KEY_BITS) - 1u;
@@ -122,7 +130,7 @@ __device__ __forceinline__ void field_lat_refill(const NsrLevel *lds_lv, const u
     nsr_grid_locate((float)(((key & kmask) >> sh) << sh) * rk, mlv.resolution, 1, ff, n0);
     nsr_grid_locate((float)((((key >> LAT_KEY_BITS) & kmask) >> sh) << sh) * rk, mlv.resolution, 1, ff, n1);
     nsr_grid_locate((float)(((key >> (2 * LAT_KEY_BITS)) >> sh) << sh) * rk, mlv.resolution, 1, ff, n2);
-    const uint4 old = anch[l];
+    const uint4 old = anch[l & (NANCH - 1)];
     const bool chg = lane < 16 && ((FWD_LAT_LEVELS >> l) & 1u) && (n0 != old.x || n1 != old.y || n2 != old.z);
     if (chg) anch[l] = make_uint4(n0, n1, n2, 0u);
     uint32_t stale = (uint32_t)__ballot(chg);
@@ -191,19 +199,20 @@ __device__ __forceinline__ void field_encode_lat(const NsrLevel *lds_lv, const u
     field_mix_rows<CD>(v, w, live, xd, xc);
 }
 
-template <int CD>
+template <int CD, bool DIRS = false>
 __global__ void __launch_bounds__(256)
-k_field_fwd_lat(FieldArgs a, FieldLatArgs la) {
+k_field_fwd_lat(FieldArgsOf<DIRS> a, FieldLatArgs la) {
+    const float *const dirs = field_dirs_of(a);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     short *wl = reinterpret_cast<short *>(smem);
-    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + FW_TOTAL * 2);
+    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + FW_IMAGE<DIRS> * 2);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    char *wbase = smem + FW_TOTAL * 2 + 16 * sizeof(NsrLevel) + (size_t)wave * la.wave_bytes;
+    char *wbase = smem + FW_IMAGE<DIRS> * 2 + 16 * sizeof(NsrLevel) + (size_t)wave * la.wave_bytes;
     uint4 *anch = reinterpret_cast<uint4 *>(wbase);
-    uint2 *lat = reinterpret_cast<uint2 *>(wbase + FWD_LAT_ANCHOR_BYTES);
-    field_build_fw<CD, false>(wl, a.params);
+    uint2 *lat = reinterpret_cast<uint2 *>(wbase + FWD_LAT_ANCHORS<DIRS> * sizeof(uint4));
+    field_build_fw<CD, false, DIRS>(wl, a.params);
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
-    if (lane < 16) anch[lane] = make_uint4(LAT_NONE, LAT_NONE, LAT_NONE, 0u);
+    if (lane < FWD_LAT_ANCHORS<DIRS>) anch[lane] = make_uint4(LAT_NONE, LAT_NONE, LAT_NONE, 0u);
     __syncthreads();
 
     const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
@@ -237,7 +246,7 @@ k_field_fwd_lat(FieldArgs a, FieldLatArgs la) {
             const uint32_t key = (uint32_t)__builtin_amdgcn_readlane((int)bkey, (int)__builtin_ctzll(lm));
             if (cur_key == LAT_NONE || ((key ^ cur_key) & la.key_mask) != 0u) {
                 cur_key = key;
-                field_lat_refill(lds_lv, tables, anch, lat, key, lane);
+                field_lat_refill<FWD_LAT_ANCHORS<DIRS>>(lds_lv, tables, anch, lat, key, lane);
             }
         }
         s8v xd, xc;
@@ -252,41 +261,70 @@ k_field_fwd_lat(FieldArgs a, FieldLatArgs la) {
         if (valid && g == 0) a.sigmas[m] = expf(o[0]) * a.density_scale;   // tcnn_nerf.py:55-60, renderer.py:225
 
         f4v rgb, cls;
-        field_colour_nets<CD>(wl, lane, xc, rgb, cls);
+        if constexpr (DIRS) field_colour_nets<CD, true>(wl, lane, xc, rgb, cls, field_sh_frag<CD>(dirs, m, valid, g));
+        else field_colour_nets<CD>(wl, lane, xc, rgb, cls);
         if (valid) field_store_channels(a, m, g, rgb, cls);
+    }
+}
+
+// stand-alone SH encoding (the tcnn.Encoding stand-in of SHEncoder): out[m, 0..15], fp32, not rounded
+__global__ void __launch_bounds__(256)
+k_sh_encode(const float *__restrict__ dirs, uint32_t M, float *__restrict__ out) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < M * 4u; i += gridDim.x * 256u) {
+        const uint32_t m = i >> 2;
+        const f4v c = field_sh4((int)(i & 3u), dirs[(size_t)m * 3 + 0], dirs[(size_t)m * 3 + 1], dirs[(size_t)m * 3 + 2]);
+        reinterpret_cast<float4 *>(out)[i] = make_float4(c[0], c[1], c[2], c[3]);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-template <typename TT, int CD>
-static int field_launch_fwd(const FieldArgs &a, uint32_t nblocks, bool sigma_only, hipStream_t s) {
+// The lattice kernel's launch geometry for a level table, written into b.lv[].pad_ and la; returns its LDS bytes, or 0 where the
+// walk keeps the gather (a grid the scatter's lattices do not fit, or one that needs more than a quarter of a CU's LDS).
+template <bool DIRS>
+static size_t field_lat_plan(NsrLevel (&lv)[16], FieldLatArgs &la) {
+    if (!nsr_table_scatter_supported(lv)) return 0;
+    // lattices of FWD_LAT_LEVELS, packed: pad_ = S | shift << 4 | first slot << 8 (the other levels' pad_ is not read)
+    LatGeom geo;
+    lat_geometry(lv, geo, 1024u);
+    uint32_t slots = 0, min_shift = LAT_KEY_BITS;
+    for (int l = 0; l < 16; l++) {
+        if (!((FWD_LAT_LEVELS >> l) & 1u)) continue;
+        lv[l].pad_ = (uint32_t)geo.S[l] | ((uint32_t)geo.shift[l] << 4) | (slots << 8);
+        slots += (uint32_t)geo.S[l] * geo.S[l] * geo.S[l];
+        if (geo.shift[l] < min_shift) min_shift = geo.shift[l];
+    }
+    const uint32_t axis = ((1u << LAT_KEY_BITS) - 1u) & ~((1u << min_shift) - 1u);
+    la.key_mask = axis | (axis << LAT_KEY_BITS) | (axis << (2 * LAT_KEY_BITS));
+    la.wave_bytes = FWD_LAT_ANCHORS<DIRS> * (uint32_t)sizeof(uint4) + ((slots * (uint32_t)sizeof(uint2) + 15u) & ~15u);
+    const size_t lds = FW_IMAGE<DIRS> * 2 + 16 * sizeof(NsrLevel) + 4 * (size_t)la.wave_bytes;
+    return lds <= 40960 ? lds : 0;      // four workgroups per CU, as k_field_fwd; a grid that needs more keeps the gather
+}
+
+template <typename TT, int CD, bool DIRS = false>
+static int field_launch_fwd(const FieldArgs &a, uint32_t nblocks, bool sigma_only, hipStream_t s, const float *dirs = nullptr) {
+    if (DIRS && sigma_only) return NSR_ERR_INVALID_ARG;      // the sigma-only branch has no direction-taking form
     if constexpr (sizeof(TT) == 2) {
-        if (!sigma_only && a.perm && nsr_table_scatter_supported(a.lv)) {
-            // lattices of FWD_LAT_LEVELS, packed: pad_ = S | shift << 4 | first slot << 8 (the other levels' pad_ is not read)
-            LatGeom geo;
-            lat_geometry(a.lv, geo, 1024u);
-            FieldArgs b = a;
+        if (!sigma_only && a.perm) {
+            FieldArgsOf<DIRS> b;
+            static_cast<FieldArgs &>(b) = a;
+            if constexpr (DIRS) b.dirs = dirs;
             FieldLatArgs la;
-            uint32_t slots = 0, min_shift = LAT_KEY_BITS;
-            for (int l = 0; l < 16; l++) {
-                if (!((FWD_LAT_LEVELS >> l) & 1u)) continue;
-                b.lv[l].pad_ = (uint32_t)geo.S[l] | ((uint32_t)geo.shift[l] << 4) | (slots << 8);
-                slots += (uint32_t)geo.S[l] * geo.S[l] * geo.S[l];
-                if (geo.shift[l] < min_shift) min_shift = geo.shift[l];
-            }
-            const uint32_t axis = ((1u << LAT_KEY_BITS) - 1u) & ~((1u << min_shift) - 1u);
-            la.key_mask = axis | (axis << LAT_KEY_BITS) | (axis << (2 * LAT_KEY_BITS));
-            la.wave_bytes = FWD_LAT_ANCHOR_BYTES + ((slots * (uint32_t)sizeof(uint2) + 15u) & ~15u);
-            const size_t lds = FW_TOTAL * 2 + 16 * sizeof(NsrLevel) + 4 * (size_t)la.wave_bytes;
-            if (lds <= 40960) {      // four workgroups per CU, as k_field_fwd; a grid that needs more keeps the gather
-                hipLaunchKernelGGL((k_field_fwd_lat<CD>), dim3(nblocks), dim3(256), lds, s, b, la);
+            const size_t lds = field_lat_plan<DIRS>(b.lv, la);
+            if (lds) {
+                hipLaunchKernelGGL((k_field_fwd_lat<CD, DIRS>), dim3(nblocks), dim3(256), lds, s, b, la);
                 return nsr_launch_status();
             }
         }
     }
-    if (sigma_only) {
+    if constexpr (DIRS) {
+        const size_t lds = FW_TOTAL_DIRS * 2 + 16 * sizeof(NsrLevel);
+        FieldDirsArgs b;
+        static_cast<FieldArgs &>(b) = a;
+        b.dirs = dirs;
+        hipLaunchKernelGGL((k_field_fwd<TT, CD, false, true>), dim3(nblocks), dim3(256), lds, s, b);
+    } else if (sigma_only) {
         const size_t lds = FW_SIGMA_TOTAL * 2 + 16 * sizeof(NsrLevel);
         hipLaunchKernelGGL((k_field_fwd<TT, CD, true>), dim3(nblocks), dim3(256), lds, s, a);
     } else {
@@ -318,6 +356,52 @@ int nsr_field_forward(const nsr_field_desc *desc, const void *tables, const floa
     if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_BF16) return field_launch_fwd<float, NSR_BF16>(a, nblocks, so, s);
     if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_F16) return field_launch_fwd<_Float16, NSR_F16>(a, nblocks, so, s);
     if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_BF16) return field_launch_fwd<_Float16, NSR_BF16>(a, nblocks, so, s);
+    return NSR_ERR_UNSUPPORTED;
+}
+
+uint32_t nsr_field_mlp_param_count(int with_dirs) { return with_dirs ? P_TOTAL_DIRS : P_TOTAL; }
+
+int nsr_field_forward_uses_lattice(const nsr_field_desc *desc, int with_perm, int with_dirs) {
+    if (desc == nullptr) return 0;
+    FieldArgs a;
+    uint32_t nblocks;
+    if (field_fill_args(desc, a, 16, nblocks) != NSR_OK) return 0;
+    if (!with_perm || desc->table_dtype != NSR_F16) return 0;
+    FieldLatArgs la;
+    return (with_dirs ? field_lat_plan<true>(a.lv, la) : field_lat_plan<false>(a.lv, la)) != 0;
+}
+
+int nsr_sh_encode(const float *dirs, uint32_t M, float *out, nsr_stream_t stream) {
+    if (M == 0) return NSR_OK;
+    NSR_CHECK_PTR(dirs); NSR_CHECK_PTR(out);
+    if (((uintptr_t)out & 15u) || M > 0x3FFFFFFFu) return NSR_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(k_sh_encode, dim3(nsr_grid_1d((uint64_t)M * 4, 256)), dim3(256), 0, (hipStream_t)stream, dirs, M, out);
+    return nsr_launch_status();
+}
+
+int nsr_field_forward_dirs(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *xyzs, uint32_t M,
+                           const int32_t *m_dev, float *sigmas, float *rgbs, void *feats, const uint32_t *perm, const float *dirs,
+                           nsr_stream_t stream) {
+    // the sigma-only branch never reads directions (nor the SH columns): it is nsr_field_forward's
+    if (rgbs == nullptr) return nsr_field_forward(desc, tables, mlp_params, xyzs, M, m_dev, sigmas, rgbs, feats, perm, stream);
+    if (M == 0) return NSR_OK;
+    NSR_CHECK_PTR(desc); NSR_CHECK_PTR(tables); NSR_CHECK_PTR(mlp_params); NSR_CHECK_PTR(xyzs); NSR_CHECK_PTR(sigmas);
+    NSR_CHECK_PTR(dirs);
+    FieldArgs a;
+    uint32_t nblocks;
+    const int st = field_fill_args(desc, a, M, nblocks);
+    if (st != NSR_OK) return st;
+    if ((uintptr_t)tables & 15u) return NSR_ERR_INVALID_ARG;
+    if (a.C_ch == 8 && ((uintptr_t)rgbs & 15u)) return NSR_ERR_INVALID_ARG;
+    a.tables = tables; a.params = mlp_params; a.xyzs = xyzs; a.m_dev = m_dev; a.sigmas = sigmas; a.rgbs = rgbs;
+    a.feats = feats;
+    a.perm = perm;
+    if (feats && ((uintptr_t)feats & 15u)) return NSR_ERR_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_F16) return field_launch_fwd<float, NSR_F16, true>(a, nblocks, false, s, dirs);
+    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_BF16) return field_launch_fwd<float, NSR_BF16, true>(a, nblocks, false, s, dirs);
+    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_F16) return field_launch_fwd<_Float16, NSR_F16, true>(a, nblocks, false, s, dirs);
+    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_BF16) return field_launch_fwd<_Float16, NSR_BF16, true>(a, nblocks, false, s, dirs);
     return NSR_ERR_UNSUPPORTED;
 }
 

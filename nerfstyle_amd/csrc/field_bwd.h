@@ -22,6 +22,8 @@
 //   field_bwd_gout.hip  k_field_bwd_gout: writes them out for the stand-alone table scatter (table_scatter.hip), and
 //                       k_field_bwd_color, its colour-table-only form; compiled with -mllvm --amdgpu-mfma-vgpr-form.
 #pragma once
+#include <type_traits>
+
 #include "field_common.h"
 #include "table_scatter.h"
 
@@ -42,6 +44,9 @@ constexpr int BWD_THREADS = 256;
 constexpr size_t BWD_QUEUE_BYTES_PER_WAVE = 1024 * 16 + 1024 * 4 + 16 * 16 * 16;
 constexpr size_t BWD_LDS_BYTES = (size_t)FW_TOTAL * 2 + (size_t)BW_TOTAL * 2 + 16 * sizeof(NsrLevel) +
                                  (BWD_THREADS / 64) * BWD_QUEUE_BYTES_PER_WAVE;
+// the direction-taking instantiations: the forward image is 2 KB larger (field_common.h), everything behind it moves up
+constexpr size_t BWD_LDS_BYTES_DIRS = BWD_LDS_BYTES + (size_t)(FW_TOTAL_DIRS - FW_TOTAL) * 2;
+static_assert(BWD_LDS_BYTES_DIRS <= 160 * 1024, "one workgroup per CU owns all of its LDS, and no more");
 
 
 struct FieldBwdArgs {
@@ -54,6 +59,21 @@ struct FieldBwdArgs {
     uint32_t nc;
     float4 *gout;              // gradients-out kernels: [M][16 levels] float4 = d loss / d (density f0, f1, colour f0, f1) of every sample
 };
+// argument of the direction-taking kernels (nsr_field_backward_dirs): dirs [M,3], indexed like xyzs.  Their recomputed forward
+// runs color2's K = 32 first layer; the dgrad through it is unchanged (only the color1 columns carry a gradient onwards, BW_R1T
+// stays), and the SH columns' weight gradient dH1^T x SH is four more accumulator tiles (64 in all: 256 registers).
+struct FieldBwdDirsArgs : FieldBwdArgs {
+    const float *dirs;
+};
+template <bool DIRS> using FieldBwdArgsOf = std::conditional_t<DIRS, FieldBwdDirsArgs, FieldBwdArgs>;
+__device__ __forceinline__ const float *field_dirs_of(const FieldBwdArgs &) { return nullptr; }
+__device__ __forceinline__ const float *field_dirs_of(const FieldBwdDirsArgs &b) { return b.dirs; }
+static inline FieldBwdDirsArgs field_bwd_with_dirs(const FieldBwdArgs &b, const float *dirs) {
+    FieldBwdDirsArgs bd;
+    static_cast<FieldBwdArgs &>(bd) = b;
+    bd.dirs = dirs;
+    return bd;
+}
 
 template <int CD>
 __device__ __forceinline__ void field_build_bw(short *lds, const float *__restrict__ p) {
@@ -165,4 +185,6 @@ static int field_bwd_dispatch(int table_dtype, int compute_dtype, bool feats, F 
 }
 
 // field_bwd_gout.hip: the gradients-out kernel, or its colour-table-only form where that is all the caller wants
-int nsr_field_bwd_launch_gout(const FieldBwdArgs &b, int table_dtype, int compute_dtype, bool feats, dim3 grid, hipStream_t s);
+// (dirs != NULL: the direction-taking instantiations)
+int nsr_field_bwd_launch_gout(const FieldBwdArgs &b, int table_dtype, int compute_dtype, bool feats, dim3 grid, hipStream_t s,
+                              const float *dirs);

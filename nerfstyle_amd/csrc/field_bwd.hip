@@ -240,15 +240,17 @@ __device__ __forceinline__ void field_wgrad(f4v (&acc)[NG * NA], const s4v (&Gt)
 // for this kernel on the bench frame (48.6 M samples): one net at a time (49.0 -> 48.0 ms); plain ReLU (packed v_pk_max_f16:
 // 49.0 -> 49.5 ms); weight fragments read at the point of use (the scatter already separates loads from their use, and the
 // read-ahead costs registers: 49.4 -> 51.2 ms); the next tile's inputs loaded right before the scatter.
-template <typename TT, int CD, bool FEATS>
+template <typename TT, int CD, bool FEATS, bool DIRS = false>
 __global__ void __launch_bounds__(BWD_THREADS)
-k_field_bwd_tracker(FieldBwdArgs b) {
+k_field_bwd_tracker(FieldBwdArgsOf<DIRS> b) {
+    constexpr int FWT = FW_IMAGE<DIRS>;
+    const float *const dirs = field_dirs_of(b);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     short *wl = reinterpret_cast<short *>(smem);
-    short *wt = wl + FW_TOTAL;
-    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + (size_t)(FW_TOTAL + BW_TOTAL) * 2);
+    short *wt = wl + FWT;
+    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + (size_t)(FWT + BW_TOTAL) * 2);
     const FieldArgs &a = b.f;
-    field_build_fw<CD, false>(wl, a.params);
+    field_build_fw<CD, false, DIRS>(wl, a.params);
     field_build_bw<CD>(wt, a.params);
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
     __syncthreads();
@@ -265,7 +267,7 @@ k_field_bwd_tracker(FieldBwdArgs b) {
     const s4v ident = mm_identity_frag<CD>(lane);
     const int nc = (int)b.nc;
     ScatterQueue q;
-    char *qbase = smem + (size_t)(FW_TOTAL + BW_TOTAL) * 2 + 16 * sizeof(NsrLevel) + (size_t)wave * BWD_QUEUE_BYTES_PER_WAVE;
+    char *qbase = smem + (size_t)(FWT + BW_TOTAL) * 2 + 16 * sizeof(NsrLevel) + (size_t)wave * BWD_QUEUE_BYTES_PER_WAVE;
     q.vals = reinterpret_cast<float4 *>(qbase);
     q.rows = reinterpret_cast<uint32_t *>(qbase + SCQ_CAP * 16);
     q.head = q.tail = 0;
@@ -279,8 +281,10 @@ k_field_bwd_tracker(FieldBwdArgs b) {
     float *const gt1 = b.grad_tables - 4;      // ring rows are stored +1 (field_scatter_seq)
     // weight-gradient accumulators (60 tiles x 4 regs), resident for the whole launch
     f4v w_r3[4], w_r2[16], w_r1[4], w_c1b[4], w_c1a[8], w_k2[4], w_k1[8], w_d2[4], w_d1[8];
+    f4v w_sh[4];             // DIRS: color2's SH columns (P_SH), tiles 60..63
     {
         const f4v z = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (DIRS) { w_sh[0] = z; w_sh[1] = z; w_sh[2] = z; w_sh[3] = z; }
 #pragma unroll
         for (int q4 = 0; q4 < 4; q4++) { w_r3[q4] = z; w_r1[q4] = z; w_c1b[q4] = z; w_k2[q4] = z; w_d2[q4] = z; }
 #pragma unroll
@@ -351,6 +355,12 @@ k_field_bwd_tracker(FieldBwdArgs b) {
         // no saved features: gather them now (dependent loads, the slow path)
         if (!FEATS) field_encode<TT, CD, false>(lds_lv, tables, u0, u1, u2, live, g, cur.xd, cur.xc, a.fast_levels);
 
+        // DIRS: this tile's direction is requested here, not a tile ahead with the other inputs (three registers the 64
+        // accumulator tiles do not leave): its first use, color2's first layer, is two nets away
+        float dv[3] = {0.f, 0.f, 0.f};
+        if constexpr (DIRS) {
+            if (valid) { dv[0] = dirs[(size_t)m * 3 + 0]; dv[1] = dirs[(size_t)m * 3 + 1]; dv[2] = dirs[(size_t)m * 3 + 2]; }
+        }
         TileIn nxt{};
         f4v gxd[2], gxc[2];        // d L / d (density, colour) features of this lane's levels
         // paced drain of the previous tile's records: SCQ_PACE(n) issues <= n atomic wave-instructions
@@ -425,7 +435,14 @@ k_field_bwd_tracker(FieldBwdArgs b) {
             mm_pack64<CD, true, false>(h, hc);
             mm_layer32<CD, 1, 2>(wl + FW_C1B, lane, hc, c1);
             const s4v c1b = mm_round4<CD, false>(c1[0]);
-            mm_layer16<CD, 4>(wl + FW_R1, lane, c1b, h);
+            s4v shb = {};
+            if constexpr (DIRS) {
+                shb = mm_round4<CD, false>(field_sh4(g, dv[0], dv[1], dv[2]));
+                const s8v b1[1] = {mm_cat(c1b, shb)};
+                mm_layer32<CD, 4, 1>(wl + FW_R1, lane, b1, h);
+            } else {
+                mm_layer16<CD, 4>(wl + FW_R1, lane, c1b, h);
+            }
             mm_pack64<CD, true, false>(h, hr1);
             mm_layer32<CD, 4, 2>(wl + FW_R2, lane, hr1, h);
             mm_pack64<CD, true, false>(h, hr2);
@@ -468,6 +485,11 @@ k_field_bwd_tracker(FieldBwdArgs b) {
                 field_tr4<CD>(g1, ident, g1t);
                 const s4v c1t[1] = {mm_transpose16<CD>(c1b, ident)};
                 field_wgrad<CD>(w_r1, g1t, c1t);
+                if constexpr (DIRS) {
+                    // the SH values sit in the lane layout of the color1 output tile: the same identity-MFMA transpose
+                    const s4v sht[1] = {mm_transpose16<CD>(shb, ident)};
+                    field_wgrad<CD>(w_sh, g1t, sht);
+                }
                 SCQ_PACE(4);
             }
             s8v gh[2];
@@ -523,13 +545,17 @@ k_field_bwd_tracker(FieldBwdArgs b) {
         __syncthreads();                                   // every wave is done with the weight fragments
         for (int w = 0; w < BWD_THREADS / 64; w++) {
             if (wave == w) {
+                // (DIRS: tiles 60..63 lie past the two weight images, over the level table and the head of wave 0's ring --
+                // every wave has flushed its ring by now)
                 if (w == 0) {
 #define NSR_RED_ST(arr, base, n) _Pragma("unroll") for (int i = 0; i < n; i++) red[((base) + i) * 64 + lane] = arr[i];
                     NSR_RED_ALL(NSR_RED_ST)
+                    if constexpr (DIRS) { NSR_RED_ST(w_sh, 60, 4) }
 #undef NSR_RED_ST
                 } else {
 #define NSR_RED_ADD(arr, base, n) _Pragma("unroll") for (int i = 0; i < n; i++) red[((base) + i) * 64 + lane] += arr[i];
                     NSR_RED_ALL(NSR_RED_ADD)
+                    if constexpr (DIRS) { NSR_RED_ADD(w_sh, 60, 4) }
 #undef NSR_RED_ADD
                 }
             }
@@ -538,8 +564,10 @@ k_field_bwd_tracker(FieldBwdArgs b) {
         if (wave == 0) {
 #define NSR_RED_LD(arr, base, n) _Pragma("unroll") for (int i = 0; i < n; i++) arr[i] = red[((base) + i) * 64 + lane];
             NSR_RED_ALL(NSR_RED_LD)
+            if constexpr (DIRS) { NSR_RED_LD(w_sh, 60, 4) }
 #undef NSR_RED_LD
             float *gm = b.grad_mlp;
+            if constexpr (DIRS) field_wgrad_flush<4, 1>(gm + P_SH, 16, 0, 64, w_sh, lane);
             field_wgrad_flush<1, 4>(gm + P_R3, 64, 0, 3, w_r3, lane);
             field_wgrad_flush<4, 4>(gm + P_R2, 64, 0, 64, w_r2, lane);
             field_wgrad_flush<4, 1>(gm + P_R1, 16, 0, 64, w_r1, lane);
@@ -554,11 +582,22 @@ k_field_bwd_tracker(FieldBwdArgs b) {
     }
 }
 
-static int field_bwd_launch_tracker(const FieldBwdArgs &b, int table_dtype, int compute_dtype, bool feats, dim3 grid, hipStream_t s) {
+static int field_bwd_launch_tracker(const FieldBwdArgs &b, int table_dtype, int compute_dtype, bool feats, dim3 grid, hipStream_t s,
+                                    const float *dirs) {
     return field_bwd_dispatch(table_dtype, compute_dtype, feats, [&](auto tt, auto cd, auto ft) {
+        if (dirs) {
+            const FieldBwdDirsArgs bd = field_bwd_with_dirs(b, dirs);
+            return nsr_launch_lds<k_field_bwd_tracker<decltype(tt), cd(), ft(), true>>(BWD_LDS_BYTES_DIRS, grid, dim3(BWD_THREADS),
+                                                                                       BWD_LDS_BYTES_DIRS, s, bd);
+        }
         return nsr_launch_lds<k_field_bwd_tracker<decltype(tt), cd(), ft()>>(BWD_LDS_BYTES, grid, dim3(BWD_THREADS), BWD_LDS_BYTES, s, b);
     });
 }
+
+static int field_backward_any(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *xyzs, uint32_t M,
+                              const int32_t *m_dev, const float *grad_sigmas, const float *grad_rgbs, float *grad_tables,
+                              float *grad_mlp, int train_density_table, int train_color_table, const void *feats,
+                              const uint32_t *perm, void *workspace, const float *dirs, nsr_stream_t stream);
 
 extern "C" {
 
@@ -570,6 +609,26 @@ int nsr_field_backward(const nsr_field_desc *desc, const void *tables, const flo
                        const int32_t *m_dev, const float *grad_sigmas, const float *grad_rgbs, float *grad_tables,
                        float *grad_mlp, int train_density_table, int train_color_table, const void *feats,
                        const uint32_t *perm, void *workspace, nsr_stream_t stream) {
+    return field_backward_any(desc, tables, mlp_params, xyzs, M, m_dev, grad_sigmas, grad_rgbs, grad_tables, grad_mlp,
+                              train_density_table, train_color_table, feats, perm, workspace, nullptr, stream);
+}
+
+int nsr_field_backward_dirs(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *xyzs, uint32_t M,
+                            const int32_t *m_dev, const float *grad_sigmas, const float *grad_rgbs, float *grad_tables,
+                            float *grad_mlp, int train_density_table, int train_color_table, const void *feats,
+                            const uint32_t *perm, void *workspace, const float *dirs, nsr_stream_t stream) {
+    if (M == 0) return NSR_OK;
+    NSR_CHECK_PTR(dirs);
+    return field_backward_any(desc, tables, mlp_params, xyzs, M, m_dev, grad_sigmas, grad_rgbs, grad_tables, grad_mlp,
+                              train_density_table, train_color_table, feats, perm, workspace, dirs, stream);
+}
+
+}   // extern "C"
+
+static int field_backward_any(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *xyzs, uint32_t M,
+                              const int32_t *m_dev, const float *grad_sigmas, const float *grad_rgbs, float *grad_tables,
+                              float *grad_mlp, int train_density_table, int train_color_table, const void *feats,
+                              const uint32_t *perm, void *workspace, const float *dirs, nsr_stream_t stream) {
     if (M == 0) return NSR_OK;
     NSR_CHECK_PTR(desc); NSR_CHECK_PTR(tables); NSR_CHECK_PTR(mlp_params); NSR_CHECK_PTR(xyzs);
     NSR_CHECK_PTR(grad_sigmas); NSR_CHECK_PTR(grad_rgbs);
@@ -603,12 +662,10 @@ int nsr_field_backward(const nsr_field_desc *desc, const void *tables, const flo
     b.train_density = train_density_table; b.train_color = train_color_table; b.nc = desc->num_classes;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nblocks);
-    if (!gout) return field_bwd_launch_tracker(b, desc->table_dtype, desc->compute_dtype, feats != nullptr, grid, s);
-    const int st1 = nsr_field_bwd_launch_gout(b, desc->table_dtype, desc->compute_dtype, feats != nullptr, grid, s);
+    if (!gout) return field_bwd_launch_tracker(b, desc->table_dtype, desc->compute_dtype, feats != nullptr, grid, s, dirs);
+    const int st1 = nsr_field_bwd_launch_gout(b, desc->table_dtype, desc->compute_dtype, feats != nullptr, grid, s, dirs);
     if (st1 != NSR_OK) return st1;
     // second kernel: the table scatter in the permutation's order, many waves per CU
     return nsr_table_scatter_launch(b.f.lv, b.f.bmin, b.f.bsize, xyzs, perm, m_dev, M, workspace, grad_tables, train_density_table,
                                     train_color_table, s);
 }
-
-}   // extern "C"

@@ -78,6 +78,13 @@ __device__ __forceinline__ void field_tr5p(const s8v (&x)[2], s4v y, s4v ident, 
     mm_transpose16_n<CD, 5, TR_DEPTH>(in, ident, o);
     out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3]; yt[0] = o[4];
 }
+template <int CD>
+__device__ __forceinline__ void field_tr6p(const s8v (&x)[2], s4v y, s4v z, s4v ident, s4v (&out)[4], s4v (&yt)[1], s4v (&zt)[1]) {
+    const s4v in[6] = {mm_lo(x[0]), mm_hi(x[0]), mm_lo(x[1]), mm_hi(x[1]), y, z};
+    s4v o[6];
+    mm_transpose16_n<CD, 6, TR_DEPTH>(in, ident, o);
+    out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3]; yt[0] = o[4]; zt[0] = o[5];
+}
 
 // One wave per SIMD (its 240 weight-gradient accumulators).  The schedule of the MLP section is the one measured fastest
 // for this kernel on the bench frame (48.6 M samples): straight order (one net at a time: 13.45 against 13.0 ms once the
@@ -90,15 +97,18 @@ __device__ __forceinline__ void field_tr5p(const s8v (&x)[2], s4v y, s4v ident, 
 // transposes through LDS (ds_write_b64 + ds_read_b64_tr_b16, 49 per tile) instead of an MFMA with the identity +
 // re-rounding: 1304 -> 1240 instructions per tile and the same time (21.4 vs 21.5 ms for the pair) -- the LDS round trips
 // cost what the MFMAs did.
-template <typename TT, int CD, bool FEATS>
+// DIRS: 64 accumulator tiles -- all 256 registers of the accumulator half.
+template <typename TT, int CD, bool FEATS, bool DIRS = false>
 __global__ void __launch_bounds__(BWD_THREADS)
-k_field_bwd_gout(FieldBwdArgs b) {
+k_field_bwd_gout(FieldBwdArgsOf<DIRS> b) {
+    constexpr int FWT = FW_IMAGE<DIRS>;
+    const float *const dirs = field_dirs_of(b);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     short *wl = reinterpret_cast<short *>(smem);
-    short *wt = wl + FW_TOTAL;
-    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + (size_t)(FW_TOTAL + BW_TOTAL) * 2);
+    short *wt = wl + FWT;
+    NsrLevel *lds_lv = reinterpret_cast<NsrLevel *>(smem + (size_t)(FWT + BW_TOTAL) * 2);
     const FieldArgs &a = b.f;
-    field_build_fw<CD, false>(wl, a.params);
+    field_build_fw<CD, false, DIRS>(wl, a.params);
     field_build_bw<CD>(wt, a.params);
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
     __syncthreads();
@@ -118,8 +128,10 @@ k_field_bwd_gout(FieldBwdArgs b) {
     const bool td = b.train_density != 0, tc = b.train_color != 0;
     // weight-gradient accumulators (60 tiles x 4 regs), resident for the whole launch
     f4v w_r3[4], w_r2[16], w_r1[4], w_c1b[4], w_c1a[8], w_k2[4], w_k1[8], w_d2[4], w_d1[8];
+    f4v w_sh[4];             // DIRS: color2's SH columns (P_SH), tiles 60..63
     {
         const f4v z = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (DIRS) { w_sh[0] = z; w_sh[1] = z; w_sh[2] = z; w_sh[3] = z; }
 #pragma unroll
         for (int q4 = 0; q4 < 4; q4++) { w_r3[q4] = z; w_r1[q4] = z; w_c1b[q4] = z; w_k2[q4] = z; w_d2[q4] = z; }
 #pragma unroll
@@ -209,6 +221,12 @@ k_field_bwd_gout(FieldBwdArgs b) {
         // first MFMA that reads cur.xc).  The loads of `cur` are a whole tile old at this point.
         asm volatile("" :: "v"(cur.x0), "v"(cur.x1), "v"(cur.x2), "v"(cur.gsig), "v"(cur.grgb[0]), "v"(cur.grgb[1]),
                      "v"(cur.grgb[2]), "v"(cur.grgb[3]), "v"(cur.xd), "v"(cur.xc), "v"(idx_next));
+        // DIRS: this tile's direction is requested here, not a tile ahead with the other inputs (three registers the 64
+        // accumulator tiles do not leave): its first use, color2's first layer, is four layers away
+        float dv[3] = {0.f, 0.f, 0.f};
+        if constexpr (DIRS) {
+            if (valid) { dv[0] = dirs[(size_t)idx_cur * 3 + 0]; dv[1] = dirs[(size_t)idx_cur * 3 + 1]; dv[2] = dirs[(size_t)idx_cur * 3 + 2]; }
+        }
         const float u0 = valid ? field_unit(cur.x0, a.bmin[0], a.bsize[0]) : 0.f;
         const float u1 = valid ? field_unit(cur.x1, a.bmin[1], a.bsize[1]) : 0.f;
         const float u2 = valid ? field_unit(cur.x2, a.bmin[2], a.bsize[2]) : 0.f;
@@ -251,9 +269,17 @@ k_field_bwd_gout(FieldBwdArgs b) {
         mm_queue32<2>(wq, wl + FW_C1B, lane);
         mm_pack64<CD, true, true>(h, hc);
         mm_layer32_q<CD, 1, 2>(wq, wl + FW_C1B, lane, hc, c1);
-        mm_queue16<4>(wq16, wl + FW_R1, lane);
+        s4v shb = {};
+        if constexpr (DIRS) mm_queue32<4>(wq, wl + FW_R1, lane);
+        else mm_queue16<4>(wq16, wl + FW_R1, lane);
         const s4v c1b = mm_round4<CD, false>(c1[0]);
-        mm_layer16_q<CD, 4>(wq16, c1b, h);
+        if constexpr (DIRS) {
+            shb = mm_round4<CD, false>(field_sh4(g, dv[0], dv[1], dv[2]));
+            const s8v b1[1] = {mm_cat(c1b, shb)};
+            mm_layer32_q<CD, 4, 1>(wq, wl + FW_R1, lane, b1, h);
+        } else {
+            mm_layer16_q<CD, 4>(wq16, c1b, h);
+        }
         mm_queue32<8>(wq, wl + FW_R2, lane);
         mm_pack64<CD, true, true>(h, hr1);
         mm_layer32_q<CD, 4, 2>(wq, wl + FW_R2, lane, hr1, h);
@@ -313,8 +339,16 @@ k_field_bwd_gout(FieldBwdArgs b) {
             field_tr4p<CD>(g2, ident, g2t);
             field_tr4p<CD>(hr1, ident, hr1t);
             field_wgrad<CD>(w_r2, g2t, hr1t);
-            field_tr5p<CD>(g1, c1b, ident, g1t, c1t);
-            field_wgrad<CD>(w_r1, g1t, c1t);
+            if constexpr (DIRS) {
+                // the SH values sit in the lane layout of the color1 output tile: the same transpose, one more in the pipeline
+                s4v sht[1];
+                field_tr6p<CD>(g1, c1b, shb, ident, g1t, c1t, sht);
+                field_wgrad<CD>(w_r1, g1t, c1t);
+                field_wgrad<CD>(w_sh, g1t, sht);
+            } else {
+                field_tr5p<CD>(g1, c1b, ident, g1t, c1t);
+                field_wgrad<CD>(w_r1, g1t, c1t);
+            }
         }
         // transposed encoder features (shared by the color1 / class / density wgrads)
         s4v xct[2], xdt[2];
@@ -390,6 +424,7 @@ k_field_bwd_gout(FieldBwdArgs b) {
         field_wgrad_settle(w_r3); field_wgrad_settle(w_r2); field_wgrad_settle(w_r1); field_wgrad_settle(w_c1b);
         field_wgrad_settle(w_c1a); field_wgrad_settle(w_k2); field_wgrad_settle(w_k1); field_wgrad_settle(w_d2);
         field_wgrad_settle(w_d1);
+        if constexpr (DIRS) field_wgrad_settle(w_sh);
 
     // ---- weight gradients: summed over the workgroup's waves in LDS, then ONE wave adds them to grad_mlp ----------------
     // Every wave holds 60 tiles = 15 360 partial sums.  Flushed wave by wave (rounds 1-2) that is 240 atomic wave-instructions
@@ -406,13 +441,16 @@ k_field_bwd_gout(FieldBwdArgs b) {
         __syncthreads();                                   // every wave is done with the weight fragments
         for (int w = 0; w < BWD_THREADS / 64; w++) {
             if (wave == w) {
+                // (DIRS: tiles 60..63 lie past the two weight images, over the level table and LDS this kernel does not use)
                 if (w == 0) {
 #define NSR_RED_ST(arr, base, n) _Pragma("unroll") for (int i = 0; i < n; i++) red[((base) + i) * 64 + lane] = arr[i];
                     NSR_RED_ALL(NSR_RED_ST)
+                    if constexpr (DIRS) { NSR_RED_ST(w_sh, 60, 4) }
 #undef NSR_RED_ST
                 } else {
 #define NSR_RED_ADD(arr, base, n) _Pragma("unroll") for (int i = 0; i < n; i++) red[((base) + i) * 64 + lane] += arr[i];
                     NSR_RED_ALL(NSR_RED_ADD)
+                    if constexpr (DIRS) { NSR_RED_ADD(w_sh, 60, 4) }
 #undef NSR_RED_ADD
                 }
             }
@@ -421,8 +459,10 @@ k_field_bwd_gout(FieldBwdArgs b) {
         if (wave == 0) {
 #define NSR_RED_LD(arr, base, n) _Pragma("unroll") for (int i = 0; i < n; i++) arr[i] = red[((base) + i) * 64 + lane];
             NSR_RED_ALL(NSR_RED_LD)
+            if constexpr (DIRS) { NSR_RED_LD(w_sh, 60, 4) }
 #undef NSR_RED_LD
             float *gm = b.grad_mlp;
+            if constexpr (DIRS) field_wgrad_flush<4, 1>(gm + P_SH, 16, 0, 64, w_sh, lane);
             field_wgrad_flush<1, 4>(gm + P_R3, 64, 0, 3, w_r3, lane);
             field_wgrad_flush<4, 4>(gm + P_R2, 64, 0, 64, w_r2, lane);
             field_wgrad_flush<4, 1>(gm + P_R1, 16, 0, 64, w_r1, lane);
@@ -445,15 +485,16 @@ k_field_bwd_gout(FieldBwdArgs b) {
 // colour gradients are bit-identical to its.  gout's density components are written as zeros (the scatter ignores them).
 // Weight-fragment reads run four ahead of the MFMA stream (mfma_tiles.h), as everywhere in this unit.
 constexpr int COLOR_THREADS = 512;       // 8 waves share one 60 KB weight image: two workgroups per CU = four waves per SIMD (90 registers)
-template <int CD>
+template <int CD, bool DIRS = false>
 __global__ void __launch_bounds__(COLOR_THREADS)
-k_field_bwd_color(FieldBwdArgs b) {
+k_field_bwd_color(FieldBwdArgsOf<DIRS> b) {
     constexpr int AHEAD = 4;
+    const float *const dirs = field_dirs_of(b);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     short *wl = reinterpret_cast<short *>(smem);
-    short *wt = wl + FW_TOTAL;
+    short *wt = wl + FW_IMAGE<DIRS>;
     const FieldArgs &a = b.f;
-    field_build_fw<CD, false>(wl, a.params);
+    field_build_fw<CD, false, DIRS>(wl, a.params);
     field_build_bw<CD>(wt, a.params);
     __syncthreads();
     const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
@@ -497,7 +538,12 @@ k_field_bwd_color(FieldBwdArgs b) {
         mm_pack64<CD, true, true>(h, hc);
         mm_layer32<CD, 1, 2, AHEAD>(wl + FW_C1B, lane, hc, c1);
         const s4v c1b = mm_round4<CD, false>(c1[0]);
-        mm_layer16<CD, 4, AHEAD>(wl + FW_R1, lane, c1b, h);
+        if constexpr (DIRS) {
+            const s8v b1[1] = {mm_cat(c1b, field_sh_frag<CD>(dirs, m, valid, g))};
+            mm_layer32<CD, 4, 1, AHEAD>(wl + FW_R1, lane, b1, h);
+        } else {
+            mm_layer16<CD, 4, AHEAD>(wl + FW_R1, lane, c1b, h);
+        }
         mm_pack64<CD, true, true>(h, hr1);
         mm_layer32<CD, 4, 2, AHEAD>(wl + FW_R2, lane, hr1, h);
         mm_pack64<CD, true, true>(h, hr2);
@@ -545,22 +591,32 @@ k_field_bwd_color(FieldBwdArgs b) {
     }
 }
 template <int CD>
-static int field_bwd_launch_color(const FieldBwdArgs &b, hipStream_t s) {
-    const size_t lds = (size_t)(FW_TOTAL + BW_TOTAL) * 2;
+static int field_bwd_launch_color(const FieldBwdArgs &b, hipStream_t s, const float *dirs) {
+    const size_t lds = (size_t)(FW_IMAGE<false> + BW_TOTAL) * 2, lds_dirs = (size_t)(FW_IMAGE<true> + BW_TOTAL) * 2;
     // two resident workgroups per CU; >= 8 tiles per wave so that the weight-image build amortises
     const uint32_t ntiles = (b.f.M + 15) / 16;
     uint32_t nb = (ntiles + 63) / 64;
     if (nb > 512) nb = 512;
     if (nb == 0) nb = 1;
+    if (dirs) {
+        const FieldBwdDirsArgs bd = field_bwd_with_dirs(b, dirs);
+        return nsr_launch_lds<k_field_bwd_color<CD, true>>(lds_dirs, dim3(nb), dim3(COLOR_THREADS), lds_dirs, s, bd);
+    }
     return nsr_launch_lds<k_field_bwd_color<CD>>(lds, dim3(nb), dim3(COLOR_THREADS), lds, s, b);
 }
 
-int nsr_field_bwd_launch_gout(const FieldBwdArgs &b, int table_dtype, int compute_dtype, bool feats, dim3 grid, hipStream_t s) {
+int nsr_field_bwd_launch_gout(const FieldBwdArgs &b, int table_dtype, int compute_dtype, bool feats, dim3 grid, hipStream_t s,
+                              const float *dirs) {
     if (b.grad_mlp == nullptr && !b.train_density && b.train_color && feats && b.f.perm != nullptr) {
-        if (compute_dtype == NSR_F16) return field_bwd_launch_color<NSR_F16>(b, s);
-        if (compute_dtype == NSR_BF16) return field_bwd_launch_color<NSR_BF16>(b, s);
+        if (compute_dtype == NSR_F16) return field_bwd_launch_color<NSR_F16>(b, s, dirs);
+        if (compute_dtype == NSR_BF16) return field_bwd_launch_color<NSR_BF16>(b, s, dirs);
     }
     return field_bwd_dispatch(table_dtype, compute_dtype, feats, [&](auto tt, auto cd, auto ft) {
+        if (dirs) {
+            const FieldBwdDirsArgs bd = field_bwd_with_dirs(b, dirs);
+            return nsr_launch_lds<k_field_bwd_gout<decltype(tt), cd(), ft(), true>>(BWD_LDS_BYTES_DIRS, grid, dim3(BWD_THREADS),
+                                                                                    BWD_LDS_BYTES_DIRS, s, bd);
+        }
         return nsr_launch_lds<k_field_bwd_gout<decltype(tt), cd(), ft()>>(BWD_LDS_BYTES, grid, dim3(BWD_THREADS), BWD_LDS_BYTES, s, b);
     });
 }

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 #include "mfma_tiles.h"
 
 // ---- parameter layout (floats) inside mlp_params: density, color1, color2, class ------------
@@ -15,10 +17,17 @@ constexpr int P_R3 = 11264;    // 16 x 64 (rows 0..2 = rgb)
 constexpr int P_K1 = 12288;    // 64 x 32
 constexpr int P_K2 = 14336;    // 16 x 64 (rows 0..nc-1 = classes)
 constexpr int P_TOTAL = 15360;
+// view-dependent models only (the *_dirs entry points): color2's first layer is 64 x 32 = [color1 | SH]; its SH columns are
+// appended so that every offset above stays where it is
+constexpr int P_SH = 15360;    // 64 x 16
+constexpr int P_TOTAL_DIRS = 16384;
 
 // ---- forward LDS image (units: shorts).  frag32 = 512 shorts, frag16 = 256 shorts ----------
 constexpr int FW_D1 = 0, FW_D2 = 2048, FW_C1A = 3072, FW_C1B = 5120, FW_K1 = 6144, FW_K2 = 8192, FW_R2 = 9216,
               FW_R3 = 13312, FW_R1 = 14336, FW_TOTAL = 15360, FW_SIGMA_TOTAL = 3072;
+// with directions FW_R1, the image's last block, is four frag32 (K = 32: color1 output | SH coefficients) instead of four frag16
+constexpr int FW_TOTAL_DIRS = 16384;
+template <bool DIRS> constexpr int FW_IMAGE = DIRS ? FW_TOTAL_DIRS : FW_TOTAL;
 // class logits live in rows 3..3+nc-1 of their output tile so that (row == output channel) and
 // lane (s,g) stores channels 4g..4g+3 of rgbs[m, :] as one 16-byte piece.
 constexpr int CLASS_ROW_SHIFT = 3;
@@ -40,8 +49,27 @@ struct FieldArgs {
     uint32_t fast_levels;     // bit l: level l is hashed and its size is a power of two
     NsrLevel lv[16];
 };
+// argument of the direction-taking forward kernels: dirs [M,3], indexed like xyzs
+struct FieldDirsArgs : FieldArgs {
+    const float *dirs;
+};
+template <bool DIRS> using FieldArgsOf = std::conditional_t<DIRS, FieldDirsArgs, FieldArgs>;
+__device__ __forceinline__ const float *field_dirs_of(const FieldArgs &) { return nullptr; }
+__device__ __forceinline__ const float *field_dirs_of(const FieldDirsArgs &a) { return a.dirs; }
 
-template <int CD, bool SIGMA_ONLY>
+// color2's first layer with directions, four frag32: the lane that holds rows 4g..4g+3 of the color1 output tile evaluates SH
+// coefficients 4g..4g+3 (field_sh4), so its B fragment is cat(color1 rows, SH coefficients) and element e of lane (r, g) of
+// the A fragment is W[row][4g + e] for e < 4 and Wsh[row][4g + e - 4] for e >= 4 (column 8g + e of the instruction's k axis).
+template <int CD>
+__device__ __forceinline__ void field_build_r1_dirs(short *lds, const float *__restrict__ w, const float *__restrict__ wsh) {
+    for (int idx = threadIdx.x; idx < 4 * 64 * 8; idx += blockDim.x) {
+        const int e = idx & 7, lane = (idx >> 3) & 63, m = idx >> 9;
+        const int row = 16 * m + (lane & 15), col = 4 * (lane >> 4) + (e & 3);
+        lds[idx] = MM<CD>::cvt((e < 4 ? w : wsh)[row * 16 + col]);
+    }
+}
+
+template <int CD, bool SIGMA_ONLY, bool DIRS = false>
 __device__ __forceinline__ void field_build_fw(short *lds, const float *__restrict__ p) {
     mm_build_frags<CD>(lds + FW_D1, p + P_D1, 64, 32, 4, 32, false, 0, true);
     mm_build_frags<CD>(lds + FW_D2, p + P_D2, 16, 64, 1, 64, false, 0, true);
@@ -52,8 +80,47 @@ __device__ __forceinline__ void field_build_fw(short *lds, const float *__restri
         mm_build_frags<CD>(lds + FW_K2, p + P_K2, 16, 64, 1, 64, false, CLASS_ROW_SHIFT, true);
         mm_build_frags<CD>(lds + FW_R2, p + P_R2, 64, 64, 4, 64, false, 0, true);
         mm_build_frags<CD>(lds + FW_R3, p + P_R3, 16, 64, 1, 64, false, 0, true);
-        mm_build_frags<CD>(lds + FW_R1, p + P_R1, 64, 16, 4, 16, false, 0, false);
+        if constexpr (DIRS) field_build_r1_dirs<CD>(lds + FW_R1, p + P_R1, p + P_SH);
+        else mm_build_frags<CD>(lds + FW_R1, p + P_R1, 64, 16, 4, 16, false, 0, false);
     }
+}
+
+// Degree-4 spherical harmonics of a viewing direction, tiny-cuda-nn's SphericalHarmonics encoding: the reference feeds
+// u = (d + 1) / 2 and the encoder maps back with 2u - 1, both in fp32.  Returns coefficients 4g .. 4g+3.
+__device__ __forceinline__ f4v field_sh4(int g, float d0, float d1, float d2) {
+#pragma clang fp contract(off)      // the same bits in every kernel that inlines this
+    const float x = 2.0f * ((d0 + 1.0f) / 2.0f) - 1.0f, y = 2.0f * ((d1 + 1.0f) / 2.0f) - 1.0f, z = 2.0f * ((d2 + 1.0f) / 2.0f) - 1.0f;
+    const float xx = x * x, yy = y * y, zz = z * z;
+    f4v r;
+    if (g == 0) {
+        r[0] = 0.28209479177387814f;
+        r[1] = -0.48860251190291987f * y;
+        r[2] = 0.48860251190291987f * z;
+        r[3] = -0.48860251190291987f * x;
+    } else if (g == 1) {
+        r[0] = 1.0925484305920792f * (x * y);
+        r[1] = -1.0925484305920792f * (y * z);
+        r[2] = 0.94617469575755997f * zz - 0.31539156525251999f;
+        r[3] = -1.0925484305920792f * (x * z);
+    } else if (g == 2) {
+        r[0] = 0.54627421529603959f * (xx - yy);
+        r[1] = 0.59004358992664352f * y * (-3.0f * xx + yy);
+        r[2] = 2.8906114426405538f * (x * y) * z;
+        r[3] = 0.45704579946446572f * y * (1.0f - 5.0f * zz);
+    } else {
+        r[0] = 0.3731763325901154f * z * (5.0f * zz - 3.0f);
+        r[1] = 0.45704579946446572f * x * (1.0f - 5.0f * zz);
+        r[2] = 1.4453057213202769f * z * (xx - yy);
+        r[3] = 0.59004358992664352f * x * (-xx + 3.0f * yy);
+    }
+    return r;
+}
+// the same four coefficients as the upper half of color2's K = 32 B fragment (rounded to the compute type: the MLP contract)
+template <int CD>
+__device__ __forceinline__ s4v field_sh_frag(const float *__restrict__ dirs, uint32_t m, bool valid, int g) {
+    float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+    if (valid) { d0 = dirs[(size_t)m * 3 + 0]; d1 = dirs[(size_t)m * 3 + 1]; d2 = dirs[(size_t)m * 3 + 2]; }
+    return mm_round4<CD, false>(field_sh4(g, d0, d1, d2));
 }
 
 // Encoder input of a world position: BBox.normalize (common.py:276-288) then GridEncoder's
@@ -299,8 +366,9 @@ __device__ __forceinline__ f4v field_density_net(const short *wl, int lane, s8v 
 }
 
 // class, color1 and color2 nets on the colour features: rgb rows 0..2 (before the sigmoid), class rows 3..3+nc-1
-template <int CD>
-__device__ __forceinline__ void field_colour_nets(const short *wl, int lane, s8v xc, f4v &rgb_out, f4v &cls_out) {
+// DIRS: color2's first layer is the K = 32 product over cat(color1 output, shb) -- the same four MFMAs on the wider instruction
+template <int CD, bool DIRS = false>
+__device__ __forceinline__ void field_colour_nets(const short *wl, int lane, s8v xc, f4v &rgb_out, f4v &cls_out, s4v shb = s4v{}) {
     f4v h[4];
     s8v hb[2];
     // ---- class net: 32 -> 64 -> nc (rows 3..) -----------------------------------------
@@ -323,7 +391,12 @@ __device__ __forceinline__ void field_colour_nets(const short *wl, int lane, s8v
     f4v rgb[1];
     {
         const s4v c1b = mm_round4<CD, false>(c1[0]);
-        mm_layer16<CD, 4>(wl + FW_R1, lane, c1b, h);
+        if constexpr (DIRS) {
+            const s8v b1[1] = {mm_cat(c1b, shb)};
+            mm_layer32<CD, 4, 1>(wl + FW_R1, lane, b1, h);
+        } else {
+            mm_layer16<CD, 4>(wl + FW_R1, lane, c1b, h);
+        }
         mm_pack64<CD, true, true>(h, hb);
         mm_layer32<CD, 4, 2>(wl + FW_R2, lane, hb, h);
         mm_pack64<CD, true, true>(h, hb);

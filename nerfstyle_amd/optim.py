@@ -15,7 +15,7 @@ the counters and the state dicts.  A subclass adds its storage, `step()`, `_full
 import torch
 
 from . import _lib as L
-from .style_nerf import MLP_LAYOUT, StyleTCNerf
+from .style_nerf import MLP_LAYOUT, SH_LEN, SH_OFF, StyleTCNerf
 
 
 def select_regions(model: StyleTCNerf, keywords=None):
@@ -24,6 +24,8 @@ def select_regions(model: StyleTCNerf, keywords=None):
         return keywords is None or any(kw in name for kw in keywords)
     mask = (0x3 if on('x_density_embedder.embeddings') else 0) | (0xC if on('x_color_embedder.embeddings') else 0)
     nets = [(off, n) for (name, off, n) in MLP_LAYOUT if on(name + '.params')]
+    if model.use_dir and on('color2_net.params'):
+        nets.append((SH_OFF, SH_LEN))        # a view-dependent model's color2_net has a second block: its SH columns
     if mask == 0 and not nets:
         raise ValueError('Keywords {} not found in parameter names'.format(keywords))
     return mask, nets
@@ -42,6 +44,9 @@ def reference_state(model: StyleTCNerf, table_mask, nets, optim_sd, ema_sd=None)
     trainers/base.py:185-221) and torch_ema's state_dict ({'decay', 'num_updates', 'shadow_params': [...]}, over ALL
     model parameters, base.py:229) -> full-layout (arena-shaped, host) 'exp_avg', 'exp_avg_sq' and 'ema' (None without
     shadow parameters), 'step', 'ema_updates', and 'lr' / 'initial_lr' (None where the state does not give them)."""
+    if model.use_dir:
+        raise NotImplementedError('reference optimiser state for a view_dependent model: color2_net.params is stored as two '
+                                  'arena blocks, the conversion is not written')
     trained = set(off for off, _ in nets)
     names = []
     if table_mask & 0x3:
@@ -175,7 +180,7 @@ class FusedAdam(AdamBase):
         """[(offset, n, elem_mask4, half_n)] of the arena the optimiser trains, merged where contiguous: everything trained
         (the reconstruction stage) is ONE launch over the whole arena, colour table only (stylisation) is one over the tables."""
         m = self.model
-        all_nets = len(self.nets) == len(MLP_LAYOUT)
+        all_nets = len(self.nets) == len(MLP_LAYOUT) + int(m.use_dir)
         if self.table_mask == 0xF and all_nets:
             return [(0, m.arena.numel(), 0xF, m.table_elems)]
         out = []
@@ -192,7 +197,7 @@ class FusedAdam(AdamBase):
         if not self.table_mask:
             g[:m.table_elems].zero_()
         trained = {off for (off, n) in self.nets}
-        for (name, off, n) in MLP_LAYOUT:
+        for (name, off, n) in MLP_LAYOUT + ((('color2_net', SH_OFF, SH_LEN),) if m.use_dir else ()):
             if off not in trained:
                 g[m.table_elems + off: m.table_elems + off + n].zero_()
 

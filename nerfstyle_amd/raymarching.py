@@ -96,10 +96,15 @@ def march_rays_train_nosync(rays_o, rays_d, bound, density_bitfield, C, H, nears
     N = rays_o.shape[0]
     dev = rays_o.device
     if out is not None:
-        # caller-owned sample buffers (xyzs [M,3], deltas [M,4] f32, rays [N,3] i32), e.g. the static buffers of a captured step
-        xyzs, deltas, rays = out
-        assert xyzs.shape == (M, 3) and deltas.shape == (M, 4) and rays.shape == (N, 3) and not want_dirs
-        dirs = None
+        # caller-owned sample buffers (xyzs [M,3], deltas [M,4] f32, rays [N,3] i32, and with want_dirs a fourth, dirs [M,3]
+        # f32), e.g. the static buffers of a captured step
+        if want_dirs:
+            xyzs, deltas, rays, dirs = out
+            assert dirs.shape == (M, 3) and dirs.dtype == torch.float32 and dirs.is_contiguous()
+        else:
+            xyzs, deltas, rays = out
+            dirs = None
+        assert xyzs.shape == (M, 3) and deltas.shape == (M, 4) and rays.shape == (N, 3)
     else:
         xyzs = torch.empty(M, 3, dtype=torch.float32, device=dev)
         dirs = torch.empty(M, 3, dtype=torch.float32, device=dev) if want_dirs else None

@@ -208,6 +208,8 @@ class Renderer(torch.nn.Module):
         """renderer.py:196-235 -> (image [N,3], depth [N], classes [N,nc]).  Three stages that graph.GraphedPatchBackward
         also drives one by one: march (sync-free), optional spatial order of the samples, shade (field + composite).
         With `fused_nograd_train` set and autograd off the call is render_train_fused instead (non-NDC, all model channels)."""
+        if self.fused_nograd_train and self.model.use_dir:
+            raise NotImplementedError('fused_nograd_train: the streaming kernel has no direction input (view_dependent model)')
         if (self.fused_nograd_train and not torch.is_grad_enabled() and not self.cfg.use_ndc
                 and self.raymarch_channels == self.model.out_channels):
             return self.render_train_fused(rays, dense_shape=kwargs.get('dense_shape'))
@@ -231,9 +233,11 @@ class Renderer(torch.nn.Module):
             N, M = into['N'], into['M']
             assert rays.origins.shape[0] == N
             self._last_capacity = M
+            want_dirs = into.get('dirs') is not None          # a view-dependent model: the samples' directions, a static buffer too
             raymarching.march_rays_train_nosync(
                 rays.origins, rays.dirs, self.bound, self.march_bitfield, self.cascade, self.cfg.grid_size, nears, fars,
-                M, counter, 0., self.cfg.max_steps, out=(into['xyzs'], into['deltas'], into['rays_info']))
+                M, counter, 0., self.cfg.max_steps, want_dirs=want_dirs,
+                out=(into['xyzs'], into['deltas'], into['rays_info']) + ((into['dirs'],) if want_dirs else ()))
             if self.update_occ:
                 # the step bookkeeping of the allocating path: the count ring behind mean_count, the occupancy schedule's step
                 self.step_counter[self.local_step % STEP_CTR_SIZE].copy_(counter)
@@ -251,17 +255,17 @@ class Renderer(torch.nn.Module):
         N = rays.origins.shape[0]
         M = self.sample_capacity(N)
         self._last_capacity = M
-        xyzs, _, deltas, rays_info = raymarching.march_rays_train_nosync(
+        xyzs, dirs, deltas, rays_info = raymarching.march_rays_train_nosync(
             rays.origins, rays.dirs, self.bound, self.march_bitfield, self.cascade, self.cfg.grid_size, nears, fars,
-            M, counter, 0., self.cfg.max_steps)
+            M, counter, 0., self.cfg.max_steps, want_dirs=self.model.use_dir)
         return {'N': N, 'M': M, 'nears': nears, 'fars': fars, 'counter': counter, 'xyzs': xyzs, 'deltas': deltas,
-                'rays_info': rays_info}
+                'rays_info': rays_info, 'dirs': dirs}
 
     def shade_train(self, mt: dict, perm=None):
         """fused field on the marched samples + train composite with the epilogue of renderer.py:225-233 folded in
         (nsr_render_train_forward / _backward): two autograd nodes, no torch glue between them"""
         sigmas, rgbs = self.model.field(mt['xyzs'], sigma_only=False, m_dev=mt['counter'], density_scale=self.cfg.density_scale,
-                                        perm=perm)
+                                        perm=perm, dirs=mt.get('dirs'))
         image, depth, classes, _ = _render_train(sigmas, rgbs, mt['deltas'], mt['rays_info'], mt['nears'], mt['fars'],
                                                  self.cfg.t_thresh)
         return image, depth, classes
@@ -325,9 +329,9 @@ class Renderer(torch.nn.Module):
         N = rays.origins.shape[0]
         M = self.sample_capacity(N)
         counter = torch.zeros(2, dtype=torch.int32, device=self.device)
-        xyzs, _, deltas, rays_info = raymarching.march_rays_train_nosync(
+        xyzs, dirs, deltas, rays_info = raymarching.march_rays_train_nosync(
             rays.origins, rays.dirs, self.bound, self.march_bitfield, self.cascade, self.cfg.grid_size, nears, fars,
-            M, counter, 0., self.cfg.max_steps)
+            M, counter, 0., self.cfg.max_steps, want_dirs=self.model.use_dir)
         if self.samples_per_ray_cap is not None and self.samples_per_ray_cap < self.cfg.max_steps:
             # a bounded buffer can overflow, and the march then DROPS the rays that do not fit (raymarching.cu:517);
             # the reference's inference loop never drops a ray, so fall back to its iteration structure.  One host read
@@ -335,7 +339,7 @@ class Renderer(torch.nn.Module):
             self.last_test_overflow = int(counter[0].item()) >= M
             if self.last_test_overflow:
                 return self.render_test_loop(rays, **kwargs)
-        sigmas, rgbs = self.model.field(xyzs, sigma_only=False, m_dev=counter, density_scale=self.cfg.density_scale)
+        sigmas, rgbs = self.model.field(xyzs, sigma_only=False, m_dev=counter, density_scale=self.cfg.density_scale, dirs=dirs)
         C = self.raymarch_channels
         weights_sum = torch.empty(N, dtype=torch.float32, device=self.device)
         depth = torch.empty(N, dtype=torch.float32, device=self.device)
@@ -357,6 +361,8 @@ class Renderer(torch.nn.Module):
         w x h window, walked in 8 x 8 tiles so that the 16 rays a wave holds are neighbours; anything else in batch order."""
         import ctypes
         from . import _lib as L
+        if self.model.use_dir:
+            raise NotImplementedError('fused_inference: the streaming kernel has no direction input (view_dependent model)')
         nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
         if self.cfg.use_ndc:
             raise NotImplementedError('render_test_fused: NDC scenes march through render_test / render_test_loop')
@@ -403,6 +409,8 @@ class Renderer(torch.nn.Module):
         march of render_train counts every emitted sample.  dense_shape: as for render_test_fused."""
         import ctypes
         from . import _lib as L
+        if self.model.use_dir:
+            raise NotImplementedError('fused_nograd_train: the streaming kernel has no direction input (view_dependent model)')
         if self.cfg.use_ndc:
             raise NotImplementedError('render_train_fused: NDC scenes render through the buffered render_train')
         if self.occupancy_update_due():
@@ -461,10 +469,11 @@ class Renderer(torch.nn.Module):
             if n_alive <= 0:
                 break
             n_step = max(min(N // n_alive, 8), 1)
-            xyzs, _, deltas = raymarching.march_rays(
+            xyzs, dirs, deltas = raymarching.march_rays(
                 n_alive, n_step, rays_alive, rays_t, rays.origins, rays.dirs, None, self.bound, self.march_bitfield,
                 self.cascade, self.cfg.grid_size, nears, fars, 128, False, 0., self.cfg.max_steps, self.cfg.use_ndc)
-            sigmas, rgbs = self.model.field(xyzs, sigma_only=False, density_scale=self.cfg.density_scale)
+            sigmas, rgbs = self.model.field(xyzs, sigma_only=False, density_scale=self.cfg.density_scale,
+                                            dirs=dirs if self.model.use_dir else None)
             raymarching.composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, self.cfg.use_ndc,
                                        weights_sum, depth, image, self.cfg.t_thresh)
             raymarching.compact_alive(rays_alive, n_alive, rays_alive_next, n_out)

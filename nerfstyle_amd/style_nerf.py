@@ -31,6 +31,11 @@ from .gridencoder import GridEncoder
 from .network import init_mlp_params
 
 MLP_PARAMS = 15360
+# view-dependent models: color2's first layer is [64, 32] = [color1 | SH]; its SH columns are a row-major [64, 16] block
+# appended to the MLP block, so that every offset below holds for both kinds of model
+MLP_PARAMS_DIRS = 16384
+SH_OFF, SH_LEN = 15360, 1024
+COLOR2_OFF, COLOR2_LEN, COLOR2_LEN_DIRS = 6144, 6144, 7168
 # (name, offset in the MLP block, length); order fixed by include/nsr.h
 MLP_LAYOUT = (('density_net', 0, 3072), ('color1_net', 3072, 3072), ('color2_net', 6144, 6144),
               ('class_net', 12288, 3072))
@@ -74,8 +79,13 @@ class _field(Function):
     is arena.grad) and returns None for it."""
 
     @staticmethod
-    def forward(ctx, xyzs, arena, model, sigma_only, m_dev, density_scale, want_feats=False, perm=None):
+    def forward(ctx, xyzs, arena, model, sigma_only, m_dev, density_scale, want_feats=False, perm=None, dirs=None):
         xyzs = xyzs.detach().to(torch.float32).contiguous()
+        if dirs is not None:
+            dirs = dirs.detach().to(torch.float32).reshape(-1, 3).contiguous()
+            assert dirs.shape[0] == xyzs.shape[0], 'one direction per sample'
+        if model.use_dir and not sigma_only and dirs is None:
+            raise ValueError('a view_dependent StyleTCNerf needs the samples\' directions: field(pts, dirs=...)')
         M = xyzs.shape[0]
         dev = xyzs.device
         sigmas = torch.empty(M, dtype=torch.float32, device=dev)
@@ -88,17 +98,24 @@ class _field(Function):
         if (not sigma_only) and want_feats:
             feats = torch.empty(((M + 15) // 16) * 512, dtype=torch.int32, device=dev)
         with profiling.timed('field_fwd_sigma' if sigma_only else 'field_fwd'):
-            L.check(L.lib().nsr_field_forward(ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()),
-                                              L.p(xyzs), M, L.p(m_dev), L.p(sigmas), L.p(rgbs), L.p(feats),
-                                              L.p(perm) if feats is not None else None, L.stream()),
-                    'field_forward')
+            if model.use_dir and not sigma_only:
+                L.check(L.lib().nsr_field_forward_dirs(ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()),
+                                                       L.p(xyzs), M, L.p(m_dev), L.p(sigmas), L.p(rgbs), L.p(feats),
+                                                       L.p(perm) if feats is not None else None, L.p(dirs), L.stream()),
+                        'field_forward_dirs')
+            else:
+                dirs = None
+                L.check(L.lib().nsr_field_forward(ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()),
+                                                  L.p(xyzs), M, L.p(m_dev), L.p(sigmas), L.p(rgbs), L.p(feats),
+                                                  L.p(perm) if feats is not None else None, L.stream()),
+                        'field_forward')
         ctx.model = model
         ctx.m_dev = m_dev
         ctx.density_scale = density_scale
         ctx.sigma_only = sigma_only
         # feats (15.6 GB at a full-frame capacity) and perm go through save_for_backward, NOT ctx attributes: autograd
         # drops saved tensors when backward() has run, attributes live as long as anything still holds the loss
-        ctx.save_for_backward(xyzs, feats, perm)
+        ctx.save_for_backward(xyzs, feats, perm, dirs)
         if sigma_only:
             return sigmas
         return sigmas, rgbs
@@ -106,7 +123,7 @@ class _field(Function):
     @staticmethod
     def backward(ctx, grad_sigmas, grad_rgbs=None):
         model = ctx.model
-        xyzs, feats, perm = ctx.saved_tensors
+        xyzs, feats, perm, dirs = ctx.saved_tensors
         M = xyzs.shape[0]
         dev = xyzs.device
         if grad_sigmas is None:
@@ -134,11 +151,12 @@ class _field(Function):
                     ws = model._bwd_ws = torch.empty(need, dtype=torch.float32, device=dev)
         with profiling.timed('field_bwd'):
             def call(perm, wsp):
-                return L.lib().nsr_field_backward(
-                    ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()), L.p(xyzs), M, L.p(ctx.m_dev),
-                    L.p(grad_sigmas), L.p(grad_rgbs), L.p(ga), (ga.data_ptr() + model.table_elems * 4) if model.train_mlps else None,
-                    int(model.train_density_table), int(model.train_color_table), L.p(feats), L.p(perm), L.p(wsp),
-                    L.stream())
+                args = (ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()), L.p(xyzs), M, L.p(ctx.m_dev),
+                        L.p(grad_sigmas), L.p(grad_rgbs), L.p(ga), (ga.data_ptr() + model.table_elems * 4) if model.train_mlps else None,
+                        int(model.train_density_table), int(model.train_color_table), L.p(feats), L.p(perm), L.p(wsp))
+                if dirs is not None:
+                    return L.lib().nsr_field_backward_dirs(*args, L.p(dirs), L.stream())
+                return L.lib().nsr_field_backward(*args, L.stream())
             st = call(perm, ws)
             if st == -2 and perm is not None:
                 feats = None             # saved in the permutation's order: useless to a kernel that walks the buffers
@@ -147,7 +165,7 @@ class _field(Function):
                 model._spatial_scatter_unsupported = True
                 st = call(None, None)
             L.check(st, 'field_backward')
-        return None, None, None, None, None, None, None, None
+        return None, None, None, None, None, None, None, None, None
 
 
 class _EncoderView(nn.Module):
@@ -182,21 +200,72 @@ class _NetView(nn.Module):
         return o.arena.detach()[o.table_elems + self._off: o.table_elems + self._off + self._n]
 
 
+class _Color2DirsView(_NetView):
+    """color2_net of a view-dependent model: `params` is the reference-shaped (7168,) vector, ASSEMBLED from the arena's two
+    blocks (a copy, not a view; write through load_state_dict)."""
+
+    @property
+    def params(self):
+        return self._owner.views_of(self._owner.arena.detach())['color2_net.params']
+
+
+def color2_assemble(block, sh):
+    """arena blocks -> reference-shaped color2 vector: first layer row-major [64, 32] = [color1 columns | SH columns]."""
+    first = torch.cat((block[:1024].view(64, 16), sh.view(64, 16)), dim=1).reshape(-1)
+    return torch.cat((first, block[1024:]))
+
+
+def color2_split(vec):
+    """reference-shaped (7168,) color2 vector -> (arena block (6144,), SH columns (1024,))"""
+    first = vec[:2048].view(64, 32)
+    return torch.cat((first[:, :16].reshape(-1), vec[2048:])), first[:, 16:].reshape(-1)
+
+
+class SHEncoder(nn.Module):
+    """The tcnn.Encoding({'otype': 'SphericalHarmonics', 'degree': 4}) stand-in: [M,3] inputs u = (d + 1) / 2 in [0,1] (what the
+    reference feeds it) -> [M,16] fp32 coefficients (nsr_sh_encode).  Forward only: no direction gradient exists on this path."""
+
+    def __init__(self, degree=4):
+        super().__init__()
+        if degree != 4:
+            raise NotImplementedError('SHEncoder: only degree 4 (16 coefficients) is built, got {}'.format(degree))
+        self.n_input_dims, self.n_output_dims = 3, 16
+
+    @torch.no_grad()
+    def forward(self, u):
+        return self.encode_dirs(u.detach().to(torch.float32) * 2 - 1)
+
+    @staticmethod
+    @torch.no_grad()
+    def encode_dirs(dirs):
+        """The same, from the directions themselves (the kernels' input)."""
+        dirs = dirs.detach().to(torch.float32).reshape(-1, 3).contiguous()
+        out = torch.empty(dirs.shape[0], 16, dtype=torch.float32, device=dirs.device)
+        L.check(L.lib().nsr_sh_encode(L.p(dirs), dirs.shape[0], L.p(out), L.stream()), 'sh_encode')
+        return out
+
+
 class StyleTCNerf(nn.Module):
     def __init__(self, cfg: NetworkConfig, bbox: BBox, class_dim: int, enc_dtype=None, use_dir: bool = False,
-                 compute_dtype=torch.float16, device=None):
+                 compute_dtype=torch.float16, device=None, view_dependent: bool = False):
         """enc_dtype: None -> half gather tables (the reference's AMP behaviour, trainers/base.py:148
-        + grid.py:42-43); torch.float32 -> fp32 tables."""
+        + grid.py:42-43); torch.float32 -> fp32 tables.
+        view_dependent=True: the reference's use_dir=True model -- colour depends on the viewing direction through a
+        degree-4 SH encoding concatenated to color1_net's output (color2_net is 32 -> 64 -> 64 -> 3)."""
         super().__init__()
-        if use_dir:
-            raise NotImplementedError('use_dir=True (SH direction encoding) is off on this path; both reference entry '
-                                      'points pass use_dir=False (trainers/base.py:149-151, render.py:68-69)')
+        if use_dir and not view_dependent:
+            raise NotImplementedError('use_dir=True alone is not accepted: pass view_dependent=True for the SH direction '
+                                      'encoding (both reference entry points pass use_dir=False, trainers/base.py:149-151, '
+                                      'render.py:68-69)')
+        if view_dependent and int(getattr(cfg, 'dir_enc_sh_deg', 4)) != 4:
+            raise NotImplementedError('view_dependent: only cfg.dir_enc_sh_deg == 4 is built, got {}'.format(cfg.dir_enc_sh_deg))
         assert cfg.density_hidden_dims == 64 and cfg.rgb_hidden_dims == 64
         assert cfg.density_hidden_layers == 1 and cfg.rgb_hidden_layers == 2
         assert cfg.pos_enc.n_lvls == 16 and cfg.pos_enc.n_feats_per_lvl == 2
         self.cfg = cfg
         self.bounds_bbox = bbox
-        self.use_dir = False
+        self.use_dir = bool(view_dependent)
+        self.mlp_params = MLP_PARAMS_DIRS if self.use_dir else MLP_PARAMS
         self.class_dim = class_dim
         self.out_channels = 3 + class_dim
         self.compute_dtype = compute_dtype
@@ -215,13 +284,17 @@ class StyleTCNerf(nn.Module):
         self.table_elems = self.rows * 4
 
         # ---- the arena -------------------------------------------------------------------------
-        flat = torch.empty(self.table_elems + MLP_PARAMS, dtype=torch.float32)
+        flat = torch.empty(self.table_elems + self.mlp_params, dtype=torch.float32)
         g = torch.Generator().manual_seed(int(cfg.network_seed or 0))
         flat[:self.table_elems].uniform_(-1e-4, 1e-4, generator=g)   # grid.py:150-152
         seed = int(cfg.network_seed or 0)
+        if self.use_dir:
+            c2, sh = color2_split(init_mlp_params(32, 3, 64, 2, seed + 2))
+        else:
+            c2, sh = init_mlp_params(16, 3, 64, 2, seed + 2), torch.empty(0)
         mlp = torch.cat([
             init_mlp_params(32, 1, 64, 1, seed), init_mlp_params(32, 16, 64, 1, seed + 1),
-            init_mlp_params(16, 3, 64, 2, seed + 2), init_mlp_params(32, class_dim, 64, 1, seed + 3)])
+            c2, init_mlp_params(32, class_dim, 64, 1, seed + 3), sh])
         flat[self.table_elems:] = mlp
         self.arena = nn.Parameter(flat)
         self.grad_arena = None
@@ -232,7 +305,11 @@ class StyleTCNerf(nn.Module):
         self.x_color_embedder = _EncoderView(self, 1, template)
         self.density_net = _NetView(self, 'density_net', 0, 3072, 32, 1)
         self.color1_net = _NetView(self, 'color1_net', 3072, 3072, 32, 16)
-        self.color2_net = _NetView(self, 'color2_net', 6144, 6144, 16, 3)
+        if self.use_dir:
+            self.color2_net = _Color2DirsView(self, 'color2_net', 6144, 6144, 32, 3)
+            self.dir_encoder = SHEncoder(4)
+        else:
+            self.color2_net = _NetView(self, 'color2_net', 6144, 6144, 16, 3)
         self.class_net = _NetView(self, 'class_net', 12288, 3072, 32, class_dim)
         if device is not None:
             self.to(device)
@@ -312,6 +389,10 @@ class StyleTCNerf(nn.Module):
         out = {'x_density_embedder.embeddings': t[:, 0, :], 'x_color_embedder.embeddings': t[:, 1, :]}
         for name, off, n in MLP_LAYOUT:
             out[name + '.params'] = flat[self.table_elems + off: self.table_elems + off + n]
+        if self.use_dir:
+            # the one entry that is a COPY: the reference-shaped vector interleaves two arena blocks
+            out['color2_net.params'] = color2_assemble(out['color2_net.params'],
+                                                       flat[self.table_elems + SH_OFF: self.table_elems + SH_OFF + SH_LEN])
         return out
 
     def state_dict(self, *args, **kwargs):
@@ -321,8 +402,19 @@ class StyleTCNerf(nn.Module):
         return sd
 
     def load_state_dict(self, sd, strict=True):
+        n2 = sd['color2_net.params'].numel()
+        if n2 != (COLOR2_LEN_DIRS if self.use_dir else COLOR2_LEN):
+            raise ValueError('color2_net.params has {} entries, this model (view_dependent={}) holds {}: a checkpoint of a '
+                             'view_dependent={} model loads only into a model built with that switch'.format(
+                                 n2, self.use_dir, COLOR2_LEN_DIRS if self.use_dir else COLOR2_LEN, n2 == COLOR2_LEN_DIRS))
         with torch.no_grad():
-            for name, v in self.views_of(self.arena.detach()).items():
+            flat = self.arena.detach()
+            for name, v in self.views_of(flat).items():
+                if self.use_dir and name == 'color2_net.params':
+                    block, sh = color2_split(sd[name].reshape(-1).to(flat))
+                    flat[self.table_elems + COLOR2_OFF: self.table_elems + COLOR2_OFF + COLOR2_LEN].copy_(block)
+                    flat[self.table_elems + SH_OFF: self.table_elems + SH_OFF + SH_LEN].copy_(sh)
+                    continue
                 v.copy_(sd[name].reshape(v.shape))
             self.arena.add_(0)   # bump the version counter: the half copy is stale
         return self
@@ -332,13 +424,13 @@ class StyleTCNerf(nn.Module):
         return list(self.views_of(self.arena.detach()).items())
 
     # ---- forward -------------------------------------------------------------------------------
-    def field(self, pts, sigma_only=False, m_dev=None, density_scale=1.0, perm=None):
+    def field(self, pts, sigma_only=False, m_dev=None, density_scale=1.0, perm=None, dirs=None):
         """Fast path: flat sigmas [M] (and rgbs [M,3+nc]); m_dev = device int32 sample count; perm = spatial order from
         `sample_order` (int32 [M] device tensor): a training forward then walks the samples in that order (its saved features
         are tile-major in it) and the backward follows -- MLP chain first, then the table gradient with the stand-alone
         lattice scatter kernel (same result per sample, table gradient up to fp32 summation order; pays on dense batches)."""
         want_feats = bool(self.save_features and torch.is_grad_enabled() and self.arena.requires_grad and not sigma_only)
-        return _field.apply(pts, self.arena, self, sigma_only, m_dev, density_scale, want_feats, perm)
+        return _field.apply(pts, self.arena, self, sigma_only, m_dev, density_scale, want_feats, perm, dirs)
 
     @torch.no_grad()
     def density_gradient(self, pts, m_dev=None, density_scale=1.0, normalize=False):
@@ -385,5 +477,5 @@ class StyleTCNerf(nn.Module):
         pts = pts.reshape(-1, 3)
         if dirs is None:
             return self.field(pts, sigma_only=True).unsqueeze(-1)
-        sigmas, rgbs = self.field(pts, sigma_only=False)
+        sigmas, rgbs = self.field(pts, sigma_only=False, dirs=dirs.reshape(-1, 3) if self.use_dir else None)
         return rgbs, sigmas.unsqueeze(-1)
