@@ -93,7 +93,9 @@ __device__ __forceinline__ void field_tr6p(const s8v (&x)[2], s4v y, s4v z, s4v 
 // stream (11.7 -> 10.7 ms); the backward's ReLU masks on packed 16-bit pairs (1412 -> 1304 instructions per tile, 10.6 ->
 // 10.0 ms); the wgrad operand transposes as pipelines of four identity MFMAs in flight, the wgrad MFMAs in blocks of four
 // with one wait-state pad, the mask chain one instruction shorter (1254 -> 1114 instructions, 158 -> 59 no-ops per tile,
-// 10.43 -> 9.56 ms; DESIGN.md "(r5)").  An 8-deep queue for the two 8-fragment layers: no change.  The wgrad operand
+// 10.43 -> 9.56 ms; DESIGN.md "(r5)"); the wave index, and with it the tile counter and the prefetch conditions, in scalar
+// registers, lanes past the count masked by selects instead of EXEC regions, the next tile requested unconditionally (1095 ->
+// 996 instructions, 23 -> 5 EXEC regions, 9.59 -> 9.29 ms; DESIGN.md "(r9)").  An 8-deep queue for the two 8-fragment layers: no change.  The wgrad operand
 // transposes through LDS (ds_write_b64 + ds_read_b64_tr_b16, 49 per tile) instead of an MFMA with the identity +
 // re-rounding: 1304 -> 1240 instructions per tile and the same time (21.4 vs 21.5 ms for the pair) -- the LDS round trips
 // cost what the MFMAs did.
@@ -115,7 +117,10 @@ k_field_bwd_gout(FieldBwdArgsOf<DIRS> b) {
 
     const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
     const uint32_t ntiles = (Mc + 15) / 16;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // The wave index is read through one lane: the compiler cannot tell that threadIdx.x >> 6 is the same for a wave's 64
+    // lanes, and with it per-lane the tile counter, the loop's back edge and the `is there a next tile` test all ran as
+    // EXEC-masked regions on vector registers (DESIGN.md "(r9)").
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int s = lane & 15, g = lane >> 4;
     const TT *tables = reinterpret_cast<const TT *>(a.tables);
     const uint32_t lb = field_logical_block();
@@ -205,6 +210,17 @@ k_field_bwd_gout(FieldBwdArgsOf<DIRS> b) {
         }
         gout_valid = false;
     };
+    // Which of this lane's four output channels (4g + e) exist, and which of them are colours (sigmoid) or class logits:
+    // per-launch constants.  The loop selects with them and runs no EXEC-masked region for a sample past the count: such a
+    // lane computes on the (valid) sample its clamped index names and every value it could contribute is selected to zero.
+    bool ch_on[4], ch_rgb[4], ch_cls[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const int ch = 4 * g + e;
+        ch_on[e] = a.C_ch == 8 ? g < 2 : (uint32_t)ch < a.C_ch;
+        ch_rgb[e] = (uint32_t)ch < a.C_ch && ch < 3;
+        ch_cls[e] = (uint32_t)ch < a.C_ch && ch >= 3;
+    }
     // weight-fragment queue of the MLP section (mfma_tiles.h, mm_queue32): holds the next layer's first four fragments
     s8v wq[4];
     s4v wq16[4];
@@ -224,25 +240,20 @@ k_field_bwd_gout(FieldBwdArgsOf<DIRS> b) {
         // DIRS: this tile's direction is requested here, not a tile ahead with the other inputs (three registers the 64
         // accumulator tiles do not leave): its first use, color2's first layer, is four layers away
         float dv[3] = {0.f, 0.f, 0.f};
-        if constexpr (DIRS) {
-            if (valid) { dv[0] = dirs[(size_t)idx_cur * 3 + 0]; dv[1] = dirs[(size_t)idx_cur * 3 + 1]; dv[2] = dirs[(size_t)idx_cur * 3 + 2]; }
-        }
-        const float u0 = valid ? field_unit(cur.x0, a.bmin[0], a.bsize[0]) : 0.f;
-        const float u1 = valid ? field_unit(cur.x1, a.bmin[1], a.bsize[1]) : 0.f;
-        const float u2 = valid ? field_unit(cur.x2, a.bmin[2], a.bsize[2]) : 0.f;
+        // (idx_cur is a valid index on every lane: a lane past the count reads a direction it does not use)
+        if constexpr (DIRS) { dv[0] = dirs[(size_t)idx_cur * 3 + 0]; dv[1] = dirs[(size_t)idx_cur * 3 + 1]; dv[2] = dirs[(size_t)idx_cur * 3 + 2]; }
+        // the u of a lane past the count are those of the sample it read instead; `live` alone says whether they are used
+        const float u0 = field_unit(cur.x0, a.bmin[0], a.bsize[0]);
+        const float u1 = field_unit(cur.x1, a.bmin[1], a.bsize[1]);
+        const float u2 = field_unit(cur.x2, a.bmin[2], a.bsize[2]);
         const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);   // NaN -> zeros too
         const float cur_gsig = valid ? cur.gsig : 0.f;
         float cur_grgb[4];
 #pragma unroll
-        for (int e = 0; e < 4; e++)
-            cur_grgb[e] = (valid && (a.C_ch == 8 ? g < 2 : (uint32_t)(4 * g + e) < a.C_ch)) ? cur.grgb[e] : 0.f;
+        for (int e = 0; e < 4; e++) cur_grgb[e] = (valid && ch_on[e]) ? cur.grgb[e] : 0.f;
         // no saved features: gather them now (dependent loads, the slow path)
         if (!FEATS) field_encode<TT, CD, false>(lds_lv, tables, u0, u1, u2, live, g, cur.xd, cur.xc, a.fast_levels);
 
-        // (value-initialised, NOT a copy of cur: copying cur's not-yet-used members here would wait for their loads,
-        // and -- one in-order vmcnt -- for the gradient stores issued in between)
-        TileIn nxt{};
-        uint32_t idx_nn = idx_next;
         f4v gxd[2], gxc[2];        // d L / d (density, colour) features of this lane's levels
         // ================= recompute forward, keeping rounded activations ====================
         s8v xd[1] = {cur.xd}, xc[1] = {cur.xc};
@@ -255,10 +266,10 @@ k_field_bwd_gout(FieldBwdArgsOf<DIRS> b) {
         // There is no scatter between the end of the MLP section and the loop edge: loads issued there are waited for at
         // once (SQ_WAIT_ANY = 51 % of the wave's cycles, profiles/).  The next tile's inputs are requested HERE instead, a
         // whole MLP section ahead, at the price of 16 registers held through it.
-        if (tile + 1 < w_end) {
-            nxt = load_tile(tile + 1, idx_next);
-            if (tile + 2 < w_end) idx_nn = fetch_idx(tile + 2);
-        }
+        // The wave's last tile requests itself again (idx_next is then idx_cur, the index two ahead any clamped one): a few
+        // loads nobody uses, once per wave, instead of a branch and sixteen zeroed registers in every tile.
+        const TileIn nxt = load_tile(min(tile + 1, w_end - 1), idx_next);
+        const uint32_t idx_nn = fetch_idx(min(tile + 2, w_end - 1));
         mm_pack64<CD, true, true>(h, hd);
         mm_layer32_q<CD, 1, 2>(wq, wl + FW_D2, lane, hd, logit);
         mm_queue32<4>(wq, wl + FW_K1, lane);
@@ -291,26 +302,25 @@ k_field_bwd_gout(FieldBwdArgsOf<DIRS> b) {
         // ================= upstream gradients in B-fragment form (row = 4g + e) ===============
         s4v dyd, dyr, dyk;
         {
+            // Every lane evaluates the derivatives of its row and SELECTS: the same expressions on the lanes that keep them,
+            // zero on the others (rows that are no colour, lanes past the count), and no EXEC-masked region.  Only rows
+            // 0..2 can be colours, so element 3 has no sigmoid.
             float gd[4] = {0.f, 0.f, 0.f, 0.f}, gr[4] = {0.f, 0.f, 0.f, 0.f}, gk[4] = {0.f, 0.f, 0.f, 0.f};
-            if (valid) {
-                if (g == 0) {
-                    // sigma = exp(logit) * density_scale; trunc_exp backward clamps (tcnn_nerf.py:62-66)
-                    const float x = logit[0][0];
-                    gd[0] = cur_gsig * a.density_scale * expf(fminf(fmaxf(x, -15.0f), 15.0f));
-                }
+            {
+                // sigma = exp(logit) * density_scale; trunc_exp backward clamps (tcnn_nerf.py:62-66)
+                const float x = logit[0][0];
+                const float d = cur_gsig * a.density_scale * expf(fminf(fmaxf(x, -15.0f), 15.0f));
+                gd[0] = (valid && g == 0) ? d : 0.f;
+            }
 #pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const int ch = 4 * g + e;
-                    if ((uint32_t)ch < a.C_ch) {
-                        const float gv = cur_grgb[e];
-                        if (ch < 3) {
-                            const float sg = field_sigmoid(rgb[0][e]);
-                            gr[e] = gv * sg * (1.0f - sg);
-                        } else {
-                            gk[e] = gv;
-                        }
-                    }
+            for (int e = 0; e < 4; e++) {
+                const float gv = cur_grgb[e];
+                if (e < 3) {
+                    const float sg = field_sigmoid(rgb[0][e]);
+                    const float d = gv * sg * (1.0f - sg);
+                    gr[e] = (valid && ch_rgb[e]) ? d : 0.f;
                 }
+                gk[e] = (valid && ch_cls[e]) ? gv : 0.f;
             }
 #pragma unroll
             for (int e = 0; e < 4; e++) { dyd[e] = MM<CD>::cvt(gd[e]); dyr[e] = MM<CD>::cvt(gr[e]); dyk[e] = MM<CD>::cvt(gk[e]); }
