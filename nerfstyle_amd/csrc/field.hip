@@ -334,29 +334,32 @@ static int field_launch_fwd(const FieldArgs &a, uint32_t nblocks, bool sigma_onl
     return nsr_launch_status();
 }
 
-extern "C" {
-
-int nsr_field_forward(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *xyzs, uint32_t M,
-                      const int32_t *m_dev, float *sigmas, float *rgbs, void *feats, const uint32_t *perm, nsr_stream_t stream) {
+// the one launcher behind nsr_field_forward and nsr_field_forward_dirs (dirs != NULL: the direction-taking instantiations)
+static int field_forward_any(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *xyzs, uint32_t M,
+                             const int32_t *m_dev, float *sigmas, float *rgbs, void *feats, const uint32_t *perm, const float *dirs,
+                             nsr_stream_t stream) {
     if (M == 0) return NSR_OK;
     NSR_CHECK_PTR(desc); NSR_CHECK_PTR(tables); NSR_CHECK_PTR(mlp_params); NSR_CHECK_PTR(xyzs); NSR_CHECK_PTR(sigmas);
     FieldArgs a;
     uint32_t nblocks;
-    const int st = field_fill_args(desc, a, M, nblocks);
+    const int st = field_fill_args(desc, tables, mlp_params, a, M, nblocks);
     if (st != NSR_OK) return st;
-    if ((uintptr_t)tables & 15u) return NSR_ERR_INVALID_ARG;
     if (rgbs && a.C_ch == 8 && ((uintptr_t)rgbs & 15u)) return NSR_ERR_INVALID_ARG;
-    a.tables = tables; a.params = mlp_params; a.xyzs = xyzs; a.m_dev = m_dev; a.sigmas = sigmas; a.rgbs = rgbs;
-    a.feats = feats;
-    a.perm = perm;
     if (feats && ((uintptr_t)feats & 15u)) return NSR_ERR_INVALID_ARG;
+    a.xyzs = xyzs; a.m_dev = m_dev; a.sigmas = sigmas; a.rgbs = rgbs; a.feats = feats; a.perm = perm;
     const bool so = rgbs == nullptr;
     hipStream_t s = (hipStream_t)stream;
-    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_F16) return field_launch_fwd<float, NSR_F16>(a, nblocks, so, s);
-    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_BF16) return field_launch_fwd<float, NSR_BF16>(a, nblocks, so, s);
-    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_F16) return field_launch_fwd<_Float16, NSR_F16>(a, nblocks, so, s);
-    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_BF16) return field_launch_fwd<_Float16, NSR_BF16>(a, nblocks, so, s);
-    return NSR_ERR_UNSUPPORTED;
+    return field_dispatch(desc->table_dtype, desc->compute_dtype, [&](auto tt, auto cd) {
+        if (dirs) return field_launch_fwd<decltype(tt), cd(), true>(a, nblocks, false, s, dirs);
+        return field_launch_fwd<decltype(tt), cd()>(a, nblocks, so, s);
+    });
+}
+
+extern "C" {
+
+int nsr_field_forward(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *xyzs, uint32_t M,
+                      const int32_t *m_dev, float *sigmas, float *rgbs, void *feats, const uint32_t *perm, nsr_stream_t stream) {
+    return field_forward_any(desc, tables, mlp_params, xyzs, M, m_dev, sigmas, rgbs, feats, perm, nullptr, stream);
 }
 
 uint32_t nsr_field_mlp_param_count(int with_dirs) { return with_dirs ? P_TOTAL_DIRS : P_TOTAL; }
@@ -365,7 +368,7 @@ int nsr_field_forward_uses_lattice(const nsr_field_desc *desc, int with_perm, in
     if (desc == nullptr) return 0;
     FieldArgs a;
     uint32_t nblocks;
-    if (field_fill_args(desc, a, 16, nblocks) != NSR_OK) return 0;
+    if (field_fill_args(desc, nullptr, nullptr, a, 16, nblocks) != NSR_OK) return 0;
     if (!with_perm || desc->table_dtype != NSR_F16) return 0;
     FieldLatArgs la;
     return (with_dirs ? field_lat_plan<true>(a.lv, la) : field_lat_plan<false>(a.lv, la)) != 0;
@@ -383,26 +386,9 @@ int nsr_field_forward_dirs(const nsr_field_desc *desc, const void *tables, const
                            const int32_t *m_dev, float *sigmas, float *rgbs, void *feats, const uint32_t *perm, const float *dirs,
                            nsr_stream_t stream) {
     // the sigma-only branch never reads directions (nor the SH columns): it is nsr_field_forward's
-    if (rgbs == nullptr) return nsr_field_forward(desc, tables, mlp_params, xyzs, M, m_dev, sigmas, rgbs, feats, perm, stream);
-    if (M == 0) return NSR_OK;
-    NSR_CHECK_PTR(desc); NSR_CHECK_PTR(tables); NSR_CHECK_PTR(mlp_params); NSR_CHECK_PTR(xyzs); NSR_CHECK_PTR(sigmas);
-    NSR_CHECK_PTR(dirs);
-    FieldArgs a;
-    uint32_t nblocks;
-    const int st = field_fill_args(desc, a, M, nblocks);
-    if (st != NSR_OK) return st;
-    if ((uintptr_t)tables & 15u) return NSR_ERR_INVALID_ARG;
-    if (a.C_ch == 8 && ((uintptr_t)rgbs & 15u)) return NSR_ERR_INVALID_ARG;
-    a.tables = tables; a.params = mlp_params; a.xyzs = xyzs; a.m_dev = m_dev; a.sigmas = sigmas; a.rgbs = rgbs;
-    a.feats = feats;
-    a.perm = perm;
-    if (feats && ((uintptr_t)feats & 15u)) return NSR_ERR_INVALID_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_F16) return field_launch_fwd<float, NSR_F16, true>(a, nblocks, false, s, dirs);
-    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_BF16) return field_launch_fwd<float, NSR_BF16, true>(a, nblocks, false, s, dirs);
-    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_F16) return field_launch_fwd<_Float16, NSR_F16, true>(a, nblocks, false, s, dirs);
-    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_BF16) return field_launch_fwd<_Float16, NSR_BF16, true>(a, nblocks, false, s, dirs);
-    return NSR_ERR_UNSUPPORTED;
+    if (rgbs == nullptr) dirs = nullptr;
+    else if (M != 0) NSR_CHECK_PTR(dirs);
+    return field_forward_any(desc, tables, mlp_params, xyzs, M, m_dev, sigmas, rgbs, feats, perm, dirs, stream);
 }
 
 }   // extern "C"

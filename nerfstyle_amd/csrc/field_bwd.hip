@@ -635,16 +635,15 @@ static int field_backward_any(const nsr_field_desc *desc, const void *tables, co
     if ((train_density_table || train_color_table) && grad_tables == nullptr) return NSR_ERR_INVALID_ARG;
     FieldBwdArgs b;
     uint32_t nblocks;
-    const int st = field_fill_args(desc, b.f, M, nblocks);
+    const int st = field_fill_args(desc, tables, mlp_params, b.f, M, nblocks);
     if (st != NSR_OK) return st;
-    if ((uintptr_t)tables & 15u) return NSR_ERR_INVALID_ARG;
     // 4-wave workgroups, one wave per SIMD (each wave needs the 512-register budget): one
     // workgroup per CU is resident, each walks a contiguous range of tiles
     const uint32_t ntiles = (M + 15) / 16;
     nblocks = (ntiles + 3) / 4;
     if (nblocks > 256) nblocks = 256;
     b.f.tiles_per_block = (ntiles + nblocks - 1) / nblocks;
-    b.f.tables = tables; b.f.params = mlp_params; b.f.xyzs = xyzs; b.f.m_dev = m_dev; b.f.sigmas = nullptr; b.f.rgbs = nullptr;
+    b.f.xyzs = xyzs; b.f.m_dev = m_dev; b.f.sigmas = nullptr; b.f.rgbs = nullptr;
     const bool gout = perm != nullptr && (train_density_table || train_color_table);
     // `feats` given together with `perm` were written by nsr_field_forward in perm's order (tile-major): the gradients-out
     // kernel walks the same order; the fused tracker kernel walks the buffers and cannot use them (it re-gathers)

@@ -425,7 +425,10 @@ __device__ __forceinline__ uint32_t field_logical_block() {
 }
 
 
-static int field_fill_args(const nsr_field_desc *d, FieldArgs &a, uint32_t M, uint32_t &nblocks) {
+// host: everything of FieldArgs that the descriptor, the two parameter pointers and the sample count decide (the buffers are
+// the caller's); `tables` must be 16-byte aligned for the gathers
+static int field_fill_args(const nsr_field_desc *d, const void *tables, const float *mlp_params, FieldArgs &a, uint32_t M,
+                           uint32_t &nblocks) {
     if (d->L != 16) return NSR_ERR_UNSUPPORTED;             // 32 features = two K=32 halves per encoder
     if (d->num_classes > 13) return NSR_ERR_UNSUPPORTED;    // class rows 3..15 of one 16-row tile
     if (d->offsets == nullptr) return NSR_ERR_INVALID_ARG;
@@ -449,6 +452,21 @@ static int field_fill_args(const nsr_field_desc *d, FieldArgs &a, uint32_t M, ui
     if (nb == 0) nb = 1;
     nblocks = nb;
     a.tiles_per_block = (ntiles + nb - 1) / nb;
-    return NSR_OK;
+    a.tables = tables;
+    a.params = mlp_params;
+    return ((uintptr_t)tables & 15u) ? NSR_ERR_INVALID_ARG : NSR_OK;
+}
+
+// host: the (table type, compute type) instantiation of a field kernel.  `launch` is called with two tags: a value of the table
+// type and the compute type as an integral constant.
+template <typename F>
+static int field_dispatch(int table_dtype, int compute_dtype, F &&launch) {
+    using f16 = std::integral_constant<int, NSR_F16>;
+    using bf16 = std::integral_constant<int, NSR_BF16>;
+    if (table_dtype == NSR_F32 && compute_dtype == NSR_F16) return launch(float(), f16());
+    if (table_dtype == NSR_F32 && compute_dtype == NSR_BF16) return launch(float(), bf16());
+    if (table_dtype == NSR_F16 && compute_dtype == NSR_F16) return launch(_Float16(), f16());
+    if (table_dtype == NSR_F16 && compute_dtype == NSR_BF16) return launch(_Float16(), bf16());
+    return NSR_ERR_UNSUPPORTED;
 }
 

@@ -227,11 +227,10 @@ int nsr_field_density_gradient(const nsr_field_desc *desc, const void *tables, c
     NSR_CHECK_PTR(desc); NSR_CHECK_PTR(tables); NSR_CHECK_PTR(mlp_params); NSR_CHECK_PTR(xyzs); NSR_CHECK_PTR(grads);
     DensityGradArgs da;
     uint32_t nblocks;
-    const int st = field_fill_args(desc, da.f, M, nblocks);
+    const int st = field_fill_args(desc, tables, mlp_params, da.f, M, nblocks);
     if (st != NSR_OK) return st;
-    if ((uintptr_t)tables & 15u) return NSR_ERR_INVALID_ARG;
     FieldArgs &a = da.f;
-    a.tables = tables; a.params = mlp_params; a.xyzs = xyzs; a.m_dev = m_dev; a.sigmas = sigmas; a.rgbs = nullptr;
+    a.xyzs = xyzs; a.m_dev = m_dev; a.sigmas = sigmas; a.rgbs = nullptr;
     a.feats = nullptr; a.perm = nullptr;
     da.grads = grads;
     da.normalize = normalize;
@@ -239,11 +238,8 @@ int nsr_field_density_gradient(const nsr_field_desc *desc, const void *tables, c
     for (int l = 0; l < 16; l++) da.cell_scale[l] = (float)a.lv[l].resolution / res_top;
     for (int k = 0; k < 3; k++) da.out_scale[k] = res_top * (1.0f / (2.0f * desc->bbox_size[k]));
     hipStream_t s = (hipStream_t)stream;
-    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_F16) return dg_launch<float, NSR_F16>(da, nblocks, s);
-    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_BF16) return dg_launch<float, NSR_BF16>(da, nblocks, s);
-    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_F16) return dg_launch<_Float16, NSR_F16>(da, nblocks, s);
-    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_BF16) return dg_launch<_Float16, NSR_BF16>(da, nblocks, s);
-    return NSR_ERR_UNSUPPORTED;
+    return field_dispatch(desc->table_dtype, desc->compute_dtype,
+                          [&](auto tt, auto cd) { return dg_launch<decltype(tt), cd()>(da, nblocks, s); });
 }
 
 }   // extern "C"

@@ -219,13 +219,12 @@ static int render_stream(const nsr_field_desc *desc, const void *tables, const f
     if (max_steps == 0 || C == 0 || H == 0 || H > 1024 || !(bound > 0.0f)) return NSR_ERR_INVALID_ARG;
     RenderInferArgs a;
     uint32_t field_blocks;
-    const int st = field_fill_args(desc, a.f, N, field_blocks);      // num_classes > 13 -> NSR_ERR_UNSUPPORTED
+    const int st = field_fill_args(desc, tables, mlp_params, a.f, N, field_blocks);      // num_classes > 13 -> NSR_ERR_UNSUPPORTED
     if (st != NSR_OK) return st;
-    if ((uintptr_t)tables & 15u) return NSR_ERR_INVALID_ARG;
     // the epilogue outputs come together: rgb_map and depth_norm, and classes exactly when there are class channels
     if ((rgb_map != nullptr) != (depth_norm != nullptr)) return NSR_ERR_INVALID_ARG;
     if ((classes != nullptr) != (rgb_map != nullptr && desc->num_classes != 0)) return NSR_ERR_INVALID_ARG;
-    a.f.tables = tables; a.f.params = mlp_params; a.f.xyzs = nullptr; a.f.m_dev = nullptr; a.f.sigmas = nullptr;
+    a.f.xyzs = nullptr; a.f.m_dev = nullptr; a.f.sigmas = nullptr;
     a.f.rgbs = nullptr; a.f.feats = nullptr; a.f.perm = nullptr;
     a.rays_o = rays_o; a.rays_d = rays_d; a.order = order; a.nears = nears; a.fars = fars; a.grid = grid;
     a.N = N; a.bound = bound; a.dt_gamma = dt_gamma; a.max_steps = max_steps; a.C = C; a.H = H; a.T_thresh = T_thresh;
@@ -242,11 +241,8 @@ static int render_stream(const nsr_field_desc *desc, const void *tables, const f
     a.rays_per_wave = rpw;
     const uint32_t nblocks = nsr_div_up(N, (uint64_t)rpw * 4u);
     hipStream_t s = (hipStream_t)stream;
-    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_F16) return render_infer_launch<float, NSR_F16>(a, mode, nblocks, s);
-    if (desc->table_dtype == NSR_F32 && desc->compute_dtype == NSR_BF16) return render_infer_launch<float, NSR_BF16>(a, mode, nblocks, s);
-    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_F16) return render_infer_launch<_Float16, NSR_F16>(a, mode, nblocks, s);
-    if (desc->table_dtype == NSR_F16 && desc->compute_dtype == NSR_BF16) return render_infer_launch<_Float16, NSR_BF16>(a, mode, nblocks, s);
-    return NSR_ERR_UNSUPPORTED;
+    return field_dispatch(desc->table_dtype, desc->compute_dtype,
+                          [&](auto tt, auto cd) { return render_infer_launch<decltype(tt), cd()>(a, mode, nblocks, s); });
 }
 
 extern "C" {

@@ -17,6 +17,23 @@ import torch
 from .renderer import Renderer
 
 
+def _ready_for_capture(model):
+    """The gradient arena exists and the gather tables are current BEFORE capture: a captured replay reads the f16 copy that the
+    optimiser keeps in sync (FusedAdam refreshes it in its own pass) and must not bake a cast of stale data into the graph."""
+    model._ensure_grad()
+    model.sync_gather_tables()
+
+
+def _warm_up(device, body, passes):
+    """`passes` eager runs of `body` on a side stream (allocator pools, lazy initialisation), as torch.cuda.graphs asks"""
+    s = torch.cuda.Stream(device=device)
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(passes):
+            body()
+    torch.cuda.current_stream().wait_stream(s)
+
+
 class GraphedRenderStep:
     """graph = GraphedRenderStep(renderer, n_rays, loss_fn); loss = graph(pose, pix)
     (prefetch=True: loss = graph(pose, pix, pose_next, pix_next) -- the next call's pose and pixels, the SAME tensor objects)
@@ -64,12 +81,8 @@ class GraphedRenderStep:
 
     def _restage(self, pose, pix):
         """march (pose, pix) now, on the current stream, into the static sample buffers (allocated by the first call)"""
-        keep = self.r.update_occ
-        self.r.update_occ = False          # no occupancy update and no step bookkeeping in here: __call__ keeps the schedule
-        try:
+        with self.r.occupancy_frozen():    # __call__ keeps the schedule
             self._stage = self.r.begin_train(pose, pix, dense=self.dense, into=self._stage)
-        finally:
-            self.r.update_occ = keep
 
     def _body_prefetch(self, with_optimizer=True):
         out = self.r.finish_train(self._stage)
@@ -88,12 +101,8 @@ class GraphedRenderStep:
         return loss.detach()
 
     def _body(self, with_optimizer=True):
-        keep = self.r.update_occ
-        self.r.update_occ = False          # inside the graph: fixed launch sequence, a private device-side counter
-        try:
+        with self.r.occupancy_frozen():    # inside the graph: fixed launch sequence, a private device-side counter
             out = self.r.render(self.pose, None, training=True, pix_subset=self.pix, dense=self.dense)
-        finally:
-            self.r.update_occ = keep
         loss = self.loss_fn(out, self.pix)
         if loss.requires_grad:             # (recon_loss(..., backward=True) has back-propagated already)
             loss.backward()
@@ -108,21 +117,12 @@ class GraphedRenderStep:
             self.pose_next.copy_(pose_next if pose_next is not None else pose)
             self.pix_next.copy_(pix_next if pix_next is not None else pix)
         model = self.r.model
-        model._ensure_grad()
-        # the f16 gather copy must be current BEFORE capture: a captured replay reads the copy the optimiser keeps in sync
-        # (FusedAdam refreshes it in its own pass) and must not bake a cast of stale data into the graph
-        if model.table_dtype == torch.float16:
-            model._gather_tables()
-        # warm-up on a side stream (allocator pools, lazy initialisation), as torch.cuda.graphs asks
-        s = torch.cuda.Stream(device=self.r.device)
-        s.wait_stream(torch.cuda.current_stream())
+        _ready_for_capture(model)
         if self.optimizer is not None:
             # the scaler state lives on the device before capture (no allocation / upload inside it), and the EMA count moves there
             self.optimizer.attach_scaler(self.scaler, self.r.device)
-        with torch.cuda.stream(s):
-            for _ in range(self._warmup):
-                self._body(with_optimizer=False)   # warm-up renders only: no parameter update, no step counted
-        torch.cuda.current_stream().wait_stream(s)
+        # warm-up renders only: no parameter update, no step counted
+        _warm_up(self.r.device, lambda: self._body(with_optimizer=False), self._warmup)
         model.arena.grad.zero_()           # the warm-up passes accumulated gradients
         if self.prefetch:
             self._side = torch.cuda.Stream(device=self.r.device)
@@ -142,15 +142,11 @@ class GraphedRenderStep:
         r = self.r
         updated = False
         if self.occ_updates:
-            if r.local_step % r.cfg.update_iter == 0:
+            if r.occupancy_update_due():
                 r.update_state()
                 updated = True
             r.local_step += 1
-        m = r.model
-        if m.table_dtype == torch.float16 and m._half_version != m.arena._version:
-            # parameters changed by something other than FusedAdam (load_state_dict, an EMA swap, a stock optimiser):
-            # refresh the f16 gather copy the captured kernels read
-            m._gather_tables()
+        r.model.sync_gather_tables()       # parameters changed by something other than FusedAdam: the captured kernels read the copy
         if self.prefetch:
             # the staged samples (and the pixel ids the previous replay left in self.pix) are this step's only if the previous
             # replay marched exactly these pixels of this pose through the bitfield that is current now (never across an
@@ -168,7 +164,7 @@ class GraphedRenderStep:
             self.pose.copy_(pose)
             self.pix.copy_(pix)
         self.graph.replay()
-        self.r._last_counter = self._counter
+        r._set_last(self._counter)
         return self.loss
 
     @property
@@ -205,13 +201,9 @@ class GraphedPatchBackward:
     def _body(self):
         from .rays import generate_rays
         r = self.r
-        keep = r.update_occ
-        r.update_occ = False               # a private device-side counter, no step bookkeeping inside the graph
-        try:
+        with r.occupancy_frozen():         # a private device-side counter, no step bookkeeping inside the graph
             rays, _ = generate_rays(self.pose, r.intr, None, camera_flip=r.cfg.flip_camera, pix_subset=self.pix, device=r.device)
             mt = r.march_train(rays)
-        finally:
-            r.update_occ = keep
         perm = r.model.sample_order(mt['xyzs'], mt['counter']) if r._use_spatial_order(mt['N'], self.dense) else None
         image, _, _ = r.shade_train(mt, perm)
         image.backward(self.grad)
@@ -220,16 +212,9 @@ class GraphedPatchBackward:
     def capture(self):
         """The static buffers must hold a real patch: the warm-up passes run on them, and their gradient is removed again."""
         model = self.r.model
-        model._ensure_grad()
-        if model.table_dtype == torch.float16:
-            model._gather_tables()
+        _ready_for_capture(model)
         saved = model.arena.grad.clone()
-        s = torch.cuda.Stream(device=self.r.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(self._warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(s)
+        _warm_up(self.r.device, self._body, self._warmup)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.counter = self._body()
@@ -242,8 +227,6 @@ class GraphedPatchBackward:
         self.grad.copy_(grad)
         if self.graph is None:
             self.capture()
-        m = self.r.model
-        if m.table_dtype == torch.float16 and m._half_version != m.arena._version:
-            m._gather_tables()
+        self.r.model.sync_gather_tables()
         self.graph.replay()
-        self.r._last_counter = self.counter
+        self.r._set_last(self.counter)

@@ -10,6 +10,7 @@ What is different underneath (MI355X-first):
   * the model is two fused launches (forward / backward), not 2 encoders + 4 MLPs + exp + cat;
   * the white-background / depth epilogue stays in torch (a few [N]-sized ops).
 """
+from contextlib import contextmanager
 from math import ceil, log2
 from typing import Dict, Optional
 
@@ -53,7 +54,10 @@ class Renderer(torch.nn.Module):
         # The no-grad training render through the same kernel with the TRAINING composite (render_train_fused): what pass 1
         # of the deferred stylisation iteration and validation renders ask for.  Opt-in; unmeasured on the GPU so far.
         self.fused_nograd_train = False
+        self.reference_inference_loop = False      # render_test through render_test_loop (the reference's iteration structure)
+        self.last_test_overflow = False            # the last bounded-capacity render_test overflowed and fell back to the loop
         self._infer_stats = None
+        self._last_counter = self._last_capacity = None    # _set_last: what last_call_overflowed() answers from
         self._tile_orders = {}
         self.aabb = torch.tensor([-bound, -bound, -bound, bound, bound, bound], dtype=torch.float32)
         self.cascade = 1 + ceil(log2(bound))
@@ -66,6 +70,7 @@ class Renderer(torch.nn.Module):
         self._mean_density_dev, self._mean_density_host = None, 0.0
         self._mean_count_host, self._mean_count_stale = 0, False
         self._occ_state = None
+        self._occ_key = self._occ_ws = self._occ_xyzs = self._occ_idx = None
         self.occ_seed = 0
         self.device = torch.device('cpu')
 
@@ -147,7 +152,7 @@ class Renderer(torch.nn.Module):
     def _occ_buffers(self, P):
         """Scratch of one update; allocated once per shape (no allocation in the steady state)."""
         key = (P, str(self.device))
-        if getattr(self, '_occ_key', None) != key:
+        if self._occ_key != key:
             from . import _lib as L
             dev = self.device
             nbytes = int(L.lib().nsr_occ_workspace_bytes(self.cascade, self.cfg.grid_size))
@@ -221,45 +226,73 @@ class Renderer(torch.nn.Module):
             perm = self.model.sample_order(mt['xyzs'], mt['counter'])
         return self.shade_train(mt, perm)
 
+    @contextmanager
+    def occupancy_frozen(self):
+        """March and render without an occupancy update and without step bookkeeping (local_step and the count ring stay as
+        they are, every march counts into a counter of its own): inside a captured graph, for a render beside the training
+        schedule.  update_occ is restored on exit, also when the body raises."""
+        keep = self.update_occ
+        self.update_occ = False
+        try:
+            yield self
+        finally:
+            self.update_occ = keep
+
+    def _call_counter(self, static: Optional[torch.Tensor] = None):
+        """-> (counter, slot): the zeroed device-side (samples, rays) counter of this call, and the step bookkeeping in one place.
+        With update_occ the call is a training step: ring slot local_step % STEP_CTR_SIZE (what mean_count averages) IS the
+        counter and local_step advances.  Without (occupancy_frozen()): a fresh counter; the ring and local_step stay.
+        static: the counter of an `into=` march, whose address a captured graph holds.  The march counts into IT and the caller
+        copies it into the step's slot afterwards, the one difference: `slot` is that slot, None in every other case."""
+        slot = None
+        if self.update_occ:
+            slot = self.step_counter[self.local_step % STEP_CTR_SIZE]
+            self.local_step += 1
+        if static is None and slot is None:
+            return torch.zeros(2, dtype=torch.int32, device=self.device), None
+        counter = slot if static is None else static
+        counter.zero_()
+        return counter, (None if static is None else slot)
+
+    def _set_last(self, counter, capacity=None):
+        """(device-side counter, sample capacity) of the last training render; a graph replay hands in its captured counter alone"""
+        self._last_counter = counter
+        self._last_capacity = self._last_capacity if capacity is None else capacity
+
+    def _march(self, rays: RayBatch, into: Optional[dict] = None, step: bool = True) -> dict:
+        """march_train; step=False (render_test): a counter of the call's own, no bookkeeping, nothing for last_call_overflowed()"""
+        cfg = self.cfg
+        if into is None:
+            nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, cfg.min_near)
+            N = rays.origins.shape[0]
+            M = self.sample_capacity(N)
+            want_dirs, out = self.model.use_dir, None
+        else:
+            N, M = into['N'], into['M']
+            assert rays.origins.shape[0] == N
+            nears, fars = raymarching.near_far_from_aabb_into(rays.origins, rays.dirs, self.aabb, cfg.min_near,
+                                                              into['nears'], into['fars'])
+            want_dirs = into.get('dirs') is not None          # a view-dependent model: the samples' directions, a static buffer too
+            out = (into['xyzs'], into['deltas'], into['rays_info']) + ((into['dirs'],) if want_dirs else ())
+        if step:
+            counter, slot = self._call_counter(None if into is None else into['counter'])
+            self._set_last(counter, M)
+        else:
+            counter, slot = torch.zeros(2, dtype=torch.int32, device=self.device), None
+        xyzs, dirs, deltas, rays_info = raymarching.march_rays_train_nosync(
+            rays.origins, rays.dirs, self.bound, self.march_bitfield, self.cascade, cfg.grid_size, nears, fars,
+            M, counter, 0., cfg.max_steps, want_dirs=want_dirs, out=out)
+        if slot is not None:
+            slot.copy_(counter)          # the static counter of an `into=` march, published to the count ring (_call_counter)
+        if into is not None:
+            return into
+        return {'N': N, 'M': M, 'nears': nears, 'fars': fars, 'counter': counter, 'xyzs': xyzs, 'deltas': deltas,
+                'rays_info': rays_info, 'dirs': dirs}
+
     def march_train(self, rays: RayBatch, into: Optional[dict] = None) -> dict:
         """near/far + occupancy-grid march + compaction: capacity-sized sample buffers, device-side counts.
         into: the dict a previous call returned -- its tensors are written in place (static buffers of a captured step)."""
-        if into is not None:
-            nears, fars = raymarching.near_far_from_aabb_into(rays.origins, rays.dirs, self.aabb, self.cfg.min_near,
-                                                              into['nears'], into['fars'])
-            counter = into['counter']
-            counter.zero_()
-            self._last_counter = counter
-            N, M = into['N'], into['M']
-            assert rays.origins.shape[0] == N
-            self._last_capacity = M
-            want_dirs = into.get('dirs') is not None          # a view-dependent model: the samples' directions, a static buffer too
-            raymarching.march_rays_train_nosync(
-                rays.origins, rays.dirs, self.bound, self.march_bitfield, self.cascade, self.cfg.grid_size, nears, fars,
-                M, counter, 0., self.cfg.max_steps, want_dirs=want_dirs,
-                out=(into['xyzs'], into['deltas'], into['rays_info']) + ((into['dirs'],) if want_dirs else ()))
-            if self.update_occ:
-                # the step bookkeeping of the allocating path: the count ring behind mean_count, the occupancy schedule's step
-                self.step_counter[self.local_step % STEP_CTR_SIZE].copy_(counter)
-                self.local_step += 1
-            return into
-        nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
-        if self.update_occ:
-            counter = self.step_counter[self.local_step % STEP_CTR_SIZE]
-            counter.zero_()
-            self.local_step += 1
-        else:
-            counter = torch.zeros(2, dtype=torch.int32, device=self.device)
-
-        self._last_counter = counter     # device-side (samples, rays) of this call; never read here
-        N = rays.origins.shape[0]
-        M = self.sample_capacity(N)
-        self._last_capacity = M
-        xyzs, dirs, deltas, rays_info = raymarching.march_rays_train_nosync(
-            rays.origins, rays.dirs, self.bound, self.march_bitfield, self.cascade, self.cfg.grid_size, nears, fars,
-            M, counter, 0., self.cfg.max_steps, want_dirs=self.model.use_dir)
-        return {'N': N, 'M': M, 'nears': nears, 'fars': fars, 'counter': counter, 'xyzs': xyzs, 'deltas': deltas,
-                'rays_info': rays_info, 'dirs': dirs}
+        return self._march(rays, into)
 
     def shade_train(self, mt: dict, perm=None):
         """fused field on the marched samples + train composite with the epilogue of renderer.py:225-233 folded in
@@ -278,30 +311,19 @@ class Renderer(torch.nn.Module):
         normal_map = sum_i w_i n_i is NOT renormalised: its length is at most weights_sum, and shorter where the normals
         along a ray disagree; rays that miss the box get zeros.  depth is render_train's.  No occupancy bookkeeping: no
         update_state, and local_step and the step-counter ring stay as they are."""
-        from . import _lib as L
-        keep = (self.update_occ, getattr(self, '_last_counter', None), getattr(self, '_last_capacity', None))
-        self.update_occ = False                      # march_train then counts into a counter of its own
-        try:
+        keep = (self._last_counter, self._last_capacity)
+        with self.occupancy_frozen():                # march_train then counts into a counter of its own
             mt = self.march_train(rays)
-        finally:
-            self.update_occ, self._last_counter, self._last_capacity = keep
+        self._set_last(*keep)
         sigmas, normals = self.model.density_gradient(mt['xyzs'], m_dev=mt['counter'], density_scale=self.cfg.density_scale,
                                                       normalize=True)
-        N, M = mt['N'], mt['M']
-        dev = sigmas.device
-        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
-        depth_raw = torch.empty(N, dtype=torch.float32, device=dev)
-        normal_map = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        with_bg = torch.empty(N, 3, dtype=torch.float32, device=dev)      # the composite's white-background image: unused
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        L.check(L.lib().nsr_render_train_forward(
-            L.p(sigmas), L.p(normals), L.p(mt['deltas']), L.p(mt['rays_info']), L.p(mt['nears']), L.p(mt['fars']), M, N, 3,
-            float(self.cfg.t_thresh), L.p(weights_sum), L.p(depth_raw), L.p(normal_map), L.p(with_bg), L.p(depth), None,
-            L.stream()), 'render_train_forward')
+        # the normals as a 3-channel colour; the composite's white-background image is unused
+        weights_sum, _, normal_map, _, depth, _ = _render_train_forward(sigmas, normals, mt['deltas'], mt['rays_info'], mt['nears'],
+                                                                        mt['fars'], self.cfg.t_thresh)
         return {'normal_map': normal_map, 'weights_sum': weights_sum, 'depth': depth}
 
     def _use_spatial_order(self, n_rays: int, dense: bool) -> bool:
-        if getattr(self.model, '_spatial_scatter_unsupported', False):
+        if self.model._spatial_scatter_unsupported:
             return False                 # learnt from a backward that fell back (style_nerf._field.backward)
         if self.sort_samples != 'auto':
             return bool(self.sort_samples)
@@ -320,18 +342,13 @@ class Renderer(torch.nn.Module):
         inference kernel's arithmetic (nsr_composite_rays_infer) instead of up to max_steps host
         iterations; `self.reference_inference_loop = True` selects the reference's loop structure
         (render_test_loop), which the tests hold equal to this path."""
-        if getattr(self, 'reference_inference_loop', False):
+        if self.reference_inference_loop:
             return self.render_test_loop(rays, **kwargs)
         if self.fused_inference:
             return self.render_test_fused(rays, **kwargs)
         from . import _lib as L
-        nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
-        N = rays.origins.shape[0]
-        M = self.sample_capacity(N)
-        counter = torch.zeros(2, dtype=torch.int32, device=self.device)
-        xyzs, dirs, deltas, rays_info = raymarching.march_rays_train_nosync(
-            rays.origins, rays.dirs, self.bound, self.march_bitfield, self.cascade, self.cfg.grid_size, nears, fars,
-            M, counter, 0., self.cfg.max_steps, want_dirs=self.model.use_dir)
+        mt = self._march(rays, step=False)
+        N, M, counter, nears = mt['N'], mt['M'], mt['counter'], mt['nears']
         if self.samples_per_ray_cap is not None and self.samples_per_ray_cap < self.cfg.max_steps:
             # a bounded buffer can overflow, and the march then DROPS the rays that do not fit (raymarching.cu:517);
             # the reference's inference loop never drops a ray, so fall back to its iteration structure.  One host read
@@ -339,18 +356,53 @@ class Renderer(torch.nn.Module):
             self.last_test_overflow = int(counter[0].item()) >= M
             if self.last_test_overflow:
                 return self.render_test_loop(rays, **kwargs)
-        sigmas, rgbs = self.model.field(xyzs, sigma_only=False, m_dev=counter, density_scale=self.cfg.density_scale, dirs=dirs)
+        sigmas, rgbs = self.model.field(mt['xyzs'], sigma_only=False, m_dev=counter, density_scale=self.cfg.density_scale,
+                                        dirs=mt['dirs'])
         C = self.raymarch_channels
         weights_sum = torch.empty(N, dtype=torch.float32, device=self.device)
         depth = torch.empty(N, dtype=torch.float32, device=self.device)
         image = torch.empty(N, C, dtype=torch.float32, device=self.device)
-        L.check(L.lib().nsr_composite_rays_infer(L.p(sigmas), L.p(rgbs), L.p(deltas), L.p(rays_info), L.p(nears), M, N, C,
-                                                 float(self.cfg.t_thresh), L.p(weights_sum), L.p(depth), L.p(image),
+        L.check(L.lib().nsr_composite_rays_infer(L.p(sigmas), L.p(rgbs), L.p(mt['deltas']), L.p(mt['rays_info']), L.p(nears), M, N,
+                                                 C, float(self.cfg.t_thresh), L.p(weights_sum), L.p(depth), L.p(image),
                                                  L.stream()), 'composite_rays_infer')
+        return self._infer_epilogue(image, weights_sum, depth, nears, mt['fars'])
+
+    @staticmethod
+    def _infer_epilogue(image, weights_sum, depth, nears, fars):
+        """renderer.py:287-293 for the three inference paths: class slice, white background, depth normalisation"""
         classes = image[:, 3:]
         image = image[:, :3] + (1 - weights_sum).unsqueeze(-1)
         depth = torch.clamp(depth - nears, min=0) / (fars - nears)
         return image, depth, classes
+
+    def _render_stream(self, rays: RayBatch, dense_shape, train: bool):
+        """What render_test_fused and render_train_fused share: near/far, tile order, outputs and the one launch.  train: the training
+        composite, its epilogue outputs, the counts go to this step's counter; else the launch is nsr_render_rays_infer's.
+        -> ((image, weights_sum, depth, nears, fars) as composited, (rgb_map, depth, classes) of the epilogue | Nones, stats)"""
+        import ctypes
+        from . import _lib as L
+        nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
+        N, dev, C = rays.origins.shape[0], rays.origins.device, self.raymarch_channels
+        assert C == self.model.out_channels, 'the fused kernel composites the 3 + num_classes channels of the model'
+        order = self._tile_order(dense_shape, N, dev)
+
+        def empty(*shape):
+            return torch.empty(*shape, dtype=torch.float32, device=dev)
+        stats = self._call_counter()[0] if train else None
+        weights_sum, depth, image = empty(N), empty(N), empty(N, C)
+        if train:
+            epilogue = (empty(N, 3), empty(N), empty(N, C - 3))
+        else:
+            epilogue, stats = (None, None, None), torch.zeros(2, dtype=torch.int32, device=dev)
+        desc = self.model._desc(self.cfg.density_scale)
+        L.check(L.lib().nsr_render_rays_stream(
+            ctypes.byref(desc), L.p(self.model._gather_tables()), L.p(self.model._mlp_flat()), L.p(rays.origins), L.p(rays.dirs),
+            L.p(order), N, L.p(nears), L.p(fars), L.p(self.march_bitfield), float(self.bound), 0., self.cfg.max_steps, self.cascade,
+            self.cfg.grid_size, float(self.cfg.t_thresh), L.NSR_STREAM_TRAIN if train else L.NSR_STREAM_INFER, L.p(weights_sum),
+            L.p(depth), L.p(image), L.p(epilogue[0]), L.p(epilogue[1]), L.p(epilogue[2]) if C > 3 else None, None, L.p(stats),
+            L.stream()), 'render_rays_stream')
+        self._infer_stats = stats
+        return (image, weights_sum, depth, nears, fars), epilogue, stats
 
     @torch.no_grad()
     def render_test_fused(self, rays: RayBatch, dense_shape=None, **kwargs):
@@ -359,33 +411,11 @@ class Renderer(torch.nn.Module):
         but nothing here is sized by samples -- no capacity, so no dropped ray and no overflow fallback, no host read -- and
         a ray that stopped early costs nothing further.  dense_shape = (w, h): the rays are the row-major pixels of a
         w x h window, walked in 8 x 8 tiles so that the 16 rays a wave holds are neighbours; anything else in batch order."""
-        import ctypes
-        from . import _lib as L
         if self.model.use_dir:
             raise NotImplementedError('fused_inference: the streaming kernel has no direction input (view_dependent model)')
-        nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
         if self.cfg.use_ndc:
             raise NotImplementedError('render_test_fused: NDC scenes march through render_test / render_test_loop')
-        N = rays.origins.shape[0]
-        dev = rays.origins.device
-        C = self.raymarch_channels
-        assert C == self.model.out_channels, 'the fused kernel composites the 3 + num_classes channels of the model'
-        order = self._tile_order(dense_shape, N, dev)
-        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, C, dtype=torch.float32, device=dev)
-        stats = torch.zeros(2, dtype=torch.int32, device=dev)
-        desc = self.model._desc(self.cfg.density_scale)
-        L.check(L.lib().nsr_render_rays_infer(
-            ctypes.byref(desc), L.p(self.model._gather_tables()), L.p(self.model._mlp_flat()), L.p(rays.origins), L.p(rays.dirs),
-            L.p(order), N, L.p(nears), L.p(fars), L.p(self.march_bitfield), float(self.bound), 0., self.cfg.max_steps, 0,
-            self.cascade, self.cfg.grid_size, float(self.cfg.t_thresh), L.p(weights_sum), L.p(depth), L.p(image), L.p(stats),
-            L.stream()), 'render_rays_infer')
-        self._infer_stats = stats
-        classes = image[:, 3:]
-        image = image[:, :3] + (1 - weights_sum).unsqueeze(-1)
-        depth = torch.clamp(depth - nears, min=0) / (fars - nears)
-        return image, depth, classes
+        return self._infer_epilogue(*self._render_stream(rays, dense_shape, train=False)[0])
 
     def _tile_order(self, dense_shape, N, dev):
         """The cached 8 x 8-tile work list of a w x h window (None when the rays are not such a window)."""
@@ -407,42 +437,15 @@ class Renderer(torch.nn.Module):
         The occupancy bookkeeping is render_train's (update_state when due, local_step, the step-counter ring), except that
         the ring slot receives (samples SHADED, N): what lies behind the point where a ray stopped is not counted, where the
         march of render_train counts every emitted sample.  dense_shape: as for render_test_fused."""
-        import ctypes
-        from . import _lib as L
         if self.model.use_dir:
             raise NotImplementedError('fused_nograd_train: the streaming kernel has no direction input (view_dependent model)')
         if self.cfg.use_ndc:
             raise NotImplementedError('render_train_fused: NDC scenes render through the buffered render_train')
         if self.occupancy_update_due():
             self.update_state()
-        nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
-        N = rays.origins.shape[0]
-        dev = rays.origins.device
-        C = self.raymarch_channels
-        assert C == self.model.out_channels, 'the fused kernel composites the 3 + num_classes channels of the model'
-        if self.update_occ:
-            stats = self.step_counter[self.local_step % STEP_CTR_SIZE]
-            stats.zero_()
-            self.local_step += 1
-        else:
-            stats = torch.zeros(2, dtype=torch.int32, device=dev)
-        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
-        depth_raw = torch.empty(N, dtype=torch.float32, device=dev)
-        image_raw = torch.empty(N, C, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        classes = torch.empty(N, C - 3, dtype=torch.float32, device=dev)
-        desc = self.model._desc(self.cfg.density_scale)
-        L.check(L.lib().nsr_render_rays_stream(
-            ctypes.byref(desc), L.p(self.model._gather_tables()), L.p(self.model._mlp_flat()), L.p(rays.origins), L.p(rays.dirs),
-            L.p(self._tile_order(dense_shape, N, dev)), N, L.p(nears), L.p(fars), L.p(self.march_bitfield), float(self.bound), 0.,
-            self.cfg.max_steps, self.cascade, self.cfg.grid_size, float(self.cfg.t_thresh), L.NSR_STREAM_TRAIN, L.p(weights_sum),
-            L.p(depth_raw), L.p(image_raw), L.p(image), L.p(depth), L.p(classes) if C > 3 else None, None, L.p(stats),
-            L.stream()), 'render_rays_stream')
-        self._infer_stats = stats
-        # nothing is ever dropped: last_call_overflowed() answers False
-        self._last_counter, self._last_capacity = stats, N * self.cfg.max_steps + 1
-        return image, depth, classes
+        _, out, stats = self._render_stream(rays, dense_shape, train=True)
+        self._set_last(stats, rays.origins.shape[0] * self.cfg.max_steps + 1)   # nothing is ever dropped: last_call_overflowed() answers False
+        return out
 
     def last_infer_stats(self) -> Optional[torch.Tensor]:
         """Device tensor int32 [2] of the last render_test_fused / render_train_fused call -- (samples shaded, rays finished)
@@ -480,11 +483,7 @@ class Renderer(torch.nn.Module):
             rays_alive, rays_alive_next = rays_alive_next, rays_alive
             n_alive = int(n_out.item())
             step += n_step
-        classes = image[:, 3:]
-        image = image[:, :3]
-        image = image + (1 - weights_sum).unsqueeze(-1)
-        depth = torch.clamp(depth - nears, min=0) / (fars - nears)
-        return image, depth, classes
+        return self._infer_epilogue(image, weights_sum, depth, nears, fars)
 
     # ---- a training render in two halves (data-parallel overlap, parallel.py) ---------------------------------------
     def occupancy_update_due(self) -> bool:
@@ -539,7 +538,7 @@ class Renderer(torch.nn.Module):
             torch.cuda.current_stream(self.device).wait_stream(ctx['stream'])
         out = {'target': None}
         out['rgb_map'], out['trans_map'], out['classes'] = self.shade_train(ctx['mt'], ctx['perm'])
-        self._last_counter, self._last_capacity = ctx['mt']['counter'], ctx['mt']['M']
+        self._set_last(ctx['mt']['counter'], ctx['mt']['M'])
         return out
 
     def render(self, pose, image=None, patch: Optional[Box2D] = None, num_rays: Optional[int] = None,
@@ -562,6 +561,24 @@ class Renderer(torch.nn.Module):
         return output
 
 
+def _render_train_forward(sigmas, rgbs, deltas, rays, nears, fars, T_thresh):
+    """nsr_render_train_forward and its six outputs -> (weights_sum [N], depth_raw [N], image [N,C], rgb_map [N,3], depth [N],
+    classes [N,C-3]): the training composite of C colour channels with the epilogue of renderer.py:229-233 folded in."""
+    from . import _lib as L
+    M, N, C = sigmas.shape[0], rays.shape[0], rgbs.shape[1]
+    dev = sigmas.device
+    weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
+    depth_raw = torch.empty(N, dtype=torch.float32, device=dev)
+    image = torch.empty(N, C, dtype=torch.float32, device=dev)
+    rgb_map = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    depth = torch.empty(N, dtype=torch.float32, device=dev)
+    classes = torch.empty(N, C - 3, dtype=torch.float32, device=dev)
+    L.check(L.lib().nsr_render_train_forward(
+        L.p(sigmas), L.p(rgbs), L.p(deltas), L.p(rays), L.p(nears), L.p(fars), M, N, C, float(T_thresh), L.p(weights_sum),
+        L.p(depth_raw), L.p(image), L.p(rgb_map), L.p(depth), L.p(classes) if C > 3 else None, L.stream()), 'render_train_forward')
+    return weights_sum, depth_raw, image, rgb_map, depth, classes
+
+
 class _render_train_fn(torch.autograd.Function):
     """composite_rays_train (raymarching.cu:806-997) + `image[:, :3] + (1 - weights_sum)`, the class slice and the depth
     normalisation (renderer.py:229-233) as ONE kernel each way, over capacity-sized sample buffers.  Outputs
@@ -571,21 +588,9 @@ class _render_train_fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sigmas, rgbs, deltas, rays, nears, fars, T_thresh):
         ctx.set_materialize_grads(False)     # outputs the loss does not use arrive as None, not as zero tensors (two fills a step)
-        from . import _lib as L
         from . import profiling
-        M, N, C = sigmas.shape[0], rays.shape[0], rgbs.shape[1]
-        dev = sigmas.device
-        weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
-        depth_raw = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, C, dtype=torch.float32, device=dev)
-        rgb_map = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        classes = torch.empty(N, C - 3, dtype=torch.float32, device=dev)
         with profiling.timed('composite_fwd'):
-            L.check(L.lib().nsr_render_train_forward(
-                L.p(sigmas), L.p(rgbs), L.p(deltas), L.p(rays), L.p(nears), L.p(fars), M, N, C, float(T_thresh), L.p(weights_sum),
-                L.p(depth_raw), L.p(image), L.p(rgb_map), L.p(depth), L.p(classes) if C > 3 else None, L.stream()),
-                'render_train_forward')
+            weights_sum, _, image, rgb_map, depth, classes = _render_train_forward(sigmas, rgbs, deltas, rays, nears, fars, T_thresh)
         ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, image)
         ctx.T_thresh = T_thresh
         ctx.mark_non_differentiable(depth)

@@ -38,7 +38,7 @@ SHARD_ALIGN = 16          # floats: 64 B, and a multiple of 4 keeps the element-
 def trained_lane_mask(model: StyleTCNerf, keywords=None) -> int:
     """0xF: everything is trained (reconstruction); 0x3 / 0xC: one hash table and no net (stylisation).  Other selections
     raise NotImplementedError."""
-    if getattr(model, 'use_dir', False):
+    if model.use_dir:
         raise NotImplementedError('ShardedFusedAdam does not handle a view_dependent=True model (the appended SH-column block '
                                   'of color2_net is not in its lane layout): use optim.FusedAdam with parallel.sync_gradients')
     mask, nets = select_regions(model, keywords)

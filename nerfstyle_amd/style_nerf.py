@@ -73,6 +73,13 @@ def get_grid_encoder(cfg: NetworkConfig, max_bound: float, enc_dtype=None, use_c
                        log2_hashmap_size=pe.hashmap_size, gridtype='hash', align_corners=True)
 
 
+def _field_call(entry, dirs, *args):
+    """nsr_<entry>(*args, stream) -> status; with the samples' directions nsr_<entry>_dirs(*args, dirs, stream) (view-dependent models)"""
+    if dirs is None:
+        return getattr(L.lib(), 'nsr_' + entry)(*args, L.stream())
+    return getattr(L.lib(), 'nsr_' + entry + '_dirs')(*args, L.p(dirs), L.stream())
+
+
 class _field(Function):
     """Fused field: xyzs -> (sigmas [M], rgbs [M, 3+nc] | None).  `arena` is an input only so that
     autograd routes gradients here; the backward accumulates in place into model.grad_arena (which
@@ -97,18 +104,12 @@ class _field(Function):
         # (decided by the caller: grad mode is always off inside Function.forward)
         if (not sigma_only) and want_feats:
             feats = torch.empty(((M + 15) // 16) * 512, dtype=torch.int32, device=dev)
+        if sigma_only or not model.use_dir:
+            dirs = None
         with profiling.timed('field_fwd_sigma' if sigma_only else 'field_fwd'):
-            if model.use_dir and not sigma_only:
-                L.check(L.lib().nsr_field_forward_dirs(ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()),
-                                                       L.p(xyzs), M, L.p(m_dev), L.p(sigmas), L.p(rgbs), L.p(feats),
-                                                       L.p(perm) if feats is not None else None, L.p(dirs), L.stream()),
-                        'field_forward_dirs')
-            else:
-                dirs = None
-                L.check(L.lib().nsr_field_forward(ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()),
-                                                  L.p(xyzs), M, L.p(m_dev), L.p(sigmas), L.p(rgbs), L.p(feats),
-                                                  L.p(perm) if feats is not None else None, L.stream()),
-                        'field_forward')
+            L.check(_field_call('field_forward', dirs, ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()), L.p(xyzs), M,
+                                L.p(m_dev), L.p(sigmas), L.p(rgbs), L.p(feats), L.p(perm) if feats is not None else None),
+                    'field_forward' if dirs is None else 'field_forward_dirs')
         ctx.model = model
         ctx.m_dev = m_dev
         ctx.density_scale = density_scale
@@ -145,18 +146,16 @@ class _field(Function):
             if torch.cuda.is_current_stream_capturing():
                 ws = torch.empty(need, dtype=torch.float32, device=dev)      # graph-owned: a captured pointer must never dangle
             else:
-                ws = getattr(model, '_bwd_ws', None)
+                ws = model._bwd_ws
                 if ws is None or ws.device != dev or ws.numel() < need:
                     model._bwd_ws = None
                     ws = model._bwd_ws = torch.empty(need, dtype=torch.float32, device=dev)
         with profiling.timed('field_bwd'):
             def call(perm, wsp):
-                args = (ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()), L.p(xyzs), M, L.p(ctx.m_dev),
-                        L.p(grad_sigmas), L.p(grad_rgbs), L.p(ga), (ga.data_ptr() + model.table_elems * 4) if model.train_mlps else None,
-                        int(model.train_density_table), int(model.train_color_table), L.p(feats), L.p(perm), L.p(wsp))
-                if dirs is not None:
-                    return L.lib().nsr_field_backward_dirs(*args, L.p(dirs), L.stream())
-                return L.lib().nsr_field_backward(*args, L.stream())
+                return _field_call(
+                    'field_backward', dirs, ctypes.byref(desc), L.p(tables), L.p(model._mlp_flat()), L.p(xyzs), M, L.p(ctx.m_dev),
+                    L.p(grad_sigmas), L.p(grad_rgbs), L.p(ga), (ga.data_ptr() + model.table_elems * 4) if model.train_mlps else None,
+                    int(model.train_density_table), int(model.train_color_table), L.p(feats), L.p(perm), L.p(wsp))
             st = call(perm, ws)
             if st == -2 and perm is not None:
                 feats = None             # saved in the permutation's order: useless to a kernel that walks the buffers
@@ -300,6 +299,9 @@ class StyleTCNerf(nn.Module):
         self.grad_arena = None
         self._half_tables = None
         self._half_version = -1
+        self._bbox_host = None                   # _bbox()
+        self._bwd_ws = None                      # the ordered backward's encoder-gradient buffer (_field.backward), only ever grown
+        self._spatial_scatter_unsupported = False    # set by a backward that had to fall back from the spatial table scatter
 
         self.x_density_embedder = _EncoderView(self, 0, template)
         self.x_color_embedder = _EncoderView(self, 1, template)
@@ -353,15 +355,27 @@ class StyleTCNerf(nn.Module):
     def mark_half_synced(self):
         self._half_version = self.arena._version
 
-    def _gather_tables(self):
+    def sync_gather_tables(self):
+        """Make the gather tables current if the arena changed: the f16 copy is cast again after anything but a fused optimiser
+        (which refreshes it in its own pass) wrote the parameters.  Nothing to do for fp32 tables, which are the arena."""
         if self.table_dtype == torch.float32:
-            return self.arena.detach()
+            return
         h = self.half_tables()
         if self._half_version != self.arena._version:
             L.check(L.lib().nsr_cast_f32_to_f16(L.p(self.arena.detach()), L.p(h), self.table_elems, L.stream()),
                     'cast_f32_to_f16')
             self._half_version = self.arena._version
-        return h
+
+    def _gather_tables(self):
+        self.sync_gather_tables()
+        return self.arena.detach() if self.table_dtype == torch.float32 else self.half_tables()
+
+    def _bbox(self):
+        """Host copy (min, size) of the constant bounding box, read back once: a per-call .cpu() would be a device
+        synchronisation in the middle of an otherwise sync-free step"""
+        if self._bbox_host is None:
+            self._bbox_host = (self.bounds_bbox.min_pt.detach().cpu().tolist(), self.bounds_bbox.size.detach().cpu().tolist())
+        return self._bbox_host
 
     def _desc(self, density_scale=1.0):
         d = L.FieldDesc()
@@ -369,11 +383,7 @@ class StyleTCNerf(nn.Module):
         d.num_classes = self.class_dim
         d.table_dtype = L.dt(self.table_dtype)
         d.compute_dtype = L.dt(self.compute_dtype)
-        # host copy of the (constant) bounding box, read back once: a per-call .cpu() would be a device
-        # synchronisation in the middle of an otherwise sync-free step
-        if getattr(self, '_bbox_host', None) is None:
-            self._bbox_host = (self.bounds_bbox.min_pt.detach().cpu().tolist(), self.bounds_bbox.size.detach().cpu().tolist())
-        mn, sz = self._bbox_host
+        mn, sz = self._bbox()
         for i in range(3):
             d.bbox_min[i] = mn[i]
             d.bbox_size[i] = sz[i]
@@ -463,9 +473,7 @@ class StyleTCNerf(nn.Module):
         ws_ptr = (ws.data_ptr() + 255) & ~255
         perm = torch.empty(M, dtype=torch.int32, device=dev) if out is None else out
         assert perm.dtype == torch.int32 and perm.numel() == M and perm.is_contiguous() and perm.device == dev
-        if getattr(self, '_bbox_host', None) is None:
-            self._desc()
-        mn, sz = self._bbox_host
+        mn, sz = self._bbox()
         c3 = ctypes.c_float * 3
         L.check(L.lib().nsr_sample_order(L.p(xyzs), M, L.p(m_dev), M if sort_prefix is None else int(min(sort_prefix, M)),
                                          c3(*mn), c3(*sz), L.p(perm), ws_ptr, L.stream()), 'sample_order')

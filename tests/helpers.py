@@ -3,6 +3,7 @@ import json
 import os
 
 import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,6 +28,44 @@ def small_scene(seed=0, n_boxes=48):
     grid = synthetic_density_grid(2.0, 128, n_boxes, seed)
     bits = np.packbits((grid.reshape(-1, 8) > 0.5)[:, ::-1], axis=1).reshape(-1)   # bit i of byte n = cell 8n+i
     return grid, bits
+
+
+def render_setup(dev, nc=5, table_dtype=torch.float32, compute_dtype=torch.float16, table_scale=0.5, cap=None, contrast=1.0,
+                 ref=None, view_dependent=False, state=None):
+    """The seeded checkpoint of oracle/torch_port.py in a Renderer over the seeded synthetic occupancy (bound 2, H = 128), fixed
+    (update_occ off) -> (renderer, ref, poses, intr, bits).
+    contrast: the seeded checkpoint is nearly grey (rgb 0.50 +- 0.009, sigma 1.0 +- 0.09); scaling the last layers spreads the
+    colours (std 0.13 at 16) and the densities (0.09 .. 11.7), so that an image comparison can tell a wrong MLP from a right one.
+    ref: another reference field (prepared by the caller, `contrast` is not applied to it) with view_dependent for the model and
+    `state`, the state-dict entries that differ from the plain field's."""
+    from nerfstyle_amd.common import BBox
+    from nerfstyle_amd.config import NetworkConfig, RendererConfig
+    from nerfstyle_amd.renderer import Renderer
+    from nerfstyle_amd.scene import load_room_cameras
+    from nerfstyle_amd.style_nerf import StyleTCNerf
+    if ref is None:
+        from oracle import torch_port as TP
+        ref = TP.Field(num_classes=nc, table_scale=table_scale)
+        if contrast != 1.0:
+            with torch.no_grad():
+                ref.p_density[2048:] *= contrast
+                ref.p_color2[-1024:] *= contrast
+                ref.p_class[2048:] *= contrast
+    m = StyleTCNerf(NetworkConfig(), BBox.from_radius(2.0), nc, enc_dtype=table_dtype, use_dir=False, compute_dtype=compute_dtype,
+                    view_dependent=view_dependent)
+    sd = m.state_dict()
+    sd.update({'x_density_embedder.embeddings': ref.emb_density.detach(), 'x_color_embedder.embeddings': ref.emb_color.detach(),
+               'density_net.params': ref.p_density.detach(), 'color1_net.params': ref.p_color1.detach(),
+               'color2_net.params': ref.p_color2.detach(), 'class_net.params': ref.p_class.detach()})
+    sd.update(state or {})
+    m.load_state_dict(sd)
+    poses, intr, _ = load_room_cameras()
+    r = Renderer(m, RendererConfig.llff(), intr, 2.0, raymarch_channels=3 + nc, samples_per_ray_cap=cap).to(dev)
+    grid, bits = small_scene()
+    r.density_grid = torch.tensor(grid, device=dev)
+    r.density_bitfield = torch.tensor(bits, device=dev)
+    r.update_occ = False                     # fixed synthetic occupancy
+    return r, ref, poses, intr, bits
 
 
 def rel_l2(a, b):

@@ -8,39 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import rel_l2, small_scene
+from helpers import rel_l2, small_scene, render_setup as _setup
 
 pytestmark = pytest.mark.gpu
-
-
-def _setup(dev, nc=5, table_dtype=torch.float32, table_scale=0.5, cap=None, contrast=1.0):
-    from nerfstyle_amd.common import BBox
-    from nerfstyle_amd.config import NetworkConfig, RendererConfig
-    from nerfstyle_amd.renderer import Renderer
-    from nerfstyle_amd.scene import load_room_cameras
-    from nerfstyle_amd.style_nerf import StyleTCNerf
-    from oracle import torch_port as TP
-    ref = TP.Field(num_classes=nc, table_scale=table_scale)
-    if contrast != 1.0:
-        # the seeded checkpoint is nearly grey (rgb 0.50 +- 0.009, sigma 1.0 +- 0.09): scaling the last layers spreads the colours
-        # (std 0.13 at 16) and the densities (0.09 .. 11.7), so that an image comparison can tell a wrong MLP from a right one
-        with torch.no_grad():
-            ref.p_density[2048:] *= contrast
-            ref.p_color2[-1024:] *= contrast
-            ref.p_class[2048:] *= contrast
-    m = StyleTCNerf(NetworkConfig(), BBox.from_radius(2.0), nc, enc_dtype=table_dtype, use_dir=False)
-    sd = m.state_dict()
-    sd.update({'x_density_embedder.embeddings': ref.emb_density.detach(), 'x_color_embedder.embeddings': ref.emb_color.detach(),
-               'density_net.params': ref.p_density.detach(), 'color1_net.params': ref.p_color1.detach(),
-               'color2_net.params': ref.p_color2.detach(), 'class_net.params': ref.p_class.detach()})
-    m.load_state_dict(sd)
-    poses, intr, _ = load_room_cameras()
-    r = Renderer(m, RendererConfig.llff(), intr, 2.0, raymarch_channels=3 + nc, samples_per_ray_cap=cap).to(dev)
-    grid, bits = small_scene()
-    r.density_grid = torch.tensor(grid, device=dev)
-    r.density_bitfield = torch.tensor(bits, device=dev)
-    r.update_occ = False                     # fixed synthetic occupancy
-    return r, ref, poses, intr, bits
 
 
 def _oracle_render(O, ref, bits, ro, rd, half=None, density_scale=1.0):
@@ -1106,4 +1076,21 @@ def test_begin_train_on_a_side_stream_equals_plain_render(O, dev):
         assert torch.equal(r._last_counter, want_cnt)
         assert torch.equal(r.step_counter[(step0 + 1) % r.step_counter.shape[0]], want_cnt)
         out['rgb_map'].sum().backward()
+    # the one asymmetry of the two marches, on 256 random rays of pose 0: the allocating call counts INTO its step's ring slot, the
+    # `into=` call counts into the static counter and copies it there -- same bookkeeping, same samples
+    r.local_step = 1
+    pose = torch.tensor(poses[0], device=dev)
+    pix = torch.randperm(intr.w * intr.h, device=dev, generator=g)[:256]
+    ctx = r.begin_train(pose, pix)
+    assert r.local_step == 2
+    count = int(ctx['mt']['counter'][0])
+    assert count > 0 and torch.equal(r.step_counter[1], ctx['mt']['counter'])
+    first = {k: ctx['mt'][k].clone() for k in ('counter', 'xyzs', 'deltas', 'rays_info')}
+    assert r.begin_train(pose, pix, into=ctx) is ctx
+    assert r.local_step == 3
+    assert torch.equal(r.step_counter[2], ctx['mt']['counter']) and int(ctx['mt']['counter'][0]) == count
+    assert torch.equal(ctx['mt']['counter'], first['counter'])
+    for k in ('xyzs', 'deltas'):
+        assert torch.equal(ctx['mt'][k][:count], first[k][:count]), k
+    assert torch.equal(ctx['mt']['rays_info'], first['rays_info'])
     r.update_occ = False

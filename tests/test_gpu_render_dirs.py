@@ -4,34 +4,19 @@ import pytest
 import torch
 
 import sh_ref as SH
-from helpers import rel_l2, small_scene
+from helpers import rel_l2, render_setup
 
 pytestmark = pytest.mark.gpu
 
 
 def _setup(dev, nc=5, cap=None, contrast=16.0):
-    from nerfstyle_amd.common import BBox
-    from nerfstyle_amd.config import NetworkConfig, RendererConfig
-    from nerfstyle_amd.renderer import Renderer
-    from nerfstyle_amd.scene import load_room_cameras
-    from nerfstyle_amd.style_nerf import StyleTCNerf
     ref = SH.FieldDirs(num_classes=nc)
-    with torch.no_grad():                          # colours and densities that vary across the image (test_gpu_render._setup)
+    with torch.no_grad():                          # colours and densities that vary across the image (helpers.render_setup)
         ref.p_density[2048:] *= contrast
         ref.p_color2[-1024:] *= contrast
         ref.p_sh *= 4.0                            # and a colour that really depends on the direction
-    m = StyleTCNerf(NetworkConfig(), BBox.from_radius(2.0), nc, enc_dtype=None, view_dependent=True)
-    sd = m.state_dict()
-    sd.update({'x_density_embedder.embeddings': ref.emb_density.detach(), 'x_color_embedder.embeddings': ref.emb_color.detach(),
-               'density_net.params': ref.p_density.detach(), 'color1_net.params': ref.p_color1.detach(),
-               'color2_net.params': ref.color2_params().detach(), 'class_net.params': ref.p_class.detach()})
-    m.load_state_dict(sd)
-    poses, intr, _ = load_room_cameras()
-    r = Renderer(m, RendererConfig.llff(), intr, 2.0, raymarch_channels=3 + nc, samples_per_ray_cap=cap).to(dev)
-    grid, bits = small_scene()
-    r.density_grid = torch.tensor(grid, device=dev)
-    r.density_bitfield = torch.tensor(bits, device=dev)
-    r.update_occ = False
+    r, _, poses, intr, _ = render_setup(dev, nc=nc, table_dtype=None, cap=cap, ref=ref, view_dependent=True,
+                                        state={'color2_net.params': ref.color2_params().detach()})
     r.cfg.density_scale = 40.0
     return r, poses, intr
 

@@ -9,42 +9,12 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import small_scene
+from helpers import render_setup as _setup
 
 pytestmark = pytest.mark.gpu
 
 PATCH = (100, 60, 256, 200)         # x, y, w, h on room pose 5
 OPAQUE = 400.0                      # density_scale at which the synthetic boxes are opaque surfaces
-
-
-def _setup(dev, nc=5, table_dtype=torch.float32, compute_dtype=torch.float16, cap=None, contrast=1.0):
-    """The seeded checkpoint of oracle/torch_port.py in a Renderer over the seeded synthetic occupancy (bound 2, H = 128), the way
-    tests/test_gpu_render.py sets its scene up.  contrast: last layers scaled so that colours and densities vary across the image."""
-    from nerfstyle_amd.common import BBox
-    from nerfstyle_amd.config import NetworkConfig, RendererConfig
-    from nerfstyle_amd.renderer import Renderer
-    from nerfstyle_amd.scene import load_room_cameras
-    from nerfstyle_amd.style_nerf import StyleTCNerf
-    from oracle import torch_port as TP
-    ref = TP.Field(num_classes=nc, table_scale=0.5)
-    if contrast != 1.0:
-        with torch.no_grad():
-            ref.p_density[2048:] *= contrast
-            ref.p_color2[-1024:] *= contrast
-            ref.p_class[2048:] *= contrast
-    m = StyleTCNerf(NetworkConfig(), BBox.from_radius(2.0), nc, enc_dtype=table_dtype, use_dir=False, compute_dtype=compute_dtype)
-    sd = m.state_dict()
-    sd.update({'x_density_embedder.embeddings': ref.emb_density.detach(), 'x_color_embedder.embeddings': ref.emb_color.detach(),
-               'density_net.params': ref.p_density.detach(), 'color1_net.params': ref.p_color1.detach(),
-               'color2_net.params': ref.p_color2.detach(), 'class_net.params': ref.p_class.detach()})
-    m.load_state_dict(sd)
-    poses, intr, _ = load_room_cameras()
-    r = Renderer(m, RendererConfig.llff(), intr, 2.0, raymarch_channels=3 + nc, samples_per_ray_cap=cap).to(dev)
-    grid, bits = small_scene()
-    r.density_grid = torch.tensor(grid, device=dev)
-    r.density_bitfield = torch.tensor(bits, device=dev)
-    r.update_occ = False
-    return r, ref, poses, intr, bits
 
 
 def _patch():

@@ -69,6 +69,34 @@ def test_renderer_state_keys():
     assert r.sample_capacity(4096) == 4096 * 1024
 
 
+def test_occupancy_frozen_restores_when_the_body_raises():
+    """Renderer.occupancy_frozen(): update_occ is off inside and back afterwards, also when the body raises; local_step and the
+    count ring are left alone either way."""
+    import pytest
+    from nerfstyle_amd.common import BBox, Intrinsics
+    from nerfstyle_amd.config import NetworkConfig, RendererConfig
+    from nerfstyle_amd.renderer import Renderer
+    from nerfstyle_amd.style_nerf import StyleTCNerf
+    m = StyleTCNerf(NetworkConfig(), BBox.from_radius(2.0), 5)
+    r = Renderer(m, RendererConfig.llff(), Intrinsics(378, 504, 383.8, 383.8, 252., 189.), 2.0, raymarch_channels=8)
+    r.local_step = 7
+    r.step_counter[:] = torch.arange(r.step_counter.numel(), dtype=torch.int32).view_as(r.step_counter)
+    ring = r.step_counter.clone()
+    for keep in (True, False):
+        r.update_occ = keep
+        with pytest.raises(ZeroDivisionError):
+            with r.occupancy_frozen():
+                assert r.update_occ is False and not r.occupancy_update_due()
+                counter, slot = r._call_counter()          # what a march inside asks for: a counter of its own, no bookkeeping
+                assert slot is None and counter.data_ptr() != r.step_counter.data_ptr() and not counter.any()
+                1 / 0
+        assert r.update_occ is keep
+        assert r.local_step == 7 and torch.equal(r.step_counter, ring)
+        with r.occupancy_frozen():
+            assert r.update_occ is False
+        assert r.update_occ is keep and r.local_step == 7 and torch.equal(r.step_counter, ring)
+
+
 def test_synthetic_scene_and_cameras(O):
     from nerfstyle_amd.scene import load_room_cameras, morton3d_np
     grid, bits = small_scene()

@@ -59,7 +59,7 @@ for name, training, fused in (('render_test', False, False), ('render_train(no_g
     elif fused:
         shaded = int(r.last_infer_stats()[0])
         note = '  shaded {} samples = {:.3f} of emitted'.format(shaded, shaded / max(emitted, 1))
-    elif getattr(r, 'last_test_overflow', False):
+    elif r.last_test_overflow:
         note = '  (buffer overflowed: fell back to the host loop)'
     print('{:24s} {}x{}: {:8.2f} ms/frame  ({:.2f} Mrays/s)  peak {:9.1f} MB{}'.format(
         name, intr.w, intr.h, ms, intr.w * intr.h / ms / 1e3, peak / 1e6, note))
