@@ -136,6 +136,28 @@ int nsr_render_train_backward(const float *grad_rgb_map, const float *grad_class
                               const float *weights_sum, const float *image, uint32_t M, uint32_t N, uint32_t C,
                               float T_thresh, float *grad_sigmas, float *grad_rgbs, nsr_stream_t stream);
 
+/* Per-ray geometry terms on the weights of the training composite (no reference counterpart: its composite backward drops
+ * grad_depth and the weights never leave its kernels).  Samples, columns (is_ndc), live rule and the "offset + steps < M"
+ * drop test are nsr_composite_rays_train_forward's; w_i its weights, t_i the running sum of deltas[:, col + 1],
+ * delta_i = deltas[:, col], R = fars[index] - nears[index]:
+ *   depth [N]      = max(sum_i w_i t_i - near, 0) / R            (what nsr_render_train_forward writes as depth_norm)
+ *   distortion [N] = (sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 delta_i) / R       (mip-NeRF 360, eq. 15)
+ * Both are 0 for a dropped ray, a ray without samples and a ray whose R is not a positive finite number (a ray that misses
+ * the box has near == far == FLT_MAX), where depth_norm is 0 / 0.
+ * totals: caller-allocated [N,4] f32 (16 B per ray), written by the forward and read by the backward.  deltas 8-byte aligned.
+ * No atomics, no host read, capture-safe; two calls give the same bits. */
+int nsr_ray_geometry_forward(const float *sigmas, const float *deltas, const int32_t *rays, const float *nears,
+                             const float *fars, uint32_t M, uint32_t N, float T_thresh, int is_ndc, float *depth,
+                             float *distortion, float *totals, nsr_stream_t stream);
+/* d/d sigmas of nsr_ray_geometry_forward from grad_depth [N] and grad_distortion [N] (each may be NULL = zero), with the
+ * live set held constant and exact on every live sample, the one the ray stops on included.  grad_sigmas [M] is WRITTEN
+ * (not accumulated) for every sample that belongs to a ray -- zeros behind the stop, for dropped rays and for rays without a
+ * range -- and left untouched elsewhere, so it need not arrive zeroed. */
+int nsr_ray_geometry_backward(const float *grad_depth, const float *grad_distortion, const float *sigmas,
+                              const float *deltas, const int32_t *rays, const float *nears, const float *fars,
+                              const float *totals, uint32_t M, uint32_t N, float T_thresh, int is_ndc, float *grad_sigmas,
+                              nsr_stream_t stream);
+
 /* Reconstruction loss of Trainer.calc_loss (trainers/base.py:251-304), value AND gradient in one pass:
  *   loss = mean((rgb_map - target_rgb[pix])^2) + ce_lambda * mean(logsumexp(classes) - classes[target_cls[pix]])
  * (nn.MSELoss + 0.001 * nn.CrossEntropyLoss on the class logits; the reference builds it from ~25 torch kernels and as

@@ -253,6 +253,152 @@ k_comp_bwd(CompArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// per-ray geometry terms on the training composite's weights: differentiable depth and the mip-NeRF 360 distortion
+// ---------------------------------------------------------------------------------------------------------------------
+// Samples, columns, live rule and trip structure are k_comp_fwd's (same alpha, same scans, so d has the bits of its depth).
+// With w_i the composite weights, t_i the running depth parameter and R = far - near:
+//   depth      = max(sum_i w_i t_i - near, 0) / R
+//   distortion = (sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 delta_i) / R
+// t never decreases along a ray, so the pair term is 2 sum_i w_i (t_i W_<i - S_<i) with the exclusive prefixes W = sum w,
+// S = sum w t: two more wave scans, no O(n^2) work.  The forward leaves (W, S, pair, self) of the whole ray in totals[index];
+// the backward walks the ray front to back once more (the live set needs T, which only exists in that direction) and takes
+// every "sum over the samples behind this one" as total minus inclusive prefix.  The prefixes of W and S are accumulated by the
+// same instructions as the totals, so on the last live sample that difference is exactly 0.
+// Unlike :961 the derivative is exact on every live sample, the stopping one included (the live set is held constant):
+//   f_k = G_depth [d > near] t_k / R + G_dist (2 sum_j w_j |t_k - t_j| + 2/3 w_k delta_k) / R        (d loss / d w_k)
+//   grad_sigma_i = delta_i (f_i T_{i+1} - sum_{k>i} f_k w_k),   T_{i+1} = T_i exp(-sigma_i delta_i)
+// (T_{i+1} from the exponential, not as T_i - w_i: behind an opaque sample that difference is 0 in fp32).
+// A ray whose R is not a positive finite number (a miss has near == far == FLT_MAX), a dropped ray and an empty one give 0 and
+// zero gradients.
+struct GeomArgs {
+    const float *sigmas, *deltas;
+    const int32_t *rays;
+    const float *nears, *fars;
+    uint32_t M, N;
+    float T_thresh;
+    int is_ndc;
+    float *depth, *distortion;             // forward outputs [N]
+    float *totals;                         // [N,4]: written by the forward, read by the backward
+    const float *g_depth, *g_dist;         // [N] each, either may be NULL (zero)
+    float *g_sigmas;                       // [M]
+};
+
+__device__ __forceinline__ bool cp_range_ok(float R) { return R > 0.0f && R <= 3.402823466e+38f; }
+
+__global__ void __launch_bounds__(CP_BLOCK)
+k_geom_fwd(GeomArgs a) {
+#pragma clang fp contract(off)                  // see k_comp_fwd
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t nwaves = gridDim.x * (CP_BLOCK / 64), gw = blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6);
+    uint32_t n = gw;
+    int32_t h0 = 0, h1 = 0, h2 = 0;
+    if (n < a.N) { h0 = a.rays[n * 3]; h1 = a.rays[n * 3 + 1]; h2 = a.rays[n * 3 + 2]; }
+    for (; n < a.N; n += nwaves) {
+        const uint32_t index = (uint32_t)__builtin_amdgcn_readfirstlane(h0), offset = (uint32_t)__builtin_amdgcn_readfirstlane(h1),
+                       steps = (uint32_t)__builtin_amdgcn_readfirstlane(h2);
+        const uint32_t nn = n + nwaves;
+        if (nn < a.N) { h0 = a.rays[nn * 3]; h1 = a.rays[nn * 3 + 1]; h2 = a.rays[nn * 3 + 2]; }     // next header in flight
+        const float nr = a.nears[index], R = a.fars[index] - nr;
+        float T = 1.0f, t = 0.0f, W = 0.0f, S = 0.0f, P = 0.0f, Q = 0.0f;
+        const bool ok = steps != 0 && offset + steps < a.M && cp_range_ok(R);
+        if (ok) {
+            for (uint32_t base = 0; base < steps; base += 64) {
+                const uint32_t i = base + lane;
+                const bool in = i < steps;
+                const size_t p = (size_t)offset + min(i, steps - 1u);
+                const float sg = a.sigmas[p];
+                const float2 dd = *reinterpret_cast<const float2 *>(a.deltas + p * 4 + (a.is_ndc ? 2 : 0));
+                const float alpha = in ? 1.0f - __expf(-sg * dd.x) : 0.0f;
+                const float incl = cp_scan_mul(1.0f - alpha);
+                const float Tb = T * cp_shift_up(incl, 1.0f);
+                const float tc = t + cp_scan_add(in ? dd.y : 0.0f);
+                const bool live = in && (i == 0u || Tb >= a.T_thresh);
+                const float w = live ? alpha * Tb : 0.0f;
+                const float wi = cp_scan_add(w), si = cp_scan_add(w * tc);
+                const float Wex = W + cp_shift_up(wi, 0.0f), Sex = S + cp_shift_up(si, 0.0f);   // over the samples in front
+                P += cp_sum(w * (tc * Wex - Sex));
+                Q += cp_sum(w * w * dd.x);
+                W += cp_lane(wi, 63);
+                S += cp_lane(si, 63);
+                T *= cp_lane(incl, 63);
+                t = cp_lane(tc, 63);
+                if (__ballot(in && !live) != 0ull || T < a.T_thresh) break;
+            }
+        }
+        // lane k holds total k
+        const float mine = lane == 0u ? W : lane == 1u ? S : lane == 2u ? P : Q;
+        if (lane < 4u) a.totals[(size_t)index * 4 + lane] = mine;
+        if (lane == 0) {
+            a.depth[index] = ok ? fmaxf(S - nr, 0.0f) / R : 0.0f;
+            a.distortion[index] = ok ? (2.0f * P + Q / 3.0f) / R : 0.0f;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(CP_BLOCK)
+k_geom_bwd(GeomArgs a) {
+#pragma clang fp contract(off)                  // see k_comp_fwd
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t nwaves = gridDim.x * (CP_BLOCK / 64), gw = blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6);
+    uint32_t n = gw;
+    int32_t h0 = 0, h1 = 0, h2 = 0;
+    if (n < a.N) { h0 = a.rays[n * 3]; h1 = a.rays[n * 3 + 1]; h2 = a.rays[n * 3 + 2]; }
+    for (; n < a.N; n += nwaves) {
+        const uint32_t index = (uint32_t)__builtin_amdgcn_readfirstlane(h0), offset = (uint32_t)__builtin_amdgcn_readfirstlane(h1),
+                       steps = (uint32_t)__builtin_amdgcn_readfirstlane(h2);
+        const uint32_t nn = n + nwaves;
+        if (nn < a.N) { h0 = a.rays[nn * 3]; h1 = a.rays[nn * 3 + 1]; h2 = a.rays[nn * 3 + 2]; }
+        if (steps == 0) continue;
+        uint32_t base = 0;
+        const float nr = a.nears[index], R = a.fars[index] - nr;
+        if (offset + steps < a.M && cp_range_ok(R)) {
+            const float tl = lane < 4u ? a.totals[(size_t)index * 4 + lane] : 0.0f;
+            const float Wt = cp_lane(tl, 0), St = cp_lane(tl, 1), Pt = cp_lane(tl, 2), Qt = cp_lane(tl, 3);
+            const float gd = a.g_depth ? a.g_depth[index] : 0.0f, gx = a.g_dist ? a.g_dist[index] : 0.0f;
+            const float cD = St > nr ? gd / R : 0.0f;                       // the clamp of the depth passes a gradient iff d > near
+            const float cX = gx / R;
+            // sum_k f_k w_k over the ray: the depth part is cD * d, the distortion numerator is homogeneous of degree 2 in w
+            const float Ft = cD * St + cX * (2.0f * (2.0f * Pt + Qt / 3.0f));
+            float T = 1.0f, t = 0.0f, W = 0.0f, S = 0.0f, F = 0.0f;
+            for (; base < steps; base += 64) {
+                const uint32_t i = base + lane;
+                const bool in = i < steps;
+                const size_t p = (size_t)offset + min(i, steps - 1u);
+                const float sg = a.sigmas[p];
+                const float2 dd = *reinterpret_cast<const float2 *>(a.deltas + p * 4 + (a.is_ndc ? 2 : 0));
+                const float om = in ? __expf(-sg * dd.x) : 1.0f;
+                const float alpha = 1.0f - om;
+                const float incl = cp_scan_mul(1.0f - alpha);               // (1 - alpha, not om: the forward's bits, the same live set)
+                const float Tb = T * cp_shift_up(incl, 1.0f);
+                const float tc = t + cp_scan_add(in ? dd.y : 0.0f);
+                const bool live = in && (i == 0u || Tb >= a.T_thresh);
+                const float w = live ? alpha * Tb : 0.0f;
+                const float wi = cp_scan_add(w), si = cp_scan_add(w * tc);
+                const float Wex = W + cp_shift_up(wi, 0.0f), Sex = S + cp_shift_up(si, 0.0f);
+                const float Win = W + wi, Sin = S + si;
+                // sum_j w_j |t_k - t_j|: the samples in front, then the samples behind (total - inclusive prefix)
+                const float A = (tc * Wex - Sex) + ((St - Sin) - tc * (Wt - Win));
+                const float f = cD * tc + cX * (2.0f * A + (2.0f / 3.0f) * (w * dd.x));
+                const float fi = F + cp_scan_add(f * w);
+                if (in) a.g_sigmas[p] = live ? dd.x * (f * (Tb * om) - (Ft - fi)) : 0.0f;
+                W += cp_lane(wi, 63);
+                S += cp_lane(si, 63);
+                F = cp_lane(fi, 63);
+                T *= cp_lane(incl, 63);
+                t = cp_lane(tc, 63);
+                if (__ballot(in && !live) != 0ull || T < a.T_thresh) { base += 64; break; }
+            }
+        }
+        // the samples behind an early stop, a dropped ray (inside the buffer only), a ray without a range: zeros
+        for (; base < steps; base += 64) {
+            const uint32_t i = base + lane;
+            const size_t p = (size_t)offset + i;
+            if (i < steps && p < a.M) a.g_sigmas[p] = 0.0f;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // reconstruction loss: value and gradient in one pass
 // ---------------------------------------------------------------------------------------------------------------------
 struct LossArgs {
@@ -410,6 +556,35 @@ int nsr_render_train_backward(const float *grad_rgb_map, const float *grad_class
     a.g_ws = grad_weights_sum; a.g_rgb_map = grad_rgb_map; a.g_classes = grad_classes; a.ws_in = weights_sum; a.image_in = image;
     a.g_sigmas = grad_sigmas; a.g_rgbs = grad_rgbs; a.zero_fill = 1; a.epilogue = 1;
     return cp_launch<true>(a, (hipStream_t)stream);
+}
+
+int nsr_ray_geometry_forward(const float *sigmas, const float *deltas, const int32_t *rays, const float *nears, const float *fars,
+                             uint32_t M, uint32_t N, float T_thresh, int is_ndc, float *depth, float *distortion, float *totals,
+                             nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
+    NSR_CHECK_PTR(depth); NSR_CHECK_PTR(distortion); NSR_CHECK_PTR(totals);
+    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
+    GeomArgs a = {};
+    a.sigmas = sigmas; a.deltas = deltas; a.rays = rays; a.nears = nears; a.fars = fars; a.M = M; a.N = N; a.T_thresh = T_thresh;
+    a.is_ndc = is_ndc; a.depth = depth; a.distortion = distortion; a.totals = totals;
+    hipLaunchKernelGGL(k_geom_fwd, dim3(cp_grid(N)), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
+    return nsr_launch_status();
+}
+
+int nsr_ray_geometry_backward(const float *grad_depth, const float *grad_distortion, const float *sigmas, const float *deltas,
+                              const int32_t *rays, const float *nears, const float *fars, const float *totals, uint32_t M,
+                              uint32_t N, float T_thresh, int is_ndc, float *grad_sigmas, nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
+    NSR_CHECK_PTR(totals); NSR_CHECK_PTR(grad_sigmas);
+    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
+    GeomArgs a = {};
+    a.sigmas = sigmas; a.deltas = deltas; a.rays = rays; a.nears = nears; a.fars = fars; a.M = M; a.N = N; a.T_thresh = T_thresh;
+    a.is_ndc = is_ndc; a.totals = const_cast<float *>(totals); a.g_depth = grad_depth; a.g_dist = grad_distortion;
+    a.g_sigmas = grad_sigmas;
+    hipLaunchKernelGGL(k_geom_bwd, dim3(cp_grid(N)), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
+    return nsr_launch_status();
 }
 
 uint64_t nsr_recon_loss_workspace_bytes(uint32_t N) {

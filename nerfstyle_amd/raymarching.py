@@ -7,7 +7,8 @@ composite_rays (:462).  Like the reference wrappers, inputs are cast to float32 
 contiguous; unlike them, nothing is silently moved to the GPU: a CPU tensor raises.
 
 Extra entry points with no reference counterpart (used by the renderer's fast path):
-march_rays_train_nosync (capacity-bounded, no `.item()`), compact_alive.
+march_rays_train_nosync (capacity-bounded, no `.item()`), compact_alive, ray_geometry (differentiable depth and
+distortion on the training composite's weights).
 """
 import torch
 from torch.autograd import Function
@@ -207,6 +208,61 @@ class _composite_rays_train(Function):
 
 
 composite_rays_train = _composite_rays_train.apply
+
+
+class _ray_geometry(Function):
+    """nsr_ray_geometry_forward / _backward (no reference counterpart): depth and distortion of every ray from the weights of
+    the training composite, with a gradient for sigmas alone."""
+
+    @staticmethod
+    def forward(ctx, sigmas, deltas, rays, nears, fars, T_thresh=1e-4, is_ndc=False, zero_unowned=True):
+        ctx.set_materialize_grads(False)     # an output the loss does not use arrives as None: NULL for the kernel
+        ctx.sigmas_shape = sigmas.shape
+        sigmas = sigmas.to(torch.float32).contiguous().view(-1)
+        deltas = deltas.contiguous()
+        nears, fars = _f32(nears).view(-1), _f32(fars).view(-1)
+        M, N = sigmas.shape[0], rays.shape[0]
+        dev = sigmas.device
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        distortion = torch.empty(N, dtype=torch.float32, device=dev)
+        totals = torch.empty(N, 4, dtype=torch.float32, device=dev)
+        with profiling.timed('geometry_fwd'):
+            L.check(L.lib().nsr_ray_geometry_forward(
+                L.p(sigmas), L.p(deltas), L.p(rays), L.p(nears), L.p(fars), M, N, float(T_thresh), int(bool(is_ndc)),
+                L.p(depth), L.p(distortion), L.p(totals), L.stream()), 'ray_geometry_forward')
+        ctx.save_for_backward(sigmas, deltas, rays, nears, fars, totals)
+        ctx.args = (M, N, float(T_thresh), int(bool(is_ndc)), bool(zero_unowned))
+        return depth, distortion
+
+    @staticmethod
+    def backward(ctx, grad_depth, grad_distortion):
+        if grad_depth is None and grad_distortion is None:
+            return (None,) * 8
+        sigmas, deltas, rays, nears, fars, totals = ctx.saved_tensors
+        M, N, T_thresh, is_ndc, zero_unowned = ctx.args
+
+        def prep(g):
+            return None if g is None else g.to(torch.float32).contiguous()
+        grad_depth, grad_distortion = prep(grad_depth), prep(grad_distortion)
+        # the kernel writes every sample that belongs to a ray; slots no ray owns keep what the buffer held
+        grad_sigmas = torch.zeros_like(sigmas) if zero_unowned else torch.empty_like(sigmas)
+        with profiling.timed('geometry_bwd'):
+            L.check(L.lib().nsr_ray_geometry_backward(
+                L.p(grad_depth), L.p(grad_distortion), L.p(sigmas), L.p(deltas), L.p(rays), L.p(nears), L.p(fars), L.p(totals),
+                M, N, T_thresh, is_ndc, L.p(grad_sigmas), L.stream()), 'ray_geometry_backward')
+        return (grad_sigmas.view(ctx.sigmas_shape),) + (None,) * 7
+
+
+def ray_geometry(sigmas, deltas, rays, nears, fars, T_thresh=1e-4, is_ndc=False, zero_unowned=True):
+    """Differentiable per-ray geometry terms on the weights w_i of composite_rays_train (same samples, delta columns and
+    stop rule) -> (depth [N], distortion [N]), R = fars - nears:
+      depth      = clamp(sum_i w_i t_i - nears, 0) / R: render_train's depth, but with a gradient;
+      distortion = (sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 delta_i) / R, the mip-NeRF 360 regulariser.
+    Both are 0 (and pass no gradient) for dropped and empty rays and where R is not a positive finite number, e.g. rays that
+    miss the box.  The gradient reaches `sigmas` only and is exact on every live sample, the one a ray stops on included.
+    zero_unowned=False hands the gradient's slots that no ray owns back uninitialised (capacity-sized buffers whose consumer
+    bounds itself by the rays, as the renderer's does)."""
+    return _ray_geometry.apply(sigmas, deltas, rays, nears, fars, T_thresh, is_ndc, zero_unowned)
 
 
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, z_hats, bound, density_bitfield,

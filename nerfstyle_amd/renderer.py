@@ -54,6 +54,10 @@ class Renderer(torch.nn.Module):
         # The no-grad training render through the same kernel with the TRAINING composite (render_train_fused): what pass 1
         # of the deferred stylisation iteration and validation renders ask for.  Opt-in; unmeasured on the GPU so far.
         self.fused_nograd_train = False
+        # Per-ray geometry terms of the training render (raymarching.ray_geometry on the shaded samples): a differentiable depth and
+        # the mip-NeRF 360 distortion, for depth supervision and a floater regulariser.  Opt-in: shade_train fills a `geometry` dict,
+        # render(training=True) / finish_train add 'depth' and 'distortion' to their output; render_test never does.
+        self.geometry_terms = False
         self.reference_inference_loop = False      # render_test through render_test_loop (the reference's iteration structure)
         self.last_test_overflow = False            # the last bounded-capacity render_test overflowed and fell back to the loop
         self._infer_stats = None
@@ -212,10 +216,11 @@ class Renderer(torch.nn.Module):
     def render_train(self, rays: RayBatch, **kwargs):
         """renderer.py:196-235 -> (image [N,3], depth [N], classes [N,nc]).  Three stages that graph.GraphedPatchBackward
         also drives one by one: march (sync-free), optional spatial order of the samples, shade (field + composite).
-        With `fused_nograd_train` set and autograd off the call is render_train_fused instead (non-NDC, all model channels)."""
+        With `fused_nograd_train` set and autograd off the call is render_train_fused instead (non-NDC, all model channels, and no
+        `geometry_terms`: the streaming kernel has no such outputs).  geometry=dict: see shade_train."""
         if self.fused_nograd_train and self.model.use_dir:
             raise NotImplementedError('fused_nograd_train: the streaming kernel has no direction input (view_dependent model)')
-        if (self.fused_nograd_train and not torch.is_grad_enabled() and not self.cfg.use_ndc
+        if (self.fused_nograd_train and not torch.is_grad_enabled() and not self.cfg.use_ndc and not self.geometry_terms
                 and self.raymarch_channels == self.model.out_channels):
             return self.render_train_fused(rays, dense_shape=kwargs.get('dense_shape'))
         if self.occupancy_update_due():
@@ -224,7 +229,7 @@ class Renderer(torch.nn.Module):
         perm = None
         if torch.is_grad_enabled() and self._use_spatial_order(mt['N'], bool(kwargs.get('dense', False))):
             perm = self.model.sample_order(mt['xyzs'], mt['counter'])
-        return self.shade_train(mt, perm)
+        return self.shade_train(mt, perm, geometry=kwargs.get('geometry'))
 
     @contextmanager
     def occupancy_frozen(self):
@@ -294,13 +299,19 @@ class Renderer(torch.nn.Module):
         into: the dict a previous call returned -- its tensors are written in place (static buffers of a captured step)."""
         return self._march(rays, into)
 
-    def shade_train(self, mt: dict, perm=None):
+    def shade_train(self, mt: dict, perm=None, geometry: Optional[dict] = None):
         """fused field on the marched samples + train composite with the epilogue of renderer.py:225-233 folded in
-        (nsr_render_train_forward / _backward): two autograd nodes, no torch glue between them"""
+        (nsr_render_train_forward / _backward): two autograd nodes, no torch glue between them.
+        geometry: with `geometry_terms` set, a dict that receives 'depth' [N] (the depth returned here, but differentiable) and
+        'distortion' [N] from a third node on the same sigmas (raymarching.ray_geometry); autograd adds its d/d sigmas to the
+        composite's.  Left alone with the switch off."""
         sigmas, rgbs = self.model.field(mt['xyzs'], sigma_only=False, m_dev=mt['counter'], density_scale=self.cfg.density_scale,
                                         perm=perm, dirs=mt.get('dirs'))
         image, depth, classes, _ = _render_train(sigmas, rgbs, mt['deltas'], mt['rays_info'], mt['nears'], mt['fars'],
                                                  self.cfg.t_thresh)
+        if geometry is not None and self.geometry_terms:
+            geometry['depth'], geometry['distortion'] = raymarching.ray_geometry(
+                sigmas, mt['deltas'], mt['rays_info'], mt['nears'], mt['fars'], self.cfg.t_thresh, False, zero_unowned=False)
         return image, depth, classes
 
     @torch.no_grad()
@@ -537,7 +548,9 @@ class Renderer(torch.nn.Module):
         if ctx.get('stream') is not None:
             torch.cuda.current_stream(self.device).wait_stream(ctx['stream'])
         out = {'target': None}
-        out['rgb_map'], out['trans_map'], out['classes'] = self.shade_train(ctx['mt'], ctx['perm'])
+        geometry = {} if self.geometry_terms else None
+        out['rgb_map'], out['trans_map'], out['classes'] = self.shade_train(ctx['mt'], ctx['perm'], geometry=geometry)
+        out.update(geometry or {})
         self._set_last(ctx['mt']['counter'], ctx['mt']['M'])
         return out
 
@@ -554,10 +567,14 @@ class Renderer(torch.nn.Module):
         if dense is None:
             dense = pix_subset is None and num_rays is None
         extra = {}
-        fused = self.fused_nograd_train and not torch.is_grad_enabled() if training else self.fused_inference
+        fused = (self.fused_nograd_train and not torch.is_grad_enabled() and not self.geometry_terms) if training else self.fused_inference
         if fused and dense and pix_subset is None and num_rays is None:
             extra['dense_shape'] = pixel_window(self.intr, patch, precrop_frac)[:2]
+        geometry = {} if training and self.geometry_terms else None
+        if geometry is not None:
+            extra['geometry'] = geometry
         output['rgb_map'], output['trans_map'], output['classes'] = render_fn(rays, dense=dense, **extra)
+        output.update(geometry or {})
         return output
 
 
