@@ -1,24 +1,23 @@
-// Training composite (raymarching.cu:806-997), the render_train epilogue (renderer.py:225-233) and the reconstruction
-// loss (trainers/base.py:251-304: MSE + lambda * cross-entropy) as three gfx950 kernels -- round 3.
+// Training composite (raymarching.cu:806-997) with the render_train epilogue (renderer.py:225-233), the per-ray geometry terms
+// (differentiable depth, mip-NeRF 360 distortion) and the reconstruction loss (trainers/base.py:251-304) for gfx950.
 //
-// Rounds 1-2 gave a ray to a group of 4/8/16 lanes (one channel per lane) that walked the ray's samples one after the
-// other: a serial dependence chain per ray, waves as long as their longest ray, 1.25 + 1.85 ms on the bench frame for
-// 2.5 + 4.3 GB (0.25 of the HBM roofline), followed by ~50 small torch kernels for the white background, the slices, the
-// MSE, the log-sum-exp and their backward (1.7 ms).  Here a WAVE owns a ray and a LANE owns a sample:
+// In the four ray kernels (k_comp_fwd, k_comp_bwd, k_geom_fwd, k_geom_bwd) a WAVE owns a ray and a LANE owns a sample:
 //   * 64 consecutive samples of the ray per trip: sigma / delta / colour rows are whole contiguous pieces of the sample
 //     buffers (16-byte loads for C = 4 or 8);
-//   * the recurrences become wave scans on the DPP network (row_shr 1/2/4/8, row_bcast 15/31): transmittance = exclusive
+//   * the recurrences are wave scans on the DPP network (row_shr 1/2/4/8, row_bcast 15/31): transmittance = exclusive
 //     product scan of (1 - alpha), t = inclusive sum scan of the step lengths, the backward's running colour = inclusive
 //     sum scans of weight * colour; sums over the ray are lane 63 of a scan; a carry (T, t, sums) links the trips of a
 //     ray longer than 64 samples; the early stop (T < T_thresh, :862 / :961) is a ballot;
 //   * persistent waves (grid-stride over rays), the next ray's header in flight while this one is evaluated;
-//   * the forward also writes what Renderer.render_train returns (image[:, :3] + (1 - weights_sum), the class channels,
-//     (depth - near) clamped / (far - near)), the backward takes the gradients of exactly those outputs.
+//   * the composite forward also writes what Renderer.render_train returns (image[:, :3] + (1 - weights_sum), the class
+//     channels, (depth - near) clamped / (far - near)), its backward takes the gradients of exactly those outputs.
+// Written once: the ray walk (CpWalk, all four), the trip carry and early stop (cp_carry, cp_stopped, all four) and the zeros behind
+// a stop and on a dropped ray (cp_zero_tail, the two backwards).  The trip front is spelled out per kernel (why).
 // The scans reassociate the reference's serial fp32 products and sums: results differ from the oracle in the last bits
 // (tests: <= 2e-5 absolute), and are bit-identical from run to run.
 //
 // The loss kernel is one thread per ray (value + gradient in one pass, targets gathered through the pixel indices), a
-// block tree for the value and a second one-block kernel that adds the block partials in a fixed order.
+// block tree for the value and a second one-block kernel that adds the block partials in a fixed order (cp_block_sum2 in both).
 #include "nsr_common.h"
 
 #define CP_MAXC 16
@@ -87,6 +86,38 @@ __device__ __forceinline__ void cp_load_row(const float *__restrict__ rgbs, size
     }
 }
 
+// persistent ray walk: wave gw takes rays gw, gw + nwaves, ...; header() hands out the wave-uniform header of ray n, then issues the
+// load of the next one.  The caller's loop advances n (r.n += r.nwaves): doing it inside header() cost k_comp_fwd<8> 26 VGPRs.
+struct CpWalk {
+    const int32_t *rays;
+    uint32_t N, nwaves, n;
+    int32_t h0 = 0, h1 = 0, h2 = 0;        // header of ray n (after header(): of ray n + nwaves), one copy per lane
+    uint32_t index, offset, steps;         // the current ray's, wave-uniform
+    __device__ __forceinline__ CpWalk(const int32_t *rays_, uint32_t N_)
+        : rays(rays_), N(N_), nwaves(gridDim.x * (CP_BLOCK / 64)), n(blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6)) { load(n); }
+    __device__ __forceinline__ void load(uint32_t m) { if (m < N) { h0 = rays[m * 3]; h1 = rays[m * 3 + 1]; h2 = rays[m * 3 + 2]; } }
+    __device__ __forceinline__ void header() {
+        index = (uint32_t)__builtin_amdgcn_readfirstlane(h0), offset = (uint32_t)__builtin_amdgcn_readfirstlane(h1), steps = (uint32_t)__builtin_amdgcn_readfirstlane(h2);
+        load(n + nwaves);                  // next header in flight
+    }
+};
+
+// carry into the next trip; whether the ray ends in this one (a sample of it is not live)
+__device__ __forceinline__ void cp_carry(float &T, float incl) { T *= cp_lane(incl, 63); }
+__device__ __forceinline__ void cp_carry(float &T, float &t, float incl, float tc) { cp_carry(T, incl); t = cp_lane(tc, 63); }
+__device__ __forceinline__ bool cp_stopped(bool in, bool live) { return __ballot(in && !live) != 0ull; }
+// zeros from `base` to the ray's end inside the buffer: behind an early stop, a dropped ray (:929), one without a range.  C == 0: sigmas only
+__device__ __forceinline__ void cp_zero_tail(uint32_t offset, uint32_t steps, uint32_t base, uint32_t lane, uint32_t M, float *g_sigmas, float *g_rgbs, uint32_t C) {
+    for (; base < steps; base += 64) {
+        const uint32_t i = base + lane;
+        const size_t p = (size_t)offset + i;
+        if (i < steps && p < M) {
+            g_sigmas[p] = 0.0f;
+            for (uint32_t k = 0; k < C; k++) g_rgbs[p * C + k] = 0.0f;
+        }
+    }
+}
+
 template <int CT>
 __global__ void __launch_bounds__(CP_BLOCK)
 k_comp_fwd(CompArgs a) {
@@ -95,16 +126,10 @@ k_comp_fwd(CompArgs a) {
 #pragma clang fp contract(off)
     constexpr int NC = CT ? CT : CP_MAXC;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nwaves = gridDim.x * (CP_BLOCK / 64), gw = blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6);
     const uint32_t C = CT ? (uint32_t)CT : a.C;
-    uint32_t n = gw;
-    int32_t h0 = 0, h1 = 0, h2 = 0;
-    if (n < a.N) { h0 = a.rays[n * 3]; h1 = a.rays[n * 3 + 1]; h2 = a.rays[n * 3 + 2]; }
-    for (; n < a.N; n += nwaves) {
-        const uint32_t index = (uint32_t)__builtin_amdgcn_readfirstlane(h0), offset = (uint32_t)__builtin_amdgcn_readfirstlane(h1),
-                       steps = (uint32_t)__builtin_amdgcn_readfirstlane(h2);
-        const uint32_t nn = n + nwaves;
-        if (nn < a.N) { h0 = a.rays[nn * 3]; h1 = a.rays[nn * 3 + 1]; h2 = a.rays[nn * 3 + 2]; }     // next header in flight
+    for (CpWalk r(a.rays, a.N); r.n < a.N; r.n += r.nwaves) {
+        r.header();
+        const uint32_t index = r.index, offset = r.offset, steps = r.steps;
         float T = 1.0f, t = 0.0f, ws = 0.0f, d = 0.0f;
         float acc[NC];
 #pragma unroll
@@ -130,9 +155,8 @@ k_comp_fwd(CompArgs a) {
 #pragma unroll
                 for (int k = 0; k < NC; k++)
                     if (CT || (uint32_t)k < C) acc[k] += cp_sum(w * c[k]);
-                T *= cp_lane(incl, 63);
-                t = cp_lane(tc, 63);
-                if (__ballot(in && !live) != 0ull || T < a.T_thresh) break;
+                cp_carry(T, t, incl, tc);
+                if (cp_stopped(in, live) || T < a.T_thresh) break;
             }
         }
         // lane k holds channel k
@@ -159,16 +183,10 @@ k_comp_bwd(CompArgs a) {
 #pragma clang fp contract(off)                  // see k_comp_fwd
     constexpr int NC = CT ? CT : CP_MAXC;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nwaves = gridDim.x * (CP_BLOCK / 64), gw = blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6);
     const uint32_t C = CT ? (uint32_t)CT : a.C;
-    uint32_t n = gw;
-    int32_t h0 = 0, h1 = 0, h2 = 0;
-    if (n < a.N) { h0 = a.rays[n * 3]; h1 = a.rays[n * 3 + 1]; h2 = a.rays[n * 3 + 2]; }
-    for (; n < a.N; n += nwaves) {
-        const uint32_t index = (uint32_t)__builtin_amdgcn_readfirstlane(h0), offset = (uint32_t)__builtin_amdgcn_readfirstlane(h1),
-                       steps = (uint32_t)__builtin_amdgcn_readfirstlane(h2);
-        const uint32_t nn = n + nwaves;
-        if (nn < a.N) { h0 = a.rays[nn * 3]; h1 = a.rays[nn * 3 + 1]; h2 = a.rays[nn * 3 + 2]; }
+    for (CpWalk r(a.rays, a.N); r.n < a.N; r.n += r.nwaves) {
+        r.header();
+        const uint32_t index = r.index, offset = r.offset, steps = r.steps;
         if (steps == 0) continue;
         uint32_t base = 0;
         if (offset + steps < a.M) {
@@ -234,21 +252,11 @@ k_comp_bwd(CompArgs a) {
                             if ((uint32_t)k < C) a.g_rgbs[p * C + k] = gc[k];
                     }
                 }
-                T *= cp_lane(incl, 63);
-                if (__ballot(in && !live) != 0ull) { base += 64; break; }
+                cp_carry(T, incl);
+                if (cp_stopped(in, live)) { base += 64; break; }
             }
         }
-        // dropped ray (:929, inside the buffer only) or the samples behind an early stop: the zero the reference pre-fills
-        if (a.zero_fill) {
-            for (; base < steps; base += 64) {
-                const uint32_t i = base + lane;
-                const size_t p = (size_t)offset + i;
-                if (i < steps && p < a.M) {
-                    a.g_sigmas[p] = 0.0f;
-                    for (uint32_t k = 0; k < C; k++) a.g_rgbs[p * C + k] = 0.0f;
-                }
-            }
-        }
+        if (a.zero_fill) cp_zero_tail(offset, steps, base, lane, a.M, a.g_sigmas, a.g_rgbs, C);
     }
 }
 
@@ -289,15 +297,9 @@ __global__ void __launch_bounds__(CP_BLOCK)
 k_geom_fwd(GeomArgs a) {
 #pragma clang fp contract(off)                  // see k_comp_fwd
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nwaves = gridDim.x * (CP_BLOCK / 64), gw = blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6);
-    uint32_t n = gw;
-    int32_t h0 = 0, h1 = 0, h2 = 0;
-    if (n < a.N) { h0 = a.rays[n * 3]; h1 = a.rays[n * 3 + 1]; h2 = a.rays[n * 3 + 2]; }
-    for (; n < a.N; n += nwaves) {
-        const uint32_t index = (uint32_t)__builtin_amdgcn_readfirstlane(h0), offset = (uint32_t)__builtin_amdgcn_readfirstlane(h1),
-                       steps = (uint32_t)__builtin_amdgcn_readfirstlane(h2);
-        const uint32_t nn = n + nwaves;
-        if (nn < a.N) { h0 = a.rays[nn * 3]; h1 = a.rays[nn * 3 + 1]; h2 = a.rays[nn * 3 + 2]; }     // next header in flight
+    for (CpWalk r(a.rays, a.N); r.n < a.N; r.n += r.nwaves) {
+        r.header();
+        const uint32_t index = r.index, offset = r.offset, steps = r.steps;
         const float nr = a.nears[index], R = a.fars[index] - nr;
         float T = 1.0f, t = 0.0f, W = 0.0f, S = 0.0f, P = 0.0f, Q = 0.0f;
         const bool ok = steps != 0 && offset + steps < a.M && cp_range_ok(R);
@@ -320,9 +322,8 @@ k_geom_fwd(GeomArgs a) {
                 Q += cp_sum(w * w * dd.x);
                 W += cp_lane(wi, 63);
                 S += cp_lane(si, 63);
-                T *= cp_lane(incl, 63);
-                t = cp_lane(tc, 63);
-                if (__ballot(in && !live) != 0ull || T < a.T_thresh) break;
+                cp_carry(T, t, incl, tc);
+                if (cp_stopped(in, live) || T < a.T_thresh) break;
             }
         }
         // lane k holds total k
@@ -339,15 +340,9 @@ __global__ void __launch_bounds__(CP_BLOCK)
 k_geom_bwd(GeomArgs a) {
 #pragma clang fp contract(off)                  // see k_comp_fwd
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nwaves = gridDim.x * (CP_BLOCK / 64), gw = blockIdx.x * (CP_BLOCK / 64) + (threadIdx.x >> 6);
-    uint32_t n = gw;
-    int32_t h0 = 0, h1 = 0, h2 = 0;
-    if (n < a.N) { h0 = a.rays[n * 3]; h1 = a.rays[n * 3 + 1]; h2 = a.rays[n * 3 + 2]; }
-    for (; n < a.N; n += nwaves) {
-        const uint32_t index = (uint32_t)__builtin_amdgcn_readfirstlane(h0), offset = (uint32_t)__builtin_amdgcn_readfirstlane(h1),
-                       steps = (uint32_t)__builtin_amdgcn_readfirstlane(h2);
-        const uint32_t nn = n + nwaves;
-        if (nn < a.N) { h0 = a.rays[nn * 3]; h1 = a.rays[nn * 3 + 1]; h2 = a.rays[nn * 3 + 2]; }
+    for (CpWalk r(a.rays, a.N); r.n < a.N; r.n += r.nwaves) {
+        r.header();
+        const uint32_t index = r.index, offset = r.offset, steps = r.steps;
         if (steps == 0) continue;
         uint32_t base = 0;
         const float nr = a.nears[index], R = a.fars[index] - nr;
@@ -384,17 +379,11 @@ k_geom_bwd(GeomArgs a) {
                 W += cp_lane(wi, 63);
                 S += cp_lane(si, 63);
                 F = cp_lane(fi, 63);
-                T *= cp_lane(incl, 63);
-                t = cp_lane(tc, 63);
-                if (__ballot(in && !live) != 0ull || T < a.T_thresh) { base += 64; break; }
+                cp_carry(T, t, incl, tc);
+                if (cp_stopped(in, live) || T < a.T_thresh) { base += 64; break; }
             }
         }
-        // the samples behind an early stop, a dropped ray (inside the buffer only), a ray without a range: zeros
-        for (; base < steps; base += 64) {
-            const uint32_t i = base + lane;
-            const size_t p = (size_t)offset + i;
-            if (i < steps && p < a.M) a.g_sigmas[p] = 0.0f;
-        }
+        cp_zero_tail(offset, steps, base, lane, a.M, a.g_sigmas, nullptr, 0u);
     }
 }
 
@@ -415,9 +404,20 @@ struct LossArgs {
     uint32_t nblocks;
 };
 
+// fixed-order block tree over two values: true on thread 0, which leaves with the block's sums in (x, y)
+__device__ __forceinline__ bool cp_block_sum2(float &x, float &y) {
+    __shared__ float red[2][CP_BLOCK / 64];
+    for (int off = 32; off >= 1; off >>= 1) { x += __shfl_xor(x, off, 64); y += __shfl_xor(y, off, 64); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = x; red[1][threadIdx.x >> 6] = y; }
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+    x = y = 0.0f;
+    for (int w = 0; w < CP_BLOCK / 64; w++) { x += red[0][w]; y += red[1][w]; }
+    return true;
+}
+
 __global__ void __launch_bounds__(CP_BLOCK)
 k_recon_loss(LossArgs a) {
-    __shared__ float red[2][CP_BLOCK / 64];
     const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
     const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
     float mse = 0.0f, ce = 0.0f;
@@ -443,31 +443,19 @@ k_recon_loss(LossArgs a) {
             for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
         }
     }
-    // fixed-order block tree
-    for (int off = 32; off >= 1; off >>= 1) { mse += __shfl_xor(mse, off, 64); ce += __shfl_xor(ce, off, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = mse; red[1][threadIdx.x >> 6] = ce; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = 0.0f, c = 0.0f;
-        for (int w = 0; w < CP_BLOCK / 64; w++) { m += red[0][w]; c += red[1][w]; }
-        a.partials[blockIdx.x * 2] = m;
-        a.partials[blockIdx.x * 2 + 1] = c;
+    if (cp_block_sum2(mse, ce)) {
+        a.partials[blockIdx.x * 2] = mse;
+        a.partials[blockIdx.x * 2 + 1] = ce;
     }
 }
 
 __global__ void __launch_bounds__(CP_BLOCK)
 k_recon_loss_final(LossArgs a) {
-    __shared__ float red[2][CP_BLOCK / 64];
     float mse = 0.0f, ce = 0.0f;
     for (uint32_t b = threadIdx.x; b < a.nblocks; b += CP_BLOCK) { mse += a.partials[b * 2]; ce += a.partials[b * 2 + 1]; }
-    for (int off = 32; off >= 1; off >>= 1) { mse += __shfl_xor(mse, off, 64); ce += __shfl_xor(ce, off, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = mse; red[1][threadIdx.x >> 6] = ce; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = 0.0f, c = 0.0f;
-        for (int w = 0; w < CP_BLOCK / 64; w++) { m += red[0][w]; c += red[1][w]; }
-        m /= 3.0f * (float)a.N;
-        c = c / (float)a.N * a.ce_lambda;
+    if (cp_block_sum2(mse, ce)) {
+        const float m = mse / (3.0f * (float)a.N);
+        const float c = ce / (float)a.N * a.ce_lambda;
         const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
         a.out[0] = (m + c) * s;
         a.out[1] = m;
@@ -475,10 +463,11 @@ k_recon_loss_final(LossArgs a) {
     }
 }
 
-static uint32_t cp_grid(uint32_t N) {
-    // persistent waves: 256 CUs x 8 blocks of 4 waves; fewer when there are fewer rays
+// 256 CUs x 8 blocks of 4 waves: the persistent grid of the ray kernels, the cap of the loss grid and with it the loss workspace
+static constexpr uint32_t CP_MAX_BLOCKS = 2048u;
+static uint32_t cp_grid(uint32_t N) {       // fewer blocks when there are fewer rays
     const uint32_t want = nsr_div_up(N, CP_BLOCK / 64);
-    return want < 2048u ? (want ? want : 1u) : 2048u;
+    return want < CP_MAX_BLOCKS ? (want ? want : 1u) : CP_MAX_BLOCKS;
 }
 
 template <bool BWD>
@@ -495,19 +484,37 @@ static int cp_launch(const CompArgs &a, hipStream_t s) {
     return nsr_launch_status();
 }
 
+// what the four composite entry points share: the common pointers (an entry point checks its own first: the same status), the range
+// of C (from 1, or from 3 with the epilogue), deltas aligned where the kernel loads delta pairs (the backwards read 4 bytes), the fields
+static int cp_args(CompArgs &a, const float *sigmas, const float *rgbs, const float *deltas, const int32_t *rays, uint32_t M, uint32_t N,
+                   uint32_t C, float T_thresh, int is_ndc, uint32_t min_C, bool delta_pairs) {
+    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(rgbs); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays);
+    if (C < min_C || C > CP_MAXC) return NSR_ERR_UNSUPPORTED;
+    if (delta_pairs && ((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
+    a = {};
+    a.sigmas = sigmas; a.rgbs = rgbs; a.deltas = deltas; a.rays = rays; a.M = M; a.N = N; a.C = C; a.T_thresh = T_thresh; a.is_ndc = is_ndc;
+    return NSR_OK;
+}
+
+static int cp_geom_args(GeomArgs &a, const float *sigmas, const float *deltas, const int32_t *rays, const float *nears, const float *fars,
+                        uint32_t M, uint32_t N, float T_thresh, int is_ndc) {
+    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
+    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
+    a = {};
+    a.sigmas = sigmas; a.deltas = deltas; a.rays = rays; a.nears = nears; a.fars = fars; a.M = M; a.N = N; a.T_thresh = T_thresh; a.is_ndc = is_ndc;
+    return NSR_OK;
+}
+
 extern "C" {
 
 int nsr_composite_rays_train_forward(const float *sigmas, const float *rgbs, const float *deltas, const int32_t *rays,
                                      uint32_t M, uint32_t N, uint32_t C, float T_thresh, int is_ndc, float *weights_sum,
                                      float *depth, float *image, nsr_stream_t stream) {
     if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(rgbs); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays);
     NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(depth); NSR_CHECK_PTR(image);
-    if (C == 0 || C > CP_MAXC) return NSR_ERR_UNSUPPORTED;
-    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
-    CompArgs a = {};
-    a.sigmas = sigmas; a.rgbs = rgbs; a.deltas = deltas; a.rays = rays; a.M = M; a.N = N; a.C = C; a.T_thresh = T_thresh;
-    a.is_ndc = is_ndc; a.weights_sum = weights_sum; a.depth = depth; a.image = image;
+    CompArgs a;
+    if (const int e = cp_args(a, sigmas, rgbs, deltas, rays, M, N, C, T_thresh, is_ndc, 1u, true)) return e;
+    a.weights_sum = weights_sum; a.depth = depth; a.image = image;
     return cp_launch<false>(a, (hipStream_t)stream);
 }
 
@@ -516,13 +523,11 @@ int nsr_composite_rays_train_backward(const float *grad_weights_sum, const float
                                       const float *weights_sum, const float *image, uint32_t M, uint32_t N, uint32_t C,
                                       float T_thresh, float *grad_sigmas, float *grad_rgbs, nsr_stream_t stream) {
     if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(grad_weights_sum); NSR_CHECK_PTR(grad_image); NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(rgbs);
-    NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(image);
+    NSR_CHECK_PTR(grad_weights_sum); NSR_CHECK_PTR(grad_image); NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(image);
     NSR_CHECK_PTR(grad_sigmas); NSR_CHECK_PTR(grad_rgbs);
-    if (C == 0 || C > CP_MAXC) return NSR_ERR_UNSUPPORTED;
-    CompArgs a = {};
-    a.sigmas = sigmas; a.rgbs = rgbs; a.deltas = deltas; a.rays = rays; a.M = M; a.N = N; a.C = C; a.T_thresh = T_thresh;
-    a.is_ndc = is_ndc; a.g_ws = grad_weights_sum; a.g_image = grad_image; a.ws_in = weights_sum; a.image_in = image;
+    CompArgs a;
+    if (const int e = cp_args(a, sigmas, rgbs, deltas, rays, M, N, C, T_thresh, is_ndc, 1u, false)) return e;
+    a.g_ws = grad_weights_sum; a.g_image = grad_image; a.ws_in = weights_sum; a.image_in = image;
     a.g_sigmas = grad_sigmas; a.g_rgbs = grad_rgbs; a.zero_fill = 1;
     return cp_launch<true>(a, (hipStream_t)stream);
 }
@@ -531,13 +536,11 @@ int nsr_render_train_forward(const float *sigmas, const float *rgbs, const float
                              const float *fars, uint32_t M, uint32_t N, uint32_t C, float T_thresh, float *weights_sum,
                              float *depth, float *image, float *rgb_map, float *depth_norm, float *classes, nsr_stream_t stream) {
     if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(rgbs); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
+    NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
     NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(depth); NSR_CHECK_PTR(image); NSR_CHECK_PTR(rgb_map); NSR_CHECK_PTR(depth_norm);
-    if (C < 3 || C > CP_MAXC) return NSR_ERR_UNSUPPORTED;
+    CompArgs a;
+    if (const int e = cp_args(a, sigmas, rgbs, deltas, rays, M, N, C, T_thresh, 0, 3u, true)) return e;
     if (C > 3 && classes == nullptr) return NSR_ERR_INVALID_ARG;
-    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
-    CompArgs a = {};
-    a.sigmas = sigmas; a.rgbs = rgbs; a.deltas = deltas; a.rays = rays; a.M = M; a.N = N; a.C = C; a.T_thresh = T_thresh;
     a.weights_sum = weights_sum; a.depth = depth; a.image = image; a.nears = nears; a.fars = fars; a.rgb_map = rgb_map;
     a.depth_norm = depth_norm; a.classes = classes; a.epilogue = 1;
     return cp_launch<false>(a, (hipStream_t)stream);
@@ -548,11 +551,9 @@ int nsr_render_train_backward(const float *grad_rgb_map, const float *grad_class
                               const float *image, uint32_t M, uint32_t N, uint32_t C, float T_thresh, float *grad_sigmas,
                               float *grad_rgbs, nsr_stream_t stream) {
     if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(rgbs); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(weights_sum);
-    NSR_CHECK_PTR(image); NSR_CHECK_PTR(grad_sigmas); NSR_CHECK_PTR(grad_rgbs);
-    if (C < 3 || C > CP_MAXC) return NSR_ERR_UNSUPPORTED;
-    CompArgs a = {};
-    a.sigmas = sigmas; a.rgbs = rgbs; a.deltas = deltas; a.rays = rays; a.M = M; a.N = N; a.C = C; a.T_thresh = T_thresh;
+    NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(image); NSR_CHECK_PTR(grad_sigmas); NSR_CHECK_PTR(grad_rgbs);
+    CompArgs a;
+    if (const int e = cp_args(a, sigmas, rgbs, deltas, rays, M, N, C, T_thresh, 0, 3u, false)) return e;
     a.g_ws = grad_weights_sum; a.g_rgb_map = grad_rgb_map; a.g_classes = grad_classes; a.ws_in = weights_sum; a.image_in = image;
     a.g_sigmas = grad_sigmas; a.g_rgbs = grad_rgbs; a.zero_fill = 1; a.epilogue = 1;
     return cp_launch<true>(a, (hipStream_t)stream);
@@ -562,12 +563,10 @@ int nsr_ray_geometry_forward(const float *sigmas, const float *deltas, const int
                              uint32_t M, uint32_t N, float T_thresh, int is_ndc, float *depth, float *distortion, float *totals,
                              nsr_stream_t stream) {
     if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
     NSR_CHECK_PTR(depth); NSR_CHECK_PTR(distortion); NSR_CHECK_PTR(totals);
-    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
-    GeomArgs a = {};
-    a.sigmas = sigmas; a.deltas = deltas; a.rays = rays; a.nears = nears; a.fars = fars; a.M = M; a.N = N; a.T_thresh = T_thresh;
-    a.is_ndc = is_ndc; a.depth = depth; a.distortion = distortion; a.totals = totals;
+    GeomArgs a;
+    if (const int e = cp_geom_args(a, sigmas, deltas, rays, nears, fars, M, N, T_thresh, is_ndc)) return e;
+    a.depth = depth; a.distortion = distortion; a.totals = totals;
     hipLaunchKernelGGL(k_geom_fwd, dim3(cp_grid(N)), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
     return nsr_launch_status();
 }
@@ -576,20 +575,17 @@ int nsr_ray_geometry_backward(const float *grad_depth, const float *grad_distort
                               const int32_t *rays, const float *nears, const float *fars, const float *totals, uint32_t M,
                               uint32_t N, float T_thresh, int is_ndc, float *grad_sigmas, nsr_stream_t stream) {
     if (N == 0) return NSR_OK;
-    NSR_CHECK_PTR(sigmas); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
     NSR_CHECK_PTR(totals); NSR_CHECK_PTR(grad_sigmas);
-    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
-    GeomArgs a = {};
-    a.sigmas = sigmas; a.deltas = deltas; a.rays = rays; a.nears = nears; a.fars = fars; a.M = M; a.N = N; a.T_thresh = T_thresh;
-    a.is_ndc = is_ndc; a.totals = const_cast<float *>(totals); a.g_depth = grad_depth; a.g_dist = grad_distortion;
-    a.g_sigmas = grad_sigmas;
+    GeomArgs a;
+    if (const int e = cp_geom_args(a, sigmas, deltas, rays, nears, fars, M, N, T_thresh, is_ndc)) return e;
+    a.totals = const_cast<float *>(totals); a.g_depth = grad_depth; a.g_dist = grad_distortion; a.g_sigmas = grad_sigmas;
     hipLaunchKernelGGL(k_geom_bwd, dim3(cp_grid(N)), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
     return nsr_launch_status();
 }
 
 uint64_t nsr_recon_loss_workspace_bytes(uint32_t N) {
     (void)N;
-    return 2048ull * 2 * sizeof(float);
+    return (uint64_t)CP_MAX_BLOCKS * 2 * sizeof(float);
 }
 
 int nsr_recon_loss(const float *rgb_map, const float *classes, uint32_t N, uint32_t nc, const float *target_rgb,
@@ -605,7 +601,7 @@ int nsr_recon_loss(const float *rgb_map, const float *classes, uint32_t N, uint3
     a.N = N; a.nc = with_ce ? nc : 0u; a.ce_lambda = ce_lambda; a.factor = factor; a.scale = scale;
     a.g_rgb = grad_rgb_map; a.g_classes = grad_classes; a.partials = (float *)workspace; a.out = loss_out;
     uint32_t nb = nsr_div_up(N, CP_BLOCK);
-    if (nb > 2048u) nb = 2048u;
+    if (nb > CP_MAX_BLOCKS) nb = CP_MAX_BLOCKS;
     a.nblocks = nb;
     hipLaunchKernelGGL(k_recon_loss, dim3(nb), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);

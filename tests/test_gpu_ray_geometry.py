@@ -116,6 +116,26 @@ def test_backward_on_edge_rays(dev, is_ndc, which):
     assert np.array_equal(g_w[owned], gs[owned]) and (g_w[~owned] == 0).all()
 
 
+@pytest.mark.parametrize('is_ndc', [False, True])
+def test_totals_have_the_bits_of_the_composite(dev, is_ndc):
+    """totals[:, 0] and totals[:, 1] (sum w, sum w t) are weights_sum and depth of nsr_composite_rays_train_forward on the same
+    samples, to the bit: the claim above GeomArgs in composite.hip.  Rays with a range that are neither dropped nor empty."""
+    from nerfstyle_amd import _lib as L
+    c = G.geometry_case(is_ndc)
+    _, _, totals_t = _forward(c, dev)
+    sig, deltas, rays, _, _ = _inputs(c, dev)
+    N, M, C = c['N'], c['M'], 3
+    rgbs = torch.rand(M, C, device=dev)
+    ws_t, depth_t, image_t = torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(N, C, device=dev)
+    L.check(L.lib().nsr_composite_rays_train_forward(L.p(sig), L.p(rgbs), L.p(deltas), L.p(rays), M, N, C, c['T_thresh'], int(is_ndc),
+                                                     L.p(ws_t), L.p(depth_t), L.p(image_t), L.stream()), 'composite_rays_train_forward')
+    totals, ws, depth = totals_t.cpu().numpy(), ws_t.cpu().numpy(), depth_t.cpu().numpy()
+    v = c['valid']
+    assert v.sum() >= 50
+    assert np.array_equal(totals[v, 0], ws[v])
+    assert np.array_equal(totals[v, 1], depth[v])
+
+
 def test_two_runs_give_the_same_bits(dev):
     from nerfstyle_amd import raymarching as R
     c = G.geometry_case(False)
