@@ -158,6 +158,20 @@ int nsr_ray_geometry_backward(const float *grad_depth, const float *grad_distort
                               const float *totals, uint32_t M, uint32_t N, float T_thresh, int is_ndc, float *grad_sigmas,
                               nsr_stream_t stream);
 
+/* Position gradients of the marched samples back to their rays (no reference counterpart), for xyz_i = o + t_i d with the
+ * t_i, the samples and their count held constant:  grad_rays_o [N,3] = sum_i g_i,  grad_rays_d [N,3] = sum_i t_i g_i over the
+ * ray's samples, g = grad_xyzs [M,3].  The walk, the running parameter (sum scan of deltas[:, 1] carried across trips) and the
+ * "offset + steps < M" drop test are nsr_composite_rays_train_forward's; pass the march's M.
+ * nears [N] or NULL.  The march emits deltas[:, 1] = t_next - last_t with last_t starting at the ray's first parameter
+ * (nears[index] when noises == NULL), so the running sum is the parameter behind the sample, measured from that start: with
+ * nears the sample's own parameter t_i = nears[index] + sum_{j<=i} deltas[j, 1] - deltas[i, 0] is used -- where the march put
+ * xyz_i; with NULL the running sum itself.  Rows are indexed by rays[:, 0]; dropped rays and rays without samples get zeros.
+ * deltas 8-byte aligned.  No atomics, no host read, capture-safe; two calls give the same bits.
+ * is_ndc != 0 -> NSR_ERR_UNSUPPORTED (an NDC sample is not o + t d of the rays the march was given). */
+int nsr_rays_position_backward(const float *grad_xyzs, const float *deltas, const int32_t *rays, const float *nears,
+                               uint32_t M, uint32_t N, int is_ndc, float *grad_rays_o, float *grad_rays_d,
+                               nsr_stream_t stream);
+
 /* Reconstruction loss of Trainer.calc_loss (trainers/base.py:251-304), value AND gradient in one pass:
  *   loss = mean((rgb_map - target_rgb[pix])^2) + ce_lambda * mean(logsumexp(classes) - classes[target_cls[pix]])
  * (nn.MSELoss + 0.001 * nn.CrossEntropyLoss on the class logits; the reference builds it from ~25 torch kernels and as
@@ -344,6 +358,24 @@ int nsr_field_backward(const nsr_field_desc *desc, const void *tables, const flo
  * (full-frame) batches; results equal the perm == NULL call up to fp32 summation order.
  * workspace: nsr_field_backward_workspace_bytes(M, with_perm) bytes, 16-byte aligned (0 / NULL without perm). */
 uint64_t nsr_field_backward_workspace_bytes(uint32_t M, int with_perm);
+/* Contract of the workspace after nsr_field_backward / _dirs with perm != NULL: its first M * 256 bytes are
+ * enc_grad [M][16] float4, sample-major: entry [m][l] = d loss / d (density feature 0, density feature 1, colour feature 0,
+ * colour feature 1) of level l of the sample in slot m (its own slot, whatever perm's order), for every slot below the count.
+ * Slots at or past *m_dev are not written (stale bytes).  The colour-only kernel (perm, saved feats, train_density_table = 0,
+ * grad_mlp = NULL: the stylisation stage) writes ZEROS in the density half: the buffer is then not the input of a full
+ * position gradient. */
+
+/* d loss / d xyz of every sample from that buffer (csrc/field_xgrad.hip; no reference counterpart): enc_grad contracted with
+ * the spatial partials of the trilinear interpolation of both encoders (the arithmetic of nsr_grid_encode_input_backward per
+ * level, levels summed in ascending order, fp32) times the derivative of BBox.normalize and the encoder-input map,
+ * 1 / (2 * bbox_size[k]).  tables: the interleaved gather tables, f16 or f32 (desc->table_dtype); xyzs [M,3]; perm optional
+ * (the samples are then walked in its order; results per sample are bit-identical with and without it).
+ * grad_xyzs [M,3] f32 is WRITTEN for every slot: a sample whose position is NaN or encodes outside [0,1], and every slot at
+ * or past *m_dev, gets zeros -- the kernel tests that itself and never reads enc_grad there.  enc_grad 16-byte aligned.
+ * No atomics, no host read, capture-safe; two calls give the same bits.  L != 16 -> NSR_ERR_UNSUPPORTED. */
+int nsr_field_position_gradient(const nsr_field_desc *desc, const void *tables, const float *xyzs, uint32_t M,
+                                const int32_t *m_dev, const void *enc_grad, const uint32_t *perm, float *grad_xyzs,
+                                nsr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * View-dependent colour (networks/style_nerf.py with use_dir = True): color2's input is cat(color1 output [16], degree-4
@@ -538,6 +570,17 @@ int nsr_occ_update(float *density_grid, const float *sigmas, const int32_t *indi
 int nsr_generate_rays(const float *pose, uint32_t w, uint32_t h, float fx, float fy, float cx,
                       float cy, int camera_flip, const int32_t *pix, uint32_t N, float *rays_o,
                       float *rays_d, nsr_stream_t stream);
+
+/* Backward of nsr_generate_rays with respect to the pose (same leading arguments): grad_pose [3,4] f32 row-major is WRITTEN,
+ * grad_pose[:, 3] = sum_n grad_rays_o[n] and, with c_n the pixel's camera-frame direction after the flip, v_n = R c_n and
+ * d_n = v_n / |v_n|:  grad_pose[:, :3] = sum_n ((I - d_n d_n^T) grad_rays_d[n] / |v_n|) c_n^T.
+ * Terms and sums are formed in fp64 and rounded once; block tree + a fixed-order final pass (no atomics, no counter, nothing
+ * of the workspace is read that this call did not write): two calls give the same bits.  Capture-safe.
+ * workspace: nsr_generate_rays_backward_workspace_bytes(N) bytes, 8-byte aligned. */
+uint64_t nsr_generate_rays_backward_workspace_bytes(uint32_t N);
+int nsr_generate_rays_backward(const float *pose, uint32_t w, uint32_t h, float fx, float fy, float cx, float cy,
+                               int camera_flip, const int32_t *pix, uint32_t N, const float *grad_rays_o,
+                               const float *grad_rays_d, void *workspace, float *grad_pose, nsr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 // Training composite (raymarching.cu:806-997) with the render_train epilogue (renderer.py:225-233), the per-ray geometry terms
 // (differentiable depth, mip-NeRF 360 distortion) and the reconstruction loss (trainers/base.py:251-304) for gfx950.
 //
-// In the four ray kernels (k_comp_fwd, k_comp_bwd, k_geom_fwd, k_geom_bwd) a WAVE owns a ray and a LANE owns a sample:
+// In the ray kernels (k_comp_fwd, k_comp_bwd, k_geom_fwd, k_geom_bwd, and k_rays_pos_bwd, which sums the samples' position
+// gradients back to their ray on the same walk) a WAVE owns a ray and a LANE owns a sample:
 //   * 64 consecutive samples of the ray per trip: sigma / delta / colour rows are whole contiguous pieces of the sample
 //     buffers (16-byte loads for C = 4 or 8);
 //   * the recurrences are wave scans on the DPP network (row_shr 1/2/4/8, row_bcast 15/31): transmittance = exclusive
@@ -388,6 +389,54 @@ k_geom_bwd(GeomArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// position gradients of the samples back to their ray: xyz_i = o + t_i d  ->  d/d o = sum_i g_i, d/d d = sum_i t_i g_i
+// ---------------------------------------------------------------------------------------------------------------------
+// The ray walk, the "offset + steps < M" drop test and the running parameter (sum scan of deltas[:, 1], carried across trips)
+// are k_comp_fwd's.  The march emits deltas[:, 1] = t_next - last_t with last_t starting at the ray's first parameter, so that
+// running sum is the parameter BEHIND sample i measured from the start: with nears given, the sample's own parameter
+// t_i = near + sum_{j <= i} deltas[j, 1] - deltas[i, 0] is used (where the march put xyz_i); without, the running sum itself.
+// t_i, the samples of a ray and their count are constants of differentiation.  Dropped and empty rays get zeros.
+struct PosArgs {
+    const float *g_xyzs, *deltas, *nears;
+    const int32_t *rays;
+    uint32_t M, N;
+    float *g_o, *g_d;                      // [N,3] each
+};
+
+__global__ void __launch_bounds__(CP_BLOCK)
+k_rays_pos_bwd(PosArgs a) {
+#pragma clang fp contract(off)                  // see k_comp_fwd
+    const uint32_t lane = threadIdx.x & 63u;
+    for (CpWalk r(a.rays, a.N); r.n < a.N; r.n += r.nwaves) {
+        r.header();
+        const uint32_t index = r.index, offset = r.offset, steps = r.steps;
+        float t = 0.0f, so[3] = {0.0f, 0.0f, 0.0f}, sd[3] = {0.0f, 0.0f, 0.0f};
+        if (steps != 0 && offset + steps < a.M) {
+            const float t0 = a.nears ? a.nears[index] : 0.0f;
+            for (uint32_t base = 0; base < steps; base += 64) {
+                const uint32_t i = base + lane;
+                const bool in = i < steps;
+                const size_t p = (size_t)offset + min(i, steps - 1u);
+                const float2 dd = *reinterpret_cast<const float2 *>(a.deltas + p * 4);
+                const float tc = t + cp_scan_add(in ? dd.y : 0.0f);        // k_comp_fwd's t
+                const float ti = a.nears ? t0 + (tc - dd.x) : tc;
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const float g = in ? a.g_xyzs[p * 3 + k] : 0.0f;
+                    so[k] += cp_sum(g);
+                    sd[k] += cp_sum(ti * g);
+                }
+                t = cp_lane(tc, 63);
+            }
+        }
+        // lanes 0..2: d/d origin, lanes 3..5: d/d direction
+        const float mine = lane == 0u ? so[0] : lane == 1u ? so[1] : lane == 2u ? so[2] : lane == 3u ? sd[0] : lane == 4u ? sd[1] : sd[2];
+        if (lane < 3u) a.g_o[(size_t)index * 3 + lane] = mine;
+        else if (lane < 6u) a.g_d[(size_t)index * 3 + (lane - 3u)] = mine;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // reconstruction loss: value and gradient in one pass
 // ---------------------------------------------------------------------------------------------------------------------
 struct LossArgs {
@@ -580,6 +629,18 @@ int nsr_ray_geometry_backward(const float *grad_depth, const float *grad_distort
     if (const int e = cp_geom_args(a, sigmas, deltas, rays, nears, fars, M, N, T_thresh, is_ndc)) return e;
     a.totals = const_cast<float *>(totals); a.g_depth = grad_depth; a.g_dist = grad_distortion; a.g_sigmas = grad_sigmas;
     hipLaunchKernelGGL(k_geom_bwd, dim3(cp_grid(N)), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
+    return nsr_launch_status();
+}
+
+int nsr_rays_position_backward(const float *grad_xyzs, const float *deltas, const int32_t *rays, const float *nears, uint32_t M,
+                                uint32_t N, int is_ndc, float *grad_rays_o, float *grad_rays_d, nsr_stream_t stream) {
+    if (is_ndc) return NSR_ERR_UNSUPPORTED;     // an NDC sample is not o + t d of the rays the march was given
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(grad_xyzs); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(grad_rays_o); NSR_CHECK_PTR(grad_rays_d);
+    if (((uintptr_t)deltas & 7u) != 0) return NSR_ERR_INVALID_ARG;
+    PosArgs a;
+    a.g_xyzs = grad_xyzs; a.deltas = deltas; a.nears = nears; a.rays = rays; a.M = M; a.N = N; a.g_o = grad_rays_o; a.g_d = grad_rays_d;
+    hipLaunchKernelGGL(k_rays_pos_bwd, dim3(cp_grid(N)), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
     return nsr_launch_status();
 }
 

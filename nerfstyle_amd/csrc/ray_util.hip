@@ -95,6 +95,85 @@ __global__ void k_generate_rays(const float *__restrict__ pose, uint32_t w, uint
     }
 }
 
+// Backward of k_generate_rays with respect to the pose: grad_pose[:, 3] = sum_n grad_o[n]; with c_n the pixel's camera-frame
+// direction (after the flip), v_n = R c_n, d_n = v_n / |v_n|:  grad_R = sum_n ((I - d_n d_n^T) grad_d[n] / |v_n|) c_n^T.
+// Twelve sums over the rays: every ray's term and the sums are formed in fp64 (a few dozen operations per ray against two
+// 12-byte loads; the per-entry error is then the final rounding to fp32), block tree + a fixed-order one-block final pass over
+// the block partials, as k_recon_loss: no atomics, no counter, every partial the final pass reads was written by this call.
+#define RU_BLOCK 256
+#define RU_MAX_BLOCKS 2048u
+
+// fixed-order block tree over twelve values: threads 0..11 leave with the block's sum k in v[0]
+__device__ __forceinline__ void ru_block_sum12(double (&v)[12]) {
+    __shared__ double red[12][RU_BLOCK / 64];
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) v[k] += __shfl_xor(v[k], off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) red[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        double s = 0.0;
+        for (int w = 0; w < RU_BLOCK / 64; w++) s += red[threadIdx.x][w];
+        v[0] = s;
+    }
+}
+
+__global__ void __launch_bounds__(RU_BLOCK)
+k_generate_rays_bwd(const float *__restrict__ pose, uint32_t w, float fx, float fy, float cx, float cy, int camera_flip,
+                    const int32_t *__restrict__ pix, uint32_t N, const float *__restrict__ g_o, const float *__restrict__ g_d,
+                    double *__restrict__ partials) {
+    double R[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) R[r][c] = (double)pose[r * 4 + c];
+    }
+    const double f0 = (camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (camera_flip >> 0) & 1 ? -1.0 : 1.0;
+    double acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) acc[k] = 0.0;
+    for (uint32_t n = blockIdx.x * RU_BLOCK + threadIdx.x; n < N; n += gridDim.x * RU_BLOCK) {
+        const uint32_t p = pix ? (uint32_t)pix[n] : n;
+        const uint32_t py = p / w, px = p - py * w;
+        const double c[3] = {(((double)px + 0.5 - (double)cx) / (double)fx) * f0, (((double)py + 0.5 - (double)cy) / (double)fy) * f1, f2};
+        double v[3], gd[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            v[r] = R[r][0] * c[0] + R[r][1] * c[1] + R[r][2] * c[2];
+            gd[r] = (double)g_d[(size_t)n * 3 + r];
+        }
+        const double inv = 1.0 / sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        const double d[3] = {v[0] * inv, v[1] * inv, v[2] * inv};
+        const double dg = d[0] * gd[0] + d[1] * gd[1] + d[2] * gd[2];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const double h = (gd[r] - d[r] * dg) * inv;
+#pragma unroll
+            for (int k = 0; k < 3; k++) acc[r * 4 + k] += h * c[k];
+            acc[r * 4 + 3] += (double)g_o[(size_t)n * 3 + r];
+        }
+    }
+    ru_block_sum12(acc);
+    if (threadIdx.x < 12) partials[(size_t)blockIdx.x * 12 + threadIdx.x] = acc[0];
+}
+
+__global__ void __launch_bounds__(RU_BLOCK)
+k_generate_rays_bwd_final(const double *__restrict__ partials, uint32_t nblocks, float *__restrict__ grad_pose) {
+    double acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) acc[k] = 0.0;
+    for (uint32_t b = threadIdx.x; b < nblocks; b += RU_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) acc[k] += partials[(size_t)b * 12 + k];
+    }
+    ru_block_sum12(acc);
+    if (threadIdx.x < 12) grad_pose[threadIdx.x] = (float)acc[0];
+}
+
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
@@ -152,6 +231,26 @@ int nsr_generate_rays(const float *pose, uint32_t w, uint32_t h, float fx, float
     if (pix == nullptr && (uint64_t)N != (uint64_t)w * h) return NSR_ERR_INVALID_ARG;
     hipLaunchKernelGGL(k_generate_rays, dim3(nsr_grid_1d(N, 256)), dim3(256), 0, (hipStream_t)stream, pose, w, h, fx, fy, cx, cy,
                        camera_flip, pix, N, rays_o, rays_d);
+    return nsr_launch_status();
+}
+
+uint64_t nsr_generate_rays_backward_workspace_bytes(uint32_t N) {
+    (void)N;
+    return (uint64_t)RU_MAX_BLOCKS * 12 * sizeof(double);
+}
+
+int nsr_generate_rays_backward(const float *pose, uint32_t w, uint32_t h, float fx, float fy, float cx, float cy, int camera_flip,
+                               const int32_t *pix, uint32_t N, const float *grad_rays_o, const float *grad_rays_d, void *workspace,
+                               float *grad_pose, nsr_stream_t stream) {
+    if (N == 0) return NSR_OK;
+    NSR_CHECK_PTR(pose); NSR_CHECK_PTR(grad_rays_o); NSR_CHECK_PTR(grad_rays_d); NSR_CHECK_PTR(workspace); NSR_CHECK_PTR(grad_pose);
+    if (w == 0 || h == 0 || ((uintptr_t)workspace & 7u) != 0) return NSR_ERR_INVALID_ARG;
+    if (pix == nullptr && (uint64_t)N != (uint64_t)w * h) return NSR_ERR_INVALID_ARG;
+    uint32_t nb = nsr_div_up(N, RU_BLOCK);
+    if (nb > RU_MAX_BLOCKS) nb = RU_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_generate_rays_bwd, dim3(nb), dim3(RU_BLOCK), 0, (hipStream_t)stream, pose, w, fx, fy, cx, cy, camera_flip, pix,
+                       N, grad_rays_o, grad_rays_d, (double *)workspace);
+    hipLaunchKernelGGL(k_generate_rays_bwd_final, dim3(1), dim3(RU_BLOCK), 0, (hipStream_t)stream, (const double *)workspace, nb, grad_pose);
     return nsr_launch_status();
 }
 

@@ -265,6 +265,41 @@ def ray_geometry(sigmas, deltas, rays, nears, fars, T_thresh=1e-4, is_ndc=False,
     return _ray_geometry.apply(sigmas, deltas, rays, nears, fars, T_thresh, is_ndc, zero_unowned)
 
 
+def rays_position_backward(grad_xyzs, deltas, rays, M, nears=None, is_ndc=False):
+    """nsr_rays_position_backward: the samples' position gradients [M,3] summed back to their rays for xyz_i = o + t_i d
+    -> (grad_rays_o [N,3], grad_rays_d [N,3]).  M: the capacity the march used for its drop test.  nears [N]: the rays' first
+    parameters, so that t_i is the sample's own parameter (without, the composite's running sum of deltas[:, 1])."""
+    grad_xyzs = grad_xyzs.to(torch.float32).contiguous()
+    N, dev = rays.shape[0], grad_xyzs.device
+    g_o = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    g_d = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    with profiling.timed('rays_position_bwd'):
+        L.check(L.lib().nsr_rays_position_backward(L.p(grad_xyzs), L.p(deltas), L.p(rays), L.p(nears), int(M), N, int(bool(is_ndc)),
+                                                   L.p(g_o), L.p(g_d), L.stream()), 'rays_position_backward')
+    return g_o, g_d
+
+
+class _sample_positions(Function):
+    """The marched positions as a function of their rays (xyz_i = o + t_i d, the t_i and the set of samples constant): returns
+    the marched buffer itself, the backward is rays_position_backward."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, xyzs, deltas, rays, nears, M):
+        ctx.save_for_backward(deltas, rays, nears)
+        ctx.M = M
+        return xyzs
+
+    @staticmethod
+    def backward(ctx, grad_xyzs):
+        deltas, rays, nears = ctx.saved_tensors
+        g_o, g_d = rays_position_backward(grad_xyzs, deltas, rays, ctx.M, nears)
+        return g_o, g_d, None, None, None, None, None
+
+
+def sample_positions(rays_o, rays_d, xyzs, deltas, rays, nears, M):
+    return _sample_positions.apply(rays_o, rays_d, xyzs, deltas, rays, nears, M)
+
+
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, z_hats, bound, density_bitfield,
                C, H, near, far, align=-1, perturb=False, dt_gamma=0, max_steps=1024, is_ndc=False):
     """raymarching.py:357-424"""

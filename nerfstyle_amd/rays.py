@@ -35,13 +35,47 @@ def pixel_ids(intr: Intrinsics, patch: Optional[Box2D] = None, precrop: float = 
     return ids, w, h, dx, dy
 
 
+def _launch_generate_rays(pose, W, H, fx, fy, cx, cy, camera_flip, ids):
+    N = ids.shape[0]
+    rays_o = torch.empty(N, 3, dtype=torch.float32, device=pose.device)
+    rays_d = torch.empty(N, 3, dtype=torch.float32, device=pose.device)
+    L.check(L.lib().nsr_generate_rays(L.p(pose), W, H, fx, fy, cx, cy, camera_flip, L.p(ids), N, L.p(rays_o), L.p(rays_d), L.stream()),
+            'generate_rays')
+    return rays_o, rays_d
+
+
+class _generate_rays_fn(torch.autograd.Function):
+    """nsr_generate_rays with a gradient for the pose (nsr_generate_rays_backward): pose [3,4] or [4,4] -> (rays_o, rays_d)."""
+
+    @staticmethod
+    def forward(ctx, pose, W, H, fx, fy, cx, cy, camera_flip, ids):
+        flat = pose.detach().contiguous()
+        ctx.save_for_backward(flat, ids)
+        ctx.args = (W, H, fx, fy, cx, cy, camera_flip)
+        return _launch_generate_rays(flat, W, H, fx, fy, cx, cy, camera_flip, ids)
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        pose, ids = ctx.saved_tensors
+        N, dev = ids.shape[0], pose.device
+        g_o, g_d = g_o.to(torch.float32).contiguous(), g_d.to(torch.float32).contiguous()
+        ws = torch.empty(int(L.lib().nsr_generate_rays_backward_workspace_bytes(N)) // 8, dtype=torch.float64, device=dev)
+        grad = torch.zeros_like(pose)            # a [4,4] pose: its last row never reaches the rays
+        L.check(L.lib().nsr_generate_rays_backward(L.p(pose), *ctx.args, L.p(ids), N, L.p(g_o), L.p(g_d), L.p(ws), L.p(grad),
+                                                   L.stream()), 'generate_rays_backward')
+        return (grad,) + (None,) * 8
+
+
 def generate_rays(pose, intr: Intrinsics, img=None, patch: Optional[Box2D] = None, precrop: float = 1.,
-                  bsize: Optional[int] = None, camera_flip: int = 0, pix_subset=None, device=None):
+                  bsize: Optional[int] = None, camera_flip: int = 0, pix_subset=None, device=None, pose_grad: bool = False):
     """Same arguments and returns as the reference (RayBatch, target).  bsize: that many pixels
     drawn without replacement with np.random.choice, exactly like nerf_lib.py:134 (pass
     `pix_subset`, positions into the cropped pixel list, to supply your own / device-side draw).
-    img: [C, H, W] tensor -> target [K, C]."""
+    img: [C, H, W] tensor -> target [K, C].
+    pose_grad (Renderer.pose_gradients): the rays stay attached to a pose tensor that requires grad; by default the pose
+    is a constant, as in the reference."""
     device = device or (pose.device if torch.is_tensor(pose) else None)
+    pose_in = pose
     pose = torch.as_tensor(pose, dtype=torch.float32, device=device).contiguous()
     device = pose.device
     W, H = intr.size()
@@ -55,12 +89,11 @@ def generate_rays(pose, intr: Intrinsics, img=None, patch: Optional[Box2D] = Non
             pix_subset = torch.from_numpy(np.random.choice(np.arange(w * h), bsize, replace=False)).to(device)
         if pix_subset is not None:
             ids = ids[pix_subset.long()].contiguous()
-    N = ids.shape[0]
-    rays_o = torch.empty(N, 3, dtype=torch.float32, device=device)
-    rays_d = torch.empty(N, 3, dtype=torch.float32, device=device)
-    L.check(L.lib().nsr_generate_rays(L.p(pose), W, H, float(intr.fx), float(intr.fy), float(intr.cx), float(intr.cy),
-                                      int(camera_flip), L.p(ids), N, L.p(rays_o), L.p(rays_d), L.stream()),
-            'generate_rays')
+    args = (W, H, float(intr.fx), float(intr.fy), float(intr.cx), float(intr.cy), int(camera_flip), ids)
+    if pose_grad and torch.is_tensor(pose_in) and pose_in.requires_grad and torch.is_grad_enabled():
+        rays_o, rays_d = _generate_rays_fn.apply(pose_in.to(device=device, dtype=torch.float32), *args)
+    else:
+        rays_o, rays_d = _launch_generate_rays(pose, *args)
     target = None
     if img is not None:
         if H != img.shape[-2] or W != img.shape[-1]:

@@ -58,7 +58,14 @@ class Renderer(torch.nn.Module):
         # the mip-NeRF 360 distortion, for depth supervision and a floater regulariser.  Opt-in: shade_train fills a `geometry` dict,
         # render(training=True) / finish_train add 'depth' and 'distortion' to their output; render_test never does.
         self.geometry_terms = False
-        self.reference_inference_loop = False      # render_test through render_test_loop (the reference's iteration structure)
+        # Camera pose gradients through the training render (pose refinement, nerfstyle_amd/pose.py).  Opt-in: with the switch on
+        # AND a pose tensor that requires grad, the rays stay attached to the pose (rays.generate_rays), the marched positions to
+        # their rays (xyz_i = o + t_i d; the t_i, the set of samples, nears / fars and the depth normalisation are constants, as in
+        # instant-ngp) and the field returns d loss / d position.  The call then always takes the spatially ordered backward,
+        # whose encoder-gradient buffer the position gradient is built from.  Off, or with a pose that does not require grad,
+        # none of that is in the graph.
+        self.pose_gradients = False
+        self.reference_inference_loop = False     # render_test through render_test_loop (the reference's iteration structure)
         self.last_test_overflow = False            # the last bounded-capacity render_test overflowed and fell back to the loop
         self._infer_stats = None
         self._last_counter = self._last_capacity = None    # _set_last: what last_call_overflowed() answers from
@@ -218,6 +225,7 @@ class Renderer(torch.nn.Module):
         also drives one by one: march (sync-free), optional spatial order of the samples, shade (field + composite).
         With `fused_nograd_train` set and autograd off the call is render_train_fused instead (non-NDC, all model channels, and no
         `geometry_terms`: the streaming kernel has no such outputs).  geometry=dict: see shade_train."""
+        pose_grad = self._pose_grad_wanted(rays.origins, rays.dirs)
         if self.fused_nograd_train and self.model.use_dir:
             raise NotImplementedError('fused_nograd_train: the streaming kernel has no direction input (view_dependent model)')
         if (self.fused_nograd_train and not torch.is_grad_enabled() and not self.cfg.use_ndc and not self.geometry_terms
@@ -227,9 +235,24 @@ class Renderer(torch.nn.Module):
             self.update_state()
         mt = self.march_train(rays)
         perm = None
-        if torch.is_grad_enabled() and self._use_spatial_order(mt['N'], bool(kwargs.get('dense', False))):
+        if torch.is_grad_enabled() and (pose_grad or self._use_spatial_order(mt['N'], bool(kwargs.get('dense', False)))):
             perm = self.model.sample_order(mt['xyzs'], mt['counter'])
         return self.shade_train(mt, perm, geometry=kwargs.get('geometry'))
+
+    def _pose_grad_wanted(self, *tensors) -> bool:
+        """True when this training call differentiates with respect to the camera: the switch is on, autograd is recording and one
+        of `tensors` (the pose, or the rays made from it) requires grad.  Raises NotImplementedError, naming the reason, for the
+        configurations that cannot serve it -- before anything is launched."""
+        if not (self.pose_gradients and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)):
+            return False
+        why = self.model.position_gradient_refusal()
+        if why is None and self.cfg.use_ndc:
+            why = 'use_ndc: an NDC sample is not o + t d of the rays the march is given'
+        if why is None and (self.fused_nograd_train or self.fused_inference):
+            why = 'the streaming fused_* paths keep no samples to differentiate through; switch fused_nograd_train / fused_inference off'
+        if why is not None:
+            raise NotImplementedError('pose_gradients: ' + why)
+        return True
 
     @contextmanager
     def occupancy_frozen(self):
@@ -296,8 +319,15 @@ class Renderer(torch.nn.Module):
 
     def march_train(self, rays: RayBatch, into: Optional[dict] = None) -> dict:
         """near/far + occupancy-grid march + compaction: capacity-sized sample buffers, device-side counts.
-        into: the dict a previous call returned -- its tensors are written in place (static buffers of a captured step)."""
-        return self._march(rays, into)
+        into: the dict a previous call returned -- its tensors are written in place (static buffers of a captured step).
+        With `pose_gradients` and rays that require grad, 'xyzs' is the marched buffer attached to (origins, dirs)."""
+        if not self._pose_grad_wanted(rays.origins, rays.dirs):
+            return self._march(rays, into)
+        if into is not None:
+            raise NotImplementedError('pose_gradients: a march into static buffers (into=) keeps no graph from the samples to the rays')
+        mt = self._march(rays)
+        mt['xyzs'] = raymarching.sample_positions(rays.origins, rays.dirs, mt['xyzs'], mt['deltas'], mt['rays_info'], mt['nears'], mt['M'])
+        return mt
 
     def shade_train(self, mt: dict, perm=None, geometry: Optional[dict] = None):
         """fused field on the marched samples + train composite with the epilogue of renderer.py:225-233 folded in
@@ -305,8 +335,9 @@ class Renderer(torch.nn.Module):
         geometry: with `geometry_terms` set, a dict that receives 'depth' [N] (the depth returned here, but differentiable) and
         'distortion' [N] from a third node on the same sigmas (raymarching.ray_geometry); autograd adds its d/d sigmas to the
         composite's.  Left alone with the switch off."""
+        extra = {'pos_grad': True} if self._pose_grad_wanted(mt['xyzs']) else {}
         sigmas, rgbs = self.model.field(mt['xyzs'], sigma_only=False, m_dev=mt['counter'], density_scale=self.cfg.density_scale,
-                                        perm=perm, dirs=mt.get('dirs'))
+                                        perm=perm, dirs=mt.get('dirs'), **extra)
         image, depth, classes, _ = _render_train(sigmas, rgbs, mt['deltas'], mt['rays_info'], mt['nears'], mt['fars'],
                                                  self.cfg.t_thresh)
         if geometry is not None and self.geometry_terms:
@@ -507,13 +538,15 @@ class Renderer(torch.nn.Module):
         PARAMETERS (the march reads the bitfield only), so a data-parallel step may issue it for step i+1 while the gradient
         all-reduce of step i is in flight and the optimiser has not stepped yet -- as long as occupancy_update_due() is
         False.  finish_train(ctx) does the rest."""
-        rays, _ = generate_rays(pose, self.intr, None, camera_flip=self.cfg.flip_camera, pix_subset=pix_subset, device=self.device)
+        pose_grad = self._pose_grad_wanted(pose)
+        rays, _ = generate_rays(pose, self.intr, None, camera_flip=self.cfg.flip_camera, pix_subset=pix_subset, device=self.device,
+                                pose_grad=pose_grad)
         if self.occupancy_update_due():
             self.update_state()
         # into: the ctx a previous call returned; every tensor of it is rewritten in place (graph.GraphedRenderStep(prefetch=True))
         mt = self.march_train(rays, into=into['mt'] if into is not None else None)
         perm = None
-        if torch.is_grad_enabled() and self._use_spatial_order(mt['N'], dense):
+        if torch.is_grad_enabled() and (pose_grad or self._use_spatial_order(mt['N'], dense)):
             perm = self.model.sample_order(mt['xyzs'], mt['counter'], out=into['perm'] if into is not None else None)
         if into is not None:
             assert (perm is None) == (into['perm'] is None)
@@ -561,7 +594,7 @@ class Renderer(torch.nn.Module):
         precrop_frac = self.precrop_frac if self._use_precrop else 1.
         rays, output['target'] = generate_rays(pose, self.intr, image, patch=patch, precrop=precrop_frac, bsize=num_rays,
                                                camera_flip=self.cfg.flip_camera, pix_subset=pix_subset,
-                                               device=self.device)
+                                               device=self.device, pose_grad=training and self._pose_grad_wanted(pose))
         render_fn = self.render_train if training else self.render_test
         # a full frame, a patch or a centre crop is a dense pixel set: neighbouring rays share hash-table rows
         if dense is None:

@@ -86,7 +86,9 @@ class _field(Function):
     is arena.grad) and returns None for it."""
 
     @staticmethod
-    def forward(ctx, xyzs, arena, model, sigma_only, m_dev, density_scale, want_feats=False, perm=None, dirs=None):
+    def forward(ctx, xyzs, arena, model, sigma_only, m_dev, density_scale, want_feats=False, perm=None, dirs=None, pos_grad=False):
+        # pos_grad (Renderer.pose_gradients): the backward also returns d loss / d xyzs; off, positions are constants as ever
+        ctx.pos_grad = bool(pos_grad)
         xyzs = xyzs.detach().to(torch.float32).contiguous()
         if dirs is not None:
             dirs = dirs.detach().to(torch.float32).reshape(-1, 3).contiguous()
@@ -157,6 +159,10 @@ class _field(Function):
                     L.p(grad_sigmas), L.p(grad_rgbs), L.p(ga), (ga.data_ptr() + model.table_elems * 4) if model.train_mlps else None,
                     int(model.train_density_table), int(model.train_color_table), L.p(feats), L.p(perm), L.p(wsp))
             st = call(perm, ws)
+            want_pos = ctx.pos_grad and ctx.needs_input_grad[0]
+            if want_pos and (perm is None or st == -2 or dirs is not None):
+                raise NotImplementedError('position gradients need the encoder-gradient buffer of the spatially ordered backward '
+                                          '(a perm, a grid the spatial scatter supports, no view-dependent colour)')
             if st == -2 and perm is not None:
                 feats = None             # saved in the permutation's order: useless to a kernel that walks the buffers
                 # NSR_ERR_UNSUPPORTED: a grid finer than the spatial scatter's LDS lattices hold (finest resolution above
@@ -164,7 +170,15 @@ class _field(Function):
                 model._spatial_scatter_unsupported = True
                 st = call(None, None)
             L.check(st, 'field_backward')
-        return None, None, None, None, None, None, None, None, None
+        grad_xyzs = None
+        if want_pos:
+            # the workspace just filled IS the input: d loss / d (encoder output) of every sample, contracted with the
+            # interpolation's spatial partials (nsr_field_position_gradient)
+            grad_xyzs = torch.empty(M, 3, dtype=torch.float32, device=dev)
+            with profiling.timed('field_pos_grad'):
+                L.check(L.lib().nsr_field_position_gradient(ctypes.byref(desc), L.p(tables), L.p(xyzs), M, L.p(ctx.m_dev), L.p(ws),
+                                                            L.p(perm), L.p(grad_xyzs), L.stream()), 'field_position_gradient')
+        return grad_xyzs, None, None, None, None, None, None, None, None, None
 
 
 class _EncoderView(nn.Module):
@@ -434,13 +448,33 @@ class StyleTCNerf(nn.Module):
         return list(self.views_of(self.arena.detach()).items())
 
     # ---- forward -------------------------------------------------------------------------------
-    def field(self, pts, sigma_only=False, m_dev=None, density_scale=1.0, perm=None, dirs=None):
+    def position_gradient_refusal(self):
+        """Why this model cannot give d loss / d position through `field(..., pos_grad=True)` (None: it can).  The gradient is
+        built from the encoder-gradient buffer of the spatially ordered backward, which must hold both encoders' halves."""
+        if self.use_dir:
+            return 'view_dependent=True: no gradient with respect to the samples\' directions exists'
+        if self._spatial_scatter_unsupported:
+            return 'the spatial table scatter is unsupported for this grid, so its encoder-gradient buffer does not exist'
+        if not self.train_density_table or not self.train_mlps:
+            return ('train_density_table = False or train_mlps = False selects the colour-only backward (the stylisation stage), '
+                    'which leaves the density half of the encoder-gradient buffer zero')
+        return None
+
+    def field(self, pts, sigma_only=False, m_dev=None, density_scale=1.0, perm=None, dirs=None, pos_grad=False):
         """Fast path: flat sigmas [M] (and rgbs [M,3+nc]); m_dev = device int32 sample count; perm = spatial order from
         `sample_order` (int32 [M] device tensor): a training forward then walks the samples in that order (its saved features
         are tile-major in it) and the backward follows -- MLP chain first, then the table gradient with the stand-alone
-        lattice scatter kernel (same result per sample, table gradient up to fp32 summation order; pays on dense batches)."""
+        lattice scatter kernel (same result per sample, table gradient up to fp32 summation order; pays on dense batches).
+        pos_grad=True (needs perm): `pts` that require grad receive d loss / d position from the backward
+        (nsr_field_position_gradient on the encoder gradients the ordered backward has just written); otherwise positions are
+        constants of the loss and the backward returns None for them."""
         want_feats = bool(self.save_features and torch.is_grad_enabled() and self.arena.requires_grad and not sigma_only)
-        return _field.apply(pts, self.arena, self, sigma_only, m_dev, density_scale, want_feats, perm, dirs)
+        if not pos_grad:
+            return _field.apply(pts, self.arena, self, sigma_only, m_dev, density_scale, want_feats, perm, dirs)
+        why = self.position_gradient_refusal() or (None if perm is not None else 'pos_grad needs perm (the spatially ordered backward)')
+        if why is not None:
+            raise NotImplementedError('position gradients: ' + why)
+        return _field.apply(pts, self.arena, self, sigma_only, m_dev, density_scale, want_feats, perm, dirs, True)
 
     @torch.no_grad()
     def density_gradient(self, pts, m_dev=None, density_scale=1.0, normalize=False):
