@@ -409,13 +409,18 @@ int nsr_field_backward_dirs(const nsr_field_desc *desc, const void *tables, cons
                             const uint32_t *perm, void *workspace, const float *dirs, nsr_stream_t stream);
 
 /* Spatial processing order of marched samples (no reference counterpart; see csrc/sample_order.hip): perm [M] u32 =
- * indices of the first min(m_dev[0], M) samples in Morton order of their encoder input (10 bits per axis, stable: ray
- * order inside a 4^3-finest-cell block), followed by the remaining slots in identity order.  sort_prefix <= M caps the
- * number of leading slots that take part in the sort; the kernels bound themselves by min(m_dev[0], sort_prefix) on the
- * device, so M is the normal value (a smaller one is still correct: the slots past it keep identity order).  The sort is
- * the library's own LSD radix sort (3 x 9 bits: the encoder input of a position inside the box is in [0.5, 1], so the top bit
- * of every coordinate is constant; positions outside the box sort with its faces): stream-ordered, no host call, capture-safe,
- * deterministic.
+ * indices of the first n = min(max(m_dev[0], 0), sort_prefix) samples (m_dev == NULL: n = sort_prefix) in Morton order of
+ * their encoder input, stable (ray order inside a 4^3-finest-cell block), followed by the slots n .. M-1 in identity order,
+ * whatever their positions hold.  sort_prefix (a larger value is clamped to M) caps the number of leading slots that take part
+ * in the sort; the kernels bound themselves by n on the device, so M is the normal value (a smaller one is still correct: the
+ * slots past it keep identity order).
+ * Key: per axis u = ((x - bbox_min) / bbox_size + 1) / 2, q = floor(clamp(1024 u, 0, 1023)) with NaN -> 0, of which the low 9
+ * bits count: q9 = max(q - 512, 0), since u of a position inside the box is in [0.5, 1] and the top bit of its 10-bit
+ * coordinate is always set; the key is the 27-bit interleave of the three q9, x in bit 0, y in bit 1, z in bit 2 of every
+ * triple.  Positions outside the box sort with its faces (cell 0 or 511 of that axis, -inf and +inf included), NaN as cell 0.
+ * The sort is the library's own LSD radix sort (3 x 9 bits): stream-ordered, no host call, capture-safe, deterministic; every
+ * counter in the workspace is initialised by the call itself.  Returns before any launch: NSR_OK for M == 0,
+ * NSR_ERR_INVALID_ARG for a null xyzs / perm / workspace / box or a workspace that is not 256-byte aligned.
  * Consumed by nsr_field_forward / nsr_field_backward (spatial walk, table scatter in spatial order).
  * workspace: nsr_sample_order_workspace_bytes(M) bytes, 256-byte aligned.  bbox_min / bbox_size: HOST float[3]. */
 uint64_t nsr_sample_order_workspace_bytes(uint32_t M);
