@@ -43,7 +43,7 @@ k_field_fwd(FieldArgsOf<DIRS> a) {
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
     __syncthreads();
 
-    const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
+    const uint32_t Mc = FIELD_COUNT(a);
     const uint32_t ntiles = (Mc + 15) / 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -65,8 +65,7 @@ k_field_fwd(FieldArgsOf<DIRS> a) {
             u1 = field_unit(a.xyzs[(size_t)m * 3 + 1], a.bmin[1], a.bsize[1]);
             u2 = field_unit(a.xyzs[(size_t)m * 3 + 2], a.bmin[2], a.bsize[2]);
         }
-        // gridencoder.cu:107-132: inputs outside [0,1] encode to zeros
-        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);   // NaN -> zeros too
+        const bool live = valid && field_in_unit_cube(u0, u1, u2);
         s8v xd, xc;
         field_encode<TT, CD, SIGMA_ONLY, true>(lds_lv, tables, u0, u1, u2, live, g, xd, xc, a.fast_levels);
         if (!SIGMA_ONLY && a.feats) {
@@ -158,20 +157,18 @@ template <int CD>
 __device__ __forceinline__ void field_encode_lat(const NsrLevel *lds_lv, const uint2 *__restrict__ tables, const uint4 *anch,
                                                  const uint2 *lat, float u0, float u1, float u2, bool live, int g, s8v &xd, s8v &xc,
                                                  uint32_t fast_levels) {
-    const int lvl[4] = {2 * g, 2 * g + 1, 8 + 2 * g, 9 + 2 * g};
-    const uint32_t call_levels[4] = {0x0055u, 0x00AAu, 0x5500u, 0xAA00u};
     uint2 v[4][8];
     float w[4][8];
     if (live) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const NsrLevel lv = lds_lv[lvl[i]];
-            const bool fast = (fast_levels & call_levels[i]) == call_levels[i];
+            const NsrLevel lv = lds_lv[field_lane_level(g, i)];
+            const bool fast = field_call_is_fast(fast_levels, i);
             uint32_t rows[8];
-            if ((FWD_LAT_LEVELS & call_levels[i]) == call_levels[i]) {
+            if (field_call_is_fast(FWD_LAT_LEVELS, i)) {
                 uint32_t c[3];
                 field_level_cell(lv, u0, u1, u2, c, w[i]);
-                const uint4 an = anch[lvl[i]];
+                const uint4 an = anch[field_lane_level(g, i)];
                 const uint32_t S = lv.pad_ & 0xFu, d0 = c[0] - an.x, d1 = c[1] - an.y, d2 = c[2] - an.z;
                 if (d0 < S - 1u && d1 < S - 1u && d2 < S - 1u) {
                     // an LDS-typed pointer: as generic loads the two branches are merged into one flat load per corner
@@ -215,7 +212,7 @@ k_field_fwd_lat(FieldArgsOf<DIRS> a, FieldLatArgs la) {
     if (lane < FWD_LAT_ANCHORS<DIRS>) anch[lane] = make_uint4(LAT_NONE, LAT_NONE, LAT_NONE, 0u);
     __syncthreads();
 
-    const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
+    const uint32_t Mc = FIELD_COUNT(a);
     const uint32_t ntiles = (Mc + 15) / 16;
     const int s = lane & 15, g = lane >> 4;
     const uint2 *tables = reinterpret_cast<const uint2 *>(a.tables);
@@ -236,7 +233,7 @@ k_field_fwd_lat(FieldArgsOf<DIRS> a, FieldLatArgs la) {
             u1 = field_unit(a.xyzs[(size_t)m * 3 + 1], a.bmin[1], a.bsize[1]);
             u2 = field_unit(a.xyzs[(size_t)m * 3 + 2], a.bmin[2], a.bsize[2]);
         }
-        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);   // NaN -> zeros too
+        const bool live = valid && field_in_unit_cube(u0, u1, u2);
         // the block of the tile's first live sample (k_order_keys' quantisation) anchors the lattices
         const unsigned long long lm = __ballot(live);
         if (lm) {

@@ -136,15 +136,14 @@ __device__ __forceinline__ void field_scatter_seq(SeqState &st, const NsrLevel *
                                                   ScatterQueue &q, float *__restrict__ gt1, float u0, float u1, float u2,
                                                   const float4 (&sg)[4], int lane, bool td, bool tc) {
     const int s = lane & 15, g = lane >> 4;
-    const int lvl[4] = {2 * g, 2 * g + 1, 8 + 2 * g, 9 + 2 * g};
 #pragma unroll
-    for (int i = 0; i < 4; i++) G[lvl[i] * 16 + s] = sg[i];
+    for (int i = 0; i < 4; i++) G[field_lane_level(g, i) * 16 + s] = sg[i];
     __builtin_amdgcn_wave_barrier();
     // this lane's level
     const int l = lane >> 2, py = lane & 1, pz = (lane >> 1) & 1;
     const NsrLevel lv = lds_lv[l];
     const bool hashed = lv.use_hash != 0;
-    const uint32_t mulY = hashed ? 2654435761u : lv.mul[1], mulZ = hashed ? 805459861u : lv.mul[2];
+    const uint32_t mulY = hashed ? 2654435761u : lv.mul[1], mulZ = hashed ? 805459861u : lv.mul[2];     // field_corner_yz's
     const uint32_t off1 = lv.offset + 1u;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 gnext = G[l * 16];
@@ -193,7 +192,7 @@ __device__ __forceinline__ void field_scatter_seq(SeqState &st, const NsrLevel *
         const float wA = ((1 - f0) * wy) * wz, wB = (f0 * wy) * wz;
         st.aA = make_float4(fmaf(wA, gr.x, baseA.x), fmaf(wA, gr.y, baseA.y), fmaf(wA, gr.z, baseA.z), fmaf(wA, gr.w, baseA.w));
         st.aB = make_float4(fmaf(wB, gr.x, baseB.x), fmaf(wB, gr.y, baseB.y), fmaf(wB, gr.z, baseB.z), fmaf(wB, gr.w, baseB.w));
-        // ---- keys of the (possibly unchanged) cell: nsr_grid_row for both x corners ----
+        // ---- keys of the (possibly unchanged) cell: field_corner_yz / field_corner_row<false> (field_common.h) restated for both x corners ----
         if (!same) {
             const uint32_t ty = (c1 + (uint32_t)py) * mulY, tz = (c2 + (uint32_t)pz) * mulZ;
             const uint32_t comb = hashed ? (ty ^ tz) : (ty + tz);
@@ -255,7 +254,7 @@ k_field_bwd_tracker(FieldBwdArgsOf<DIRS> b) {
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
     __syncthreads();
 
-    const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
+    const uint32_t Mc = FIELD_COUNT(a);
     const uint32_t ntiles = (Mc + 15) / 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -346,7 +345,7 @@ k_field_bwd_tracker(FieldBwdArgsOf<DIRS> b) {
         const float u0 = valid ? field_unit(cur.x0, a.bmin[0], a.bsize[0]) : 0.f;
         const float u1 = valid ? field_unit(cur.x1, a.bmin[1], a.bsize[1]) : 0.f;
         const float u2 = valid ? field_unit(cur.x2, a.bmin[2], a.bsize[2]) : 0.f;
-        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);
+        const bool live = valid && field_in_unit_cube(u0, u1, u2);
         const float cur_gsig = valid ? cur.gsig : 0.f;
         float cur_grgb[4];
 #pragma unroll

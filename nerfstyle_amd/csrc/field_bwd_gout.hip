@@ -115,7 +115,7 @@ k_field_bwd_gout(FieldBwdArgsOf<DIRS> b) {
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
     __syncthreads();
 
-    const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
+    const uint32_t Mc = FIELD_COUNT(a);
     const uint32_t ntiles = (Mc + 15) / 16;
     // The wave index is read through one lane: the compiler cannot tell that threadIdx.x >> 6 is the same for a wave's 64
     // lanes, and with it per-lane the tile counter, the loop's back edge and the `is there a next tile` test all ran as
@@ -246,7 +246,7 @@ k_field_bwd_gout(FieldBwdArgsOf<DIRS> b) {
         const float u0 = field_unit(cur.x0, a.bmin[0], a.bsize[0]);
         const float u1 = field_unit(cur.x1, a.bmin[1], a.bsize[1]);
         const float u2 = field_unit(cur.x2, a.bmin[2], a.bsize[2]);
-        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);   // NaN -> zeros too
+        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);   // field_in_unit_cube, spelled out: through the call one s_and_b64 here takes its operands in the other order
         const float cur_gsig = valid ? cur.gsig : 0.f;
         float cur_grgb[4];
 #pragma unroll
@@ -507,7 +507,7 @@ k_field_bwd_color(FieldBwdArgsOf<DIRS> b) {
     field_build_fw<CD, false, DIRS>(wl, a.params);
     field_build_bw<CD>(wt, a.params);
     __syncthreads();
-    const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
+    const uint32_t Mc = FIELD_COUNT(a);
     const uint32_t ntiles = (Mc + 15) / 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -522,7 +522,7 @@ k_field_bwd_color(FieldBwdArgsOf<DIRS> b) {
         const float u0 = field_unit(a.xyzs[(size_t)m * 3 + 0], a.bmin[0], a.bsize[0]);
         const float u1 = field_unit(a.xyzs[(size_t)m * 3 + 1], a.bmin[1], a.bsize[1]);
         const float u2 = field_unit(a.xyzs[(size_t)m * 3 + 2], a.bmin[2], a.bsize[2]);
-        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);
+        const bool live = valid && field_in_unit_cube(u0, u1, u2);
         float grgb[4];
         {
             const float *gp = b.grad_rgbs + (size_t)m * a.C_ch;

@@ -179,43 +179,90 @@ template <> struct RowLd<_Float16> {
     }
 };
 
-// Trilinear interpolation of one level for both encoders (gridencoder.cu:134-181, align_corners
-// = True, style = 0 on this path: networks/tcnn_nerf.py:26-35).
+// In-range test of an encoder input (gridencoder.cu:107-132: inputs outside [0,1] encode to zeros); NaN -> zeros too
+__device__ __forceinline__ bool field_in_unit_cube(float u0, float u1, float u2) {
+    return u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1;
+}
+
+// ---- one level of the encoders (gridencoder.cu:134-181, align_corners = True, style = 0: networks/tcnn_nerf.py:26-35) ------
+// The helpers below fix an OPERATION ORDER as well as a value: the kernels that inline them sit at register steps (k_field_fwd
+// at 125 of 128 VGPRs), and e.g. forming all eight weights before the eight rows costs the forward five registers and a wave
+// per SIMD.  After any edit compare tools/kernel_stats.py against the parent (DESIGN.md "Shared encode helpers").
+
+// cell, fractions and the weights' product table of one level: w[idx] = wxy[idx & 3] * wz[idx >> 2] is (wx*wy)*wz, the
+// reference's product order (gridencoder.cu:160-175)
+__device__ __forceinline__ void field_level_front(const NsrLevel &lv, float u0, float u1, float u2, uint32_t (&c)[3], float (&f)[3],
+                                                  float (&wxy)[4], float (&wz)[2]) {
+    nsr_grid_locate(u0, lv.resolution, 1, f[0], c[0]);
+    nsr_grid_locate(u1, lv.resolution, 1, f[1], c[1]);
+    nsr_grid_locate(u2, lv.resolution, 1, f[2], c[2]);
+    wxy[0] = (1 - f[0]) * (1 - f[1]); wxy[1] = f[0] * (1 - f[1]); wxy[2] = (1 - f[0]) * f[1]; wxy[3] = f[0] * f[1];
+    wz[0] = 1 - f[2]; wz[1] = f[2];
+}
+
+// The corner index, written once.  FAST (wave-uniform, from the host's level table): the four levels a call handles, one per
+// 16-lane group, are all hashed with a power-of-two size, so row = (x ^ y*P1 ^ z*P2) & (size - 1) -- the value nsr_grid_row
+// gives -- without the per-lane hash/dense select and the invariant-divisor modulo.  The y and z products of a cell's two
+// planes are formed once per level (field_corner_yz), not once per corner.
+template <bool FAST>
+__device__ __forceinline__ bool field_corner_yz(const NsrLevel &lv, uint32_t c1, uint32_t c2, uint32_t (&ty)[2], uint32_t (&tz)[2]) {
+    const bool hashed = FAST || lv.use_hash != 0;
+    const uint32_t mulY = hashed ? 2654435761u : lv.mul[1], mulZ = hashed ? 805459861u : lv.mul[2];
+    ty[0] = c1 * mulY; ty[1] = (c1 + 1u) * mulY;
+    tz[0] = c2 * mulZ; tz[1] = (c2 + 1u) * mulZ;
+    return hashed;
+}
+// table row of the corner with x coordinate x, y product a and z product b
+template <bool FAST>
+__device__ __forceinline__ uint32_t field_corner_row(const NsrLevel &lv, bool hashed, uint32_t x, uint32_t a, uint32_t b) {
+    if (FAST) return lv.offset + ((x ^ a ^ b) & (lv.size - 1u));
+    const uint32_t index = hashed ? (x ^ a ^ b) : (x * lv.mul[0] + a + b);
+    const uint32_t t = __umulhi(lv.magic, index);
+    const uint32_t q = (t + ((index - t) >> lv.sh1)) >> lv.sh2;
+    return lv.offset + (index - q * lv.size);
+}
+
+// cell and corner weights of one level
+__device__ __forceinline__ void field_level_cell(const NsrLevel &lv, float u0, float u1, float u2, uint32_t (&c)[3], float (&w)[8]) {
+    float f[3], wxy[4], wz[2];
+    field_level_front(lv, u0, u1, u2, c, f, wxy, wz);
+#pragma unroll
+    for (uint32_t idx = 0; idx < 8; idx++) w[idx] = wxy[idx & 3] * wz[idx >> 2];
+}
+
+// table rows of the eight corners of cell c (corner idx: bit 0 = x, bit 1 = y, bit 2 = z)
+template <bool FAST>
+__device__ __forceinline__ void field_cell_rows(const NsrLevel &lv, const uint32_t (&c)[3], uint32_t (&rows)[8]) {
+    uint32_t ty[2], tz[2];
+    const bool hashed = field_corner_yz<FAST>(lv, c[1], c[2], ty, tz);
+#pragma unroll
+    for (uint32_t idx = 0; idx < 8; idx++) rows[idx] = field_corner_row<FAST>(lv, hashed, c[0] + (idx & 1u), ty[(idx >> 1) & 1], tz[idx >> 2]);
+}
+
+// rows and weights of one level.  ONE interleaved loop, not field_level_cell then field_cell_rows: weights-first takes
+// k_field_fwd<_Float16, f16, false> from 125 to 130 VGPRs (four waves per SIMD to three) and k_render_infer from 153-155 to 158-159
+template <bool FAST>
+__device__ __forceinline__ void field_level_rows(const NsrLevel &lv, float u0, float u1, float u2, uint32_t (&rows)[8], float (&w)[8]) {
+    float f[3], wxy[4], wz[2];
+    uint32_t c[3], ty[2], tz[2];
+    field_level_front(lv, u0, u1, u2, c, f, wxy, wz);
+    const bool hashed = field_corner_yz<FAST>(lv, c[1], c[2], ty, tz);
+#pragma unroll
+    for (uint32_t idx = 0; idx < 8; idx++) {
+        w[idx] = wxy[idx & 3] * wz[idx >> 2];
+        rows[idx] = field_corner_row<FAST>(lv, hashed, c[0] + (idx & 1u), ty[(idx >> 1) & 1], tz[idx >> 2]);
+    }
+}
+
+// Trilinear interpolation of one level for both encoders
 template <typename TT, bool SIGMA_ONLY, bool FAST>
 __device__ __forceinline__ float4 field_encode_level(const NsrLevel &lv, const TT *__restrict__ tables, float u0, float u1,
                                                      float u2, bool live) {
-    // FAST (wave-uniform, from the host's level table): the four levels this call handles, one per 16-lane
-    // group, are all hashed with a power-of-two size, so row = (x ^ y*P1 ^ z*P2) & (size - 1) -- the value
-    // nsr_grid_row gives -- without the per-lane hash/dense select and the invariant-divisor modulo.  Either
-    // way the y and z products are formed once per level, not once per corner.
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (live) {
-        float f[3];
-        uint32_t c[3];
-        nsr_grid_locate(u0, lv.resolution, 1, f[0], c[0]);
-        nsr_grid_locate(u1, lv.resolution, 1, f[1], c[1]);
-        nsr_grid_locate(u2, lv.resolution, 1, f[2], c[2]);
-        // (wx*wy)*wz: the reference's product order (gridencoder.cu:160-175)
-        const float wxy[4] = {(1 - f[0]) * (1 - f[1]), f[0] * (1 - f[1]), (1 - f[0]) * f[1], f[0] * f[1]};
-        const float wz[2] = {1 - f[2], f[2]};
-        const bool hashed = FAST || lv.use_hash != 0;
-        const uint32_t mulY = hashed ? 2654435761u : lv.mul[1], mulZ = hashed ? 805459861u : lv.mul[2];
-        const uint32_t ty[2] = {c[1] * mulY, (c[1] + 1u) * mulY}, tz[2] = {c[2] * mulZ, (c[2] + 1u) * mulZ};
         uint32_t rows[8];
         float w[8];
-#pragma unroll
-        for (uint32_t idx = 0; idx < 8; idx++) {
-            w[idx] = wxy[idx & 3] * wz[idx >> 2];
-            const uint32_t x = c[0] + (idx & 1u), a = ty[(idx >> 1) & 1], b = tz[idx >> 2];
-            if (FAST) {
-                rows[idx] = lv.offset + ((x ^ a ^ b) & (lv.size - 1u));
-            } else {
-                const uint32_t index = hashed ? (x ^ a ^ b) : (x * lv.mul[0] + a + b);
-                const uint32_t t = __umulhi(lv.magic, index);
-                const uint32_t q = (t + ((index - t) >> lv.sh1)) >> lv.sh2;
-                rows[idx] = lv.offset + (index - q * lv.size);
-            }
-        }
+        field_level_rows<FAST>(lv, u0, u1, u2, rows, w);
         if (SIGMA_ONLY) {
             float2 v[8];
 #pragma unroll
@@ -229,64 +276,12 @@ __device__ __forceinline__ float4 field_encode_level(const NsrLevel &lv, const T
     return acc;
 }
 
-// cell and corner weights of one level: (wx*wy)*wz, the reference's product order (gridencoder.cu:160-175)
-__device__ __forceinline__ void field_level_cell(const NsrLevel &lv, float u0, float u1, float u2, uint32_t (&c)[3], float (&w)[8]) {
-    float f[3];
-    nsr_grid_locate(u0, lv.resolution, 1, f[0], c[0]);
-    nsr_grid_locate(u1, lv.resolution, 1, f[1], c[1]);
-    nsr_grid_locate(u2, lv.resolution, 1, f[2], c[2]);
-    const float wxy[4] = {(1 - f[0]) * (1 - f[1]), f[0] * (1 - f[1]), (1 - f[0]) * f[1], f[0] * f[1]};
-    const float wz[2] = {1 - f[2], f[2]};
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx++) w[idx] = wxy[idx & 3] * wz[idx >> 2];
-}
-
-// table rows of the eight corners of cell c (corner idx: bit 0 = x, bit 1 = y, bit 2 = z)
-template <bool FAST>
-__device__ __forceinline__ void field_cell_rows(const NsrLevel &lv, const uint32_t (&c)[3], uint32_t (&rows)[8]) {
-    const bool hashed = FAST || lv.use_hash != 0;
-    const uint32_t mulY = hashed ? 2654435761u : lv.mul[1], mulZ = hashed ? 805459861u : lv.mul[2];
-    const uint32_t ty[2] = {c[1] * mulY, (c[1] + 1u) * mulY}, tz[2] = {c[2] * mulZ, (c[2] + 1u) * mulZ};
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx++) {
-        const uint32_t x = c[0] + (idx & 1u), a = ty[(idx >> 1) & 1], b = tz[idx >> 2];
-        if (FAST) {
-            rows[idx] = lv.offset + ((x ^ a ^ b) & (lv.size - 1u));
-        } else {
-            const uint32_t index = hashed ? (x ^ a ^ b) : (x * lv.mul[0] + a + b);
-            const uint32_t t = __umulhi(lv.magic, index);
-            const uint32_t q = (t + ((index - t) >> lv.sh1)) >> lv.sh2;
-            rows[idx] = lv.offset + (index - q * lv.size);
-        }
-    }
-}
-
-// rows and weights of one level (the first half of field_encode_level)
-template <bool FAST>
-__device__ __forceinline__ void field_level_rows(const NsrLevel &lv, float u0, float u1, float u2, uint32_t (&rows)[8], float (&w)[8]) {
-    float f[3];
-    uint32_t c[3];
-    nsr_grid_locate(u0, lv.resolution, 1, f[0], c[0]);
-    nsr_grid_locate(u1, lv.resolution, 1, f[1], c[1]);
-    nsr_grid_locate(u2, lv.resolution, 1, f[2], c[2]);
-    const float wxy[4] = {(1 - f[0]) * (1 - f[1]), f[0] * (1 - f[1]), (1 - f[0]) * f[1], f[0] * f[1]};
-    const float wz[2] = {1 - f[2], f[2]};
-    const bool hashed = FAST || lv.use_hash != 0;
-    const uint32_t mulY = hashed ? 2654435761u : lv.mul[1], mulZ = hashed ? 805459861u : lv.mul[2];
-    const uint32_t ty[2] = {c[1] * mulY, (c[1] + 1u) * mulY}, tz[2] = {c[2] * mulZ, (c[2] + 1u) * mulZ};
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx++) {
-        w[idx] = wxy[idx & 3] * wz[idx >> 2];
-        const uint32_t x = c[0] + (idx & 1u), a = ty[(idx >> 1) & 1], b = tz[idx >> 2];
-        if (FAST) {
-            rows[idx] = lv.offset + ((x ^ a ^ b) & (lv.size - 1u));
-        } else {
-            const uint32_t index = hashed ? (x ^ a ^ b) : (x * lv.mul[0] + a + b);
-            const uint32_t t = __umulhi(lv.magic, index);
-            const uint32_t q = (t + ((index - t) >> lv.sh1)) >> lv.sh2;
-            rows[idx] = lv.offset + (index - q * lv.size);
-        }
-    }
+// The lane's level assignment: lane group g runs four calls, call i on level field_lane_level(g, i), so call i covers one level per
+// group: {0,2,4,6} {1,3,5,7} {8,10,12,14} {9,11,13,15} (field_call_levels).  A call takes the FAST path when all four are fast.
+__device__ __forceinline__ int field_lane_level(int g, int i) { return i == 0 ? 2 * g : i == 1 ? 2 * g + 1 : i == 2 ? 8 + 2 * g : 9 + 2 * g; }
+__device__ __forceinline__ uint32_t field_call_levels(int i) { return 0x0055u << ((i & 1) + 8 * (i >> 1)); }
+__device__ __forceinline__ bool field_call_is_fast(uint32_t fast_levels, int i) {
+    return (fast_levels & field_call_levels(i)) == field_call_levels(i);
 }
 
 // fp32 sums of the four levels' gathered 16-bit rows (corners 0..7 in that order) -> the two B fragments
@@ -316,18 +311,15 @@ __device__ __forceinline__ void field_mix_rows(const uint2 (&v)[4][8], const flo
 template <typename TT, int CD, bool SIGMA_ONLY, bool BATCH_GATHER = false>
 __device__ __forceinline__ void field_encode(const NsrLevel *lds_lv, const TT *__restrict__ tables, float u0, float u1, float u2,
                                              bool live, int g, s8v &xd, s8v &xc, uint32_t fast_levels) {
-    const int lvl[4] = {2 * g, 2 * g + 1, 8 + 2 * g, 9 + 2 * g};
-    // levels per call (one per lane group): {0,2,4,6} {1,3,5,7} {8,10,12,14} {9,11,13,15}
-    const uint32_t call_levels[4] = {0x0055u, 0x00AAu, 0x5500u, 0xAA00u};
     if constexpr (BATCH_GATHER && !SIGMA_ONLY && sizeof(TT) == 2) {
         uint2 v[4][8];
         float w[4][8];
         if (live) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const NsrLevel lv = lds_lv[lvl[i]];
+                const NsrLevel lv = lds_lv[field_lane_level(g, i)];
                 uint32_t rows[8];
-                if ((fast_levels & call_levels[i]) == call_levels[i]) field_level_rows<true>(lv, u0, u1, u2, rows, w[i]);
+                if (field_call_is_fast(fast_levels, i)) field_level_rows<true>(lv, u0, u1, u2, rows, w[i]);
                 else field_level_rows<false>(lv, u0, u1, u2, rows, w[i]);
 #pragma unroll
                 for (int idx = 0; idx < 8; idx++) v[i][idx] = reinterpret_cast<const uint2 *>(tables)[rows[idx]];
@@ -338,8 +330,8 @@ __device__ __forceinline__ void field_encode(const NsrLevel *lds_lv, const TT *_
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        const NsrLevel lv = lds_lv[lvl[i]];
-        const float4 a = (fast_levels & call_levels[i]) == call_levels[i]
+        const NsrLevel lv = lds_lv[field_lane_level(g, i)];
+        const float4 a = field_call_is_fast(fast_levels, i)
                              ? field_encode_level<TT, SIGMA_ONLY, true>(lv, tables, u0, u1, u2, live)
                              : field_encode_level<TT, SIGMA_ONLY, false>(lv, tables, u0, u1, u2, live);
         xd[2 * i + 0] = MM<CD>::cvt(a.x);
@@ -424,6 +416,9 @@ __device__ __forceinline__ uint32_t field_logical_block() {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
 }
 
+// The device-side sample count (M is only a capacity).  A macro: inlined from a function the clamp gets another scalar prologue
+// and the kernel behind it another schedule; expanded in the kernel it compiles as it always has.
+#define FIELD_COUNT(a) ((a).m_dev ? min((uint32_t)max((a).m_dev[0], 0), (a).M) : (a).M)
 
 // host: everything of FieldArgs that the descriptor, the two parameter pointers and the sample count decide (the buffers are
 // the caller's); `tables` must be 16-byte aligned for the gathers

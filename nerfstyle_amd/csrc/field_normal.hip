@@ -1,6 +1,6 @@
 // Density gradient of the fused field for gfx950, in FORWARD mode: sigma and d sigma / d position of every sample in one
-// launch (normal maps: n = -grad sigma / |grad sigma|).  A translation unit of its own: it calls the shared helpers of
-// field_common.h / mfma_tiles.h and edits none of them, so the forward, backward and streaming kernels keep their ISA.
+// launch (normal maps: n = -grad sigma / |grad sigma|).  A translation unit of its own on the shared helpers of
+// field_common.h / mfma_tiles.h, whose operation order is pinned (DESIGN.md "Shared encode helpers": tools/kernel_stats.py).
 //
 // Work decomposition: k_field_fwd's.  A wave owns 16 consecutive samples; lane (s = lane&15, g = lane>>4) encodes levels
 // {2g, 2g+1, 8+2g, 9+2g} of sample s from the DENSITY half of the eight corner rows -- the value pair, with the weights and
@@ -53,7 +53,8 @@ __device__ __forceinline__ void dg_build_w1_cells(short *lds, const float *__res
 }
 
 // One level: the density feature pair (field_encode_level's SIGMA_ONLY sum, term for term) and its three partials in cell
-// units.  Corner idx: bit 0 = x, bit 1 = y, bit 2 = z.
+// units.  Restates field_level_front (it also needs wx and wy alone) and, on two channels with pre-multiplied pair weights and
+// no scale, the partials of k_grid_input_bwd (gridenc.hip): moving either changes this kernel's instruction count.  Corner idx: bit 0 = x, bit 1 = y, bit 2 = z.
 template <typename TT, bool FAST>
 __device__ __forceinline__ void dg_encode_level(const NsrLevel &lv, const TT *__restrict__ tables, float u0, float u1, float u2,
                                                 bool live, float2 &val, float2 (&tan)[3]) {
@@ -97,13 +98,11 @@ __device__ __forceinline__ void dg_encode_level(const NsrLevel &lv, const TT *__
 template <typename TT, int CD>
 __device__ __forceinline__ void dg_encode(const NsrLevel *lds_lv, const TT *__restrict__ tables, float u0, float u1, float u2,
                                           bool live, int g, s8v &xd, s8v (&td)[3], uint32_t fast_levels) {
-    const int lvl[4] = {2 * g, 2 * g + 1, 8 + 2 * g, 9 + 2 * g};
-    const uint32_t call_levels[4] = {0x0055u, 0x00AAu, 0x5500u, 0xAA00u};
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        const NsrLevel lv = lds_lv[lvl[i]];
+        const NsrLevel lv = lds_lv[field_lane_level(g, i)];
         float2 val, tan[3];
-        if ((fast_levels & call_levels[i]) == call_levels[i]) dg_encode_level<TT, true>(lv, tables, u0, u1, u2, live, val, tan);
+        if (field_call_is_fast(fast_levels, i)) dg_encode_level<TT, true>(lv, tables, u0, u1, u2, live, val, tan);
         else dg_encode_level<TT, false>(lv, tables, u0, u1, u2, live, val, tan);
         xd[2 * i + 0] = MM<CD>::cvt(val.x);
         xd[2 * i + 1] = MM<CD>::cvt(val.y);
@@ -141,7 +140,7 @@ k_field_density_grad(DensityGradArgs da) {
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
     __syncthreads();
 
-    const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
+    const uint32_t Mc = FIELD_COUNT(a);
     const uint32_t ntiles = (Mc + 15) / 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -160,8 +159,7 @@ k_field_density_grad(DensityGradArgs da) {
             u1 = field_unit(a.xyzs[(size_t)m * 3 + 1], a.bmin[1], a.bsize[1]);
             u2 = field_unit(a.xyzs[(size_t)m * 3 + 2], a.bmin[2], a.bsize[2]);
         }
-        // gridencoder.cu:107-132: inputs outside [0,1] encode to zeros
-        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);   // NaN -> zeros too
+        const bool live = valid && field_in_unit_cube(u0, u1, u2);
         s8v xd, td[3];
         dg_encode<TT, CD>(lds_lv, tables, u0, u1, u2, live, g, xd, td, a.fast_levels);
 

@@ -1,8 +1,8 @@
 // Position gradient of the fused field for gfx950: d loss / d xyz of every sample from the encoder-output gradients that the
 // ordered backward leaves in its workspace (nsr_field_backward with perm: [M][16] float4 = (density f0, density f1, colour f0,
 // colour f1) per sample slot and level, field_bwd_gout.hip), contracted with the spatial partials of the trilinear interpolation.
-// A translation unit of its own: it calls the shared helpers of field_common.h and edits none of them, so the forward, backward
-// and streaming kernels keep their ISA.  No MLP, no LDS beyond the level table, no atomics.
+// A translation unit of its own on the shared helpers of field_common.h, whose operation order is pinned (DESIGN.md "Shared
+// encode helpers").  No MLP, no LDS beyond the level table, no atomics.
 //
 // Work decomposition: k_field_fwd's.  A wave owns 16 samples (16 consecutive slots, or 16 consecutive entries of perm: the
 // gathers then hit in L2 as the forward's do); lane (s = lane&15, g = lane>>4) owns levels {2g, 2g+1, 8+2g, 9+2g} of sample s.
@@ -42,7 +42,7 @@ k_field_xgrad(XGradArgs xa) {
     if (threadIdx.x < 16) lds_lv[threadIdx.x] = a.lv[threadIdx.x];
     __syncthreads();
 
-    const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
+    const uint32_t Mc = FIELD_COUNT(a);
     const uint32_t ntiles = (Mc + 15) / 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, g = lane >> 4;
@@ -51,8 +51,6 @@ k_field_xgrad(XGradArgs xa) {
     const uint32_t tpb = (ntiles + gridDim.x - 1) / gridDim.x;
     const uint32_t t_begin = lb * tpb;
     const uint32_t t_end = min(t_begin + tpb, ntiles);
-    const int lvl[4] = {2 * g, 2 * g + 1, 8 + 2 * g, 9 + 2 * g};
-    const uint32_t call_levels[4] = {0x0055u, 0x00AAu, 0x5500u, 0xAA00u};
 
     for (uint32_t tile = t_begin + wave; tile < t_end; tile += 4) {
         const uint32_t j = tile * 16 + s;
@@ -66,8 +64,7 @@ k_field_xgrad(XGradArgs xa) {
             u1 = field_unit(a.xyzs[(size_t)m * 3 + 1], a.bmin[1], a.bsize[1]);
             u2 = field_unit(a.xyzs[(size_t)m * 3 + 2], a.bmin[2], a.bsize[2]);
         }
-        // gridencoder.cu:107-132: inputs outside [0,1] encode to zeros -> no gradient
-        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);   // NaN -> zeros too
+        const bool live = valid && field_in_unit_cube(u0, u1, u2);     // outside: no gradient
         float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};      // levels 2g, 2g+1 and 8+2g, 9+2g
         if (live) {
             Raw v[4][8];
@@ -76,17 +73,17 @@ k_field_xgrad(XGradArgs xa) {
             const float4 *ep = xa.enc_grad + (size_t)m * 16;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const NsrLevel lv = lds_lv[lvl[i]];
+                const NsrLevel lv = lds_lv[field_lane_level(g, i)];
                 uint32_t c[3], rows[8];
                 nsr_grid_locate(u0, lv.resolution, 1, f[i][0], c[0]);
                 nsr_grid_locate(u1, lv.resolution, 1, f[i][1], c[1]);
                 nsr_grid_locate(u2, lv.resolution, 1, f[i][2], c[2]);
                 scale[i] = (float)lv.resolution;
-                if ((a.fast_levels & call_levels[i]) == call_levels[i]) field_cell_rows<true>(lv, c, rows);
+                if (field_call_is_fast(a.fast_levels, i)) field_cell_rows<true>(lv, c, rows);
                 else field_cell_rows<false>(lv, c, rows);
 #pragma unroll
                 for (int idx = 0; idx < 8; idx++) v[i][idx] = tables[rows[idx]];
-                eg[i] = ep[lvl[i]];
+                eg[i] = ep[field_lane_level(g, i)];
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) {

@@ -23,6 +23,16 @@ template <> struct GeIO<_Float16> {
     __device__ static void st(_Float16 *p, float v) { *p = (_Float16)v; }
 };
 
+// weight and table row of corner idx (bit d = the upper corner on axis d) of cell g: gridencoder.cu:160-175
+__device__ __forceinline__ uint32_t ge_corner(const NsrLevel &lv, const float (&f)[3], const uint32_t (&g)[3], uint32_t idx,
+                                              uint32_t style, float &w) {
+    uint32_t p[3];
+    w = 1;
+#pragma unroll
+    for (uint32_t d = 0; d < 3; d++) { w *= (idx >> d) & 1u ? f[d] : 1 - f[d]; p[d] = g[d] + ((idx >> d) & 1u); }
+    return nsr_grid_row(lv, p[0], p[1], p[2], style);
+}
+
 // gridencoder.cu:83-187.  One thread per (sample, level); samples are the fast index so that a
 // wave's 64 lanes walk 64 consecutive samples of one level (consecutive samples of a ray share
 // cells on the coarse levels -> identical addresses are merged by the texture addresser).
@@ -53,14 +63,8 @@ k_grid_fwd(const float *__restrict__ inputs, const T *__restrict__ grid, T *__re
     for (int ch = 0; ch < C; ch++) acc[ch] = 0.0f;
 #pragma unroll
     for (uint32_t idx = 0; idx < 8; idx++) {
-        float w = 1;
-        uint32_t p[3];
-#pragma unroll
-        for (uint32_t d = 0; d < 3; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1 - f[d]; p[d] = g[d]; }
-            else { w *= f[d]; p[d] = g[d] + 1; }
-        }
-        const uint32_t row = nsr_grid_row(lv, p[0], p[1], p[2], style);
+        float w;
+        const uint32_t row = ge_corner(lv, f, g, idx, style, w);
 #pragma unroll
         for (int ch = 0; ch < C; ch++) acc[ch] += w * GeIO<T>::ld(tab + (size_t)row * C + ch);
     }
@@ -91,14 +95,8 @@ k_grid_bwd(const T *__restrict__ grad, const float *__restrict__ inputs, float *
     float *tab = grad_grid + (size_t)lv.offset * C;
 #pragma unroll
     for (uint32_t idx = 0; idx < 8; idx++) {
-        float w = 1;
-        uint32_t p[3];
-#pragma unroll
-        for (uint32_t d = 0; d < 3; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1 - f[d]; p[d] = g[d]; }
-            else { w *= f[d]; p[d] = g[d] + 1; }
-        }
-        const uint32_t row = nsr_grid_row(lv, p[0], p[1], p[2], style);
+        float w;
+        const uint32_t row = ge_corner(lv, f, g, idx, style, w);
 #pragma unroll
         for (int ch = 0; ch < C; ch++) atomicAdd(tab + (size_t)row * C + ch, w * gcur[ch]);
     }

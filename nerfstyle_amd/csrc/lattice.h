@@ -48,8 +48,8 @@ static inline bool lat_geometry(const NsrLevel *lv, LatGeom &g, uint32_t max_slo
 }
 
 #ifdef __HIPCC__
-// nsr_grid_row for style 0 with the cheap cases taken out (the level is wave-uniform here): a power-of-two table is
-// masked, a dense level needs neither 32-bit multiplies (index < 2^19) nor the modulo (index < (res + 1)^3 <= size).
+// field_corner_row (field_common.h) restated per corner with the cheap cases taken out (the level is wave-uniform here): a
+// power-of-two table is masked, a dense level needs neither 32-bit multiplies (index < 2^19) nor the modulo (index < (res + 1)^3 <= size).
 __device__ __forceinline__ uint32_t lat_row(const NsrLevel &lv, uint32_t x, uint32_t y, uint32_t z) {
     if (lv.use_hash) {
         const uint32_t index = x ^ (y * 2654435761u) ^ (z * 805459861u);

@@ -143,7 +143,7 @@ k_render_infer(RenderInferArgs a) {
             u1 = field_unit(y, a.f.bmin[1], a.f.bsize[1]);
             u2 = field_unit(z, a.f.bmin[2], a.f.bsize[2]);
         }
-        const bool live = got && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);
+        const bool live = got && field_in_unit_cube(u0, u1, u2);
         s8v xd, xc;
         field_encode<TT, CD, false, true>(lds_lv, tables, u0, u1, u2, live, g, xd, xc, a.f.fast_levels);
         const f4v o = field_density_net<CD>(wl, lane, xd);

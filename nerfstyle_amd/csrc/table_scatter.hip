@@ -156,7 +156,7 @@ k_table_scatter(TableScatterArgs a) {
     for (uint32_t k = lane; k < a.lat_slots; k += 64) lat[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
 
-    const uint32_t Mc = a.m_dev ? min((uint32_t)max(a.m_dev[0], 0), a.M) : a.M;
+    const uint32_t Mc = FIELD_COUNT(a);
     if (Mc == 0) return;
     const uint32_t ntiles = (Mc + 15) / 16;
     const uint32_t nwaves = gridDim.x * (TS_THREADS / 64), gw = blockIdx.x * (TS_THREADS / 64) + wave;
@@ -208,7 +208,7 @@ k_table_scatter(TableScatterArgs a) {
         const bool valid = tile * 16 + (uint32_t)s < Mc;
         const float u0 = field_unit(x0, a.bmin[0], a.bsize[0]), u1 = field_unit(x1, a.bmin[1], a.bsize[1]),
                     u2 = field_unit(x2, a.bmin[2], a.bsize[2]);
-        const bool live = valid && (u0 >= 0 && u0 <= 1 && u1 >= 0 && u1 <= 1 && u2 >= 0 && u2 <= 1);
+        const bool live = valid && field_in_unit_cube(u0, u1, u2);
         const uint32_t live16 = (uint32_t)(__ballot(live) & 0xFFFFull);      // lanes 0..15 are samples 0..15
         // this lane's sample's block: the sort key's quantisation (sample_order.hip), 10 bits per axis
         const uint32_t q0 = (uint32_t)fminf(fmaxf(u0 * kq, 0.0f), kq - 1.0f), q1 = (uint32_t)fminf(fmaxf(u1 * kq, 0.0f), kq - 1.0f),

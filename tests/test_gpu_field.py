@@ -531,3 +531,125 @@ def test_spatial_scatter_near_lds_limit_counts_mlp_gradient_once(O, dev, min_res
     assert float(np.abs(mlp0).sum()) > 0 and rel_l2(mlp1, mlp0) < 2e-5
     assert rel_l2(g1.cpu().numpy(), g0.cpu().numpy()) < 2e-5
 
+
+
+# ---------------------------------------------------------------------------------------------
+# the corner-row function's two branches: power-of-two mask (FAST) next to the invariant-divisor modulo
+# ---------------------------------------------------------------------------------------------
+_CORNER_REF = {}
+
+
+def _corner_row_reference(O, table_half):
+    """Built once per table type and shared, read-only: 1000 samples, two level tables with the same contents and the oracle's
+    answers for both.  Descriptor 'fast': every level hashed with a power-of-two size (fast_levels = 0xFFFF).  Descriptor
+    'general': every level 8 rows longer, so no level is fast; the 8 pad rows hold NaN.  The two hash the same corner to different
+    rows (x & (size - 1) against x % (size + 8)), so rows never coincide by construction and the form built is the issue's second
+    one: each descriptor against the oracle, which takes its rows from that descriptor's own offsets."""
+    if table_half in _CORNER_REF:
+        return _CORNER_REF[table_half]
+    from oracle import torch_port as TP
+    ref = TP.Field(num_classes=5, table_scale=0.5)
+    pls, S = ref.pls, O.grid_S(ref.pls)
+    res = O.grid_resolutions(16, S, 16).astype(np.int64)
+    size = np.array([min(2 ** 19, 1 << int(np.ceil(np.log2((r + 1) ** 3)))) for r in res], np.int64)
+    off = {'fast': np.concatenate([[0], np.cumsum(size)]).astype(np.int32),
+           'general': np.concatenate([[0], np.cumsum(size + 8)]).astype(np.int32)}
+    rng = np.random.default_rng(2024)
+    # the faces of the encoder's unit cube, just outside each, NaN, then random points.  Box radius 2: u = ((x + 2) / 4 + 1) / 2
+    # is 1 at x = 2 and 0 at x = -6; 2 (1 + 2^-20) and -6.00001 are the nearest inputs that safely round to u > 1 and u < 0
+    spec = []
+    for ax in range(3):
+        for v, v_out in ((2.0, 2.0 * (1 + 2.0 ** -20)), (-6.0, -6.00001)):
+            for w in (v, v_out):
+                q = (rng.random(3) * 8 - 6).astype(np.float32)
+                q[ax] = w
+                spec.append(q)
+    spec.append(np.array([0.5, np.nan, 0.5], np.float32))
+    cand = np.concatenate([np.array(spec, np.float32), (rng.random((1100, 3)) * 8 - 6).astype(np.float32)])
+    dead = np.zeros(len(cand), bool)
+    dead[1:12:2] = True
+    dead[12] = True
+    cand_o = cand.copy()
+    cand_o[12] = [3.0, 0.5, 0.5]                 # the oracle's stand-in for NaN: outside encodes to zeros as well
+    x = O.encoder_inputs(cand_o, 2.0)
+    rows = O.grid_corner_rows(x, off['general'], pls, 16, 0, True, 0).astype(np.int64)      # [L, B, 8], level-relative
+    inside = rows[0, :, 0] != 0xFFFFFFFF
+    assert np.array_equal(inside, ~dead)         # the oracle agrees on which of the special samples encode
+    hits_pad = (inside[None, :, None] & (rows >= size[:, None, None])).any(axis=(0, 2))
+    assert not hits_pad[:13].any() and hits_pad.mean() <= 0.05, hits_pad.mean()
+    keep = np.flatnonzero(~hits_pad)[:1000]
+    pts, pts_o = cand[keep], cand_o[keep]
+    tab = (rng.random((int(size.sum()), 2, 2)) - 0.5).astype(np.float32)
+    if table_half:
+        tab = tab.astype(np.float16).astype(np.float32)
+    tabs = {'fast': tab, 'general': np.full((int((size + 8).sum()), 2, 2), np.nan, np.float32)}
+    for l in range(16):
+        tabs['general'][off['general'][l]:off['general'][l] + size[l]] = tab[off['fast'][l]:off['fast'][l + 1]]
+    out = {'pts': pts, 'dead': dead[keep], 'off': off, 'tabs': tabs, 'ref': ref, 'share': float(hits_pad.mean())}
+    for k in ('fast', 'general'):
+        t = np.nan_to_num(tabs[k])               # the oracle never reads a pad row either (hits_pad); NaN would only warn
+        fp = O.FieldParams(np.ascontiguousarray(t[:, 0, :]), np.ascontiguousarray(t[:, 1, :]), ref.p_density.detach().numpy(),
+                           ref.p_color1.detach().numpy(), ref.p_color2.detach().numpy(), ref.p_class.detach().numpy(), off[k],
+                           pls, num_classes=5)
+        xo = O.encoder_inputs(pts_o, 2.0)
+        enc = [O.grid_encode_forward(xo, e, off[k], pls, 16, 0, True, 0) for e in (fp.emb_density, fp.emb_color)]
+        out[k] = (np.stack(enc, 1).reshape(len(pts), 2, 16, 2),) + O.field_forward(fp, pts_o, half='f16')   # [M, enc, level, f]
+    _CORNER_REF[table_half] = out
+    return out
+
+
+def _corner_row_run(dev, R, which, table_half, M):
+    import ctypes
+    from nerfstyle_amd import _lib as L
+    from nerfstyle_amd.common import BBox
+    from nerfstyle_amd.config import NetworkConfig
+    from nerfstyle_amd.style_nerf import StyleTCNerf
+    m = StyleTCNerf(NetworkConfig(), BBox.from_radius(2.0), 5, enc_dtype=None if table_half else torch.float32, use_dir=False)
+    d = m._desc(1.0)
+    off = R['off'][which]
+    d.offsets = off.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    tables = T(R['tabs'][which], dev)
+    if table_half:
+        tables = tables.to(torch.float16)
+    ref = R['ref']
+    mlp = T(np.concatenate([p.detach().numpy().ravel() for p in (ref.p_density, ref.p_color1, ref.p_color2, ref.p_class)]), dev)
+    assert mlp.numel() == L.lib().nsr_field_mlp_param_count(0)
+    xyz = T(R['pts'][:M], dev)
+    sig = torch.full((M,), -7.0, device=dev)
+    rgb = torch.full((M, 8), -7.0, device=dev)
+    feats = torch.zeros(((M + 15) // 16) * 512, dtype=torch.int32, device=dev)
+    L.check(L.lib().nsr_field_forward(ctypes.byref(d), L.p(tables), L.p(mlp), L.p(xyz), M, None, L.p(sig), L.p(rgb), L.p(feats),
+                                      None, L.stream()), 'field_forward')
+    # feats [tile][lane = 16 g + s][xd | xc][2 i + f]: level 2g + (i & 1) + 8 (i >> 1) of sample 16 tile + s -> [M, enc, level, f]
+    f = feats.view(torch.float16).view(-1, 4, 16, 2, 2, 2, 2).cpu().numpy().astype(np.float32)   # tile g s enc hi odd f
+    f = f.transpose(0, 2, 3, 4, 1, 5, 6)                                                          # tile s enc hi g odd f
+    return sig.cpu().numpy(), rgb.cpu().numpy(), f.reshape(-1, 2, 16, 2)[:M]
+
+
+@pytest.mark.parametrize('M', [1, 15, 16, 17, 1000])
+@pytest.mark.parametrize('table_half', [True, False], ids=['f16', 'f32'])
+def test_field_forward_fast_and_general_corner_rows(O, dev, table_half, M):
+    """field_corner_row<true> (mask) and <false> (modulo) on the same table contents, both against the oracle's rows.
+    Bounds: a feature is an fp32 sum of eight products (error <= 8 * 2^-24 * max|table| = 2.4e-7) rounded once to f16, the
+    oracle's is the non-contracted fp32 sum; two values that close round to the same f16 or to neighbours, so the bar is one
+    f16 ulp at max|table| = 0.5 (2^-12 = 2.4e-4) -- a wrong row moves a feature by the tables' spread, 0.29.  Outputs: the
+    existing forward bars of test_field_forward (rel L2 2e-3 against the f16-emulating oracle, 2e-2 on the logit), taken on the
+    1000 samples; a shorter call must give the bytes of the long one on its samples.  At most 5 % of the candidates are left out
+    for touching a pad row (asserted where the reference is built; seed 2024 leaves out under 2 %)."""
+    R = _corner_row_reference(O, table_half)
+    assert R['share'] <= 0.05
+    for which in ('fast', 'general'):
+        sig, rgb, f = _corner_row_run(dev, R, which, table_half, M)
+        enc_o, out_o, sig_o, logit_o = R[which]
+        dead = R['dead'][:M]
+        assert np.isfinite(sig).all() and np.isfinite(rgb).all() and np.isfinite(f).all()          # no pad row was read
+        assert not f[dead].any()                                                                    # outside and NaN: zeros
+        assert np.abs(f - enc_o[:M]).max() <= 2.0 ** -12 + 2.4e-7
+        if M == 1000:
+            assert rel_l2(rgb, out_o) < 2e-3 and np.abs(np.log(sig) - logit_o).max() < 2e-2
+            R[which + '_gpu'] = (sig, rgb, f)
+        else:
+            if which + '_gpu' not in R:
+                R[which + '_gpu'] = _corner_row_run(dev, R, which, table_half, 1000)
+            s1, r1, f1 = R[which + '_gpu']
+            assert np.array_equal(sig, s1[:M]) and np.array_equal(rgb, r1[:M]) and np.array_equal(f, f1[:M])
