@@ -587,6 +587,48 @@ int nsr_generate_rays_backward(const float *pose, uint32_t w, uint32_t h, float 
                                int camera_flip, const int32_t *pix, uint32_t N, const float *grad_rays_o,
                                const float *grad_rays_d, void *workspace, float *grad_pose, nsr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mixed-frame ray batches: the rays of many cameras in one training step.  A batch is S segments of K rays each
+ * (N = S * K), ray n belongs to segment n / K, segment s names one frame seg_frame[s] in [0, F); frames may repeat
+ * (K = 1: a frame per ray).  S, K and F are host integers; seg_frame [S] i32 and pix [N] i32 live on the device and may
+ * change between replays of a captured graph.  Every call is capture-safe.
+ * ------------------------------------------------------------------------------------------ */
+/* nsr_generate_rays with a pose per segment: poses [F,3,4] f32 row-major (device).  Row n is bit-identical to
+ * nsr_generate_rays called with the pose of frame seg_frame[n / K] and pix[n] (the same operations in the same order, no
+ * contraction).  A segment whose seg_frame entry is outside [0, F) gets NaN origins and directions -- the march and the field
+ * treat NaN positions as out of range -- and no pose is read for it. */
+int nsr_generate_rays_frames(const float *poses, uint32_t F, uint32_t w, uint32_t h, float fx, float fy, float cx, float cy,
+                             int camera_flip, const int32_t *seg_frame, const int32_t *pix, uint32_t S, uint32_t K,
+                             float *rays_o, float *rays_d, nsr_stream_t stream);
+
+/* Its backward with respect to the poses (same leading arguments): grad_poses [F,3,4] f32 row-major is WRITTEN for every
+ * frame, exact zeros for a frame that no segment names; a segment whose entry is outside [0, F) contributes nothing.  Per
+ * frame the sums of nsr_generate_rays_backward over the rays of the segments naming it.  Per-ray terms in fp64 as there;
+ * reduction order: per segment block trees (below 64 rays per segment: one thread per segment, rays in order), the segment's
+ * block partials in ascending order, then per frame the segments naming it in ascending s; all in fp64, rounded to fp32 once.
+ * No atomics, no counters, nothing of the workspace is read that this call did not write: two calls give the same bits.
+ * workspace: nsr_generate_rays_frames_backward_workspace_bytes(F, S, K) bytes, 8-byte aligned. */
+uint64_t nsr_generate_rays_frames_backward_workspace_bytes(uint32_t F, uint32_t S, uint32_t K);
+int nsr_generate_rays_frames_backward(const float *poses, uint32_t F, uint32_t w, uint32_t h, float fx, float fy, float cx,
+                                      float cy, int camera_flip, const int32_t *seg_frame, const int32_t *pix, uint32_t S,
+                                      uint32_t K, const float *grad_rays_o, const float *grad_rays_d, void *workspace,
+                                      float *grad_poses, nsr_stream_t stream);
+
+/* Draws a batch on the device: UNIFORM WITH REPLACEMENT (the reference draws without replacement inside one frame; duplicates
+ * in a 4 096-of-762 048 draw do not matter to a mean loss).  P = w * h pixels per frame.  Philox4x32-10 keyed by `seed`, with
+ * seq = sequence + (sequence_dev ? sequence_dev[0] : 0):
+ *   segment s:          r = philox(s, seq, 2, stream_id),  seg_frame[s] = umulhi(r.x, F); with fixed_frames ([S] i32, device,
+ *                       optional) seg_frame[s] = fixed_frames[s] and no draw is made
+ *   ray n = s * K + k:  q = philox(n, seq, 3, stream_id),  pix[n] = umulhi(q.x, P),  rows[n] (int64) = seg_frame[s] * P + pix[n],
+ *                       the ray's row of a [F * P, ...] target table (a fixed frame outside [0, F) counts as frame 0 in rows
+ *                       only, so that no consumer of rows reads out of bounds)
+ * stream_id: the data-parallel rank -- ranks draw distinct batches from one seed.  advance != 0 (needs sequence_dev): after the
+ * draw, on the same stream, a kernel of its own increments sequence_dev[0], so a captured graph draws a fresh batch on every
+ * replay, like nsr_occ_update. */
+int nsr_draw_frame_batch(uint32_t F, uint32_t P, uint32_t S, uint32_t K, uint64_t seed, uint32_t sequence,
+                         uint32_t *sequence_dev, uint32_t stream_id, const int32_t *fixed_frames, int advance,
+                         int32_t *seg_frame, int32_t *pix, int64_t *rows, nsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

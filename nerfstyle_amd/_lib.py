@@ -108,6 +108,10 @@ SIGNATURES = {
     'nsr_rays_position_backward': (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),
     'nsr_generate_rays_backward_workspace_bytes': (u64, [u32]),
     'nsr_generate_rays_backward': (i32, [vp, u32, u32, f32, f32, f32, f32, i32, vp, u32, vp, vp, vp, vp, vp]),
+    'nsr_generate_rays_frames': (i32, [vp, u32, u32, u32, f32, f32, f32, f32, i32, vp, vp, u32, u32, vp, vp, vp]),
+    'nsr_generate_rays_frames_backward_workspace_bytes': (u64, [u32, u32, u32]),
+    'nsr_generate_rays_frames_backward': (i32, [vp, u32, u32, u32, f32, f32, f32, f32, i32, vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    'nsr_draw_frame_batch': (i32, [u32, u32, u32, u32, u64, u32, vp, u32, vp, i32, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // What is neither march nor composite: near/far against the AABB, morton codes, the occupancy bitfield, device ray
 // generation, and the library's identity functions (ABI version, status strings, target).
 #include "rm_probe.h"
+#include "ray_pose.h"
 
 // ---------------------------------------------------------------------------------------------
 // utilities
@@ -73,26 +74,12 @@ __global__ void k_packbits(const float *__restrict__ grid, uint32_t N, float thr
 __global__ void k_generate_rays(const float *__restrict__ pose, uint32_t w, uint32_t h, float fx, float fy, float cx,
                                 float cy, int camera_flip, const int32_t *__restrict__ pix, uint32_t N,
                                 float *__restrict__ rays_o, float *__restrict__ rays_d) {
-#pragma clang fp contract(off)
-    const float r00 = pose[0], r01 = pose[1], r02 = pose[2], tx = pose[3];
-    const float r10 = pose[4], r11 = pose[5], r12 = pose[6], ty = pose[7];
-    const float r20 = pose[8], r21 = pose[9], r22 = pose[10], tz = pose[11];
+    const RuPose P = ru_load_pose(pose);
     const float f0 = (camera_flip >> 2) & 1 ? -1.0f : 1.0f;   // nerf_lib.py:121, bit order [2,1,0]
     const float f1 = (camera_flip >> 1) & 1 ? -1.0f : 1.0f;
     const float f2 = (camera_flip >> 0) & 1 ? -1.0f : 1.0f;
-    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
-        const uint32_t p = pix ? (uint32_t)pix[n] : n;
-        const uint32_t py = p / w, px = p - py * w;
-        // np.linspace(0, w, 2w+1)[1::2] == x + 0.5 exactly in fp32 for w < 2^22
-        const float i = (float)px + 0.5f, j = (float)py + 0.5f;
-        const float d0 = ((i - cx) / fx) * f0, d1 = ((j - cy) / fy) * f1, d2 = f2;
-        const float wx = r00 * d0 + r01 * d1 + r02 * d2;
-        const float wy = r10 * d0 + r11 * d1 + r12 * d2;
-        const float wz = r20 * d0 + r21 * d1 + r22 * d2;
-        const float nrm = sqrtf(wx * wx + wy * wy + wz * wz);
-        rays_d[n * 3 + 0] = wx / nrm; rays_d[n * 3 + 1] = wy / nrm; rays_d[n * 3 + 2] = wz / nrm;
-        rays_o[n * 3 + 0] = tx; rays_o[n * 3 + 1] = ty; rays_o[n * 3 + 2] = tz;
-    }
+    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x)
+        ru_write_ray(P, f0, f1, f2, pix ? (uint32_t)pix[n] : n, w, fx, fy, cx, cy, n, rays_o, rays_d);
 }
 
 // Backward of k_generate_rays with respect to the pose: grad_pose[:, 3] = sum_n grad_o[n]; with c_n the pixel's camera-frame
@@ -100,63 +87,21 @@ __global__ void k_generate_rays(const float *__restrict__ pose, uint32_t w, uint
 // Twelve sums over the rays: every ray's term and the sums are formed in fp64 (a few dozen operations per ray against two
 // 12-byte loads; the per-entry error is then the final rounding to fp32), block tree + a fixed-order one-block final pass over
 // the block partials, as k_recon_loss: no atomics, no counter, every partial the final pass reads was written by this call.
-#define RU_BLOCK 256
+// The per-ray term (ru_pose_term) and the block tree (ru_block_sum12) are ray_pose.h's.
 #define RU_MAX_BLOCKS 2048u
-
-// fixed-order block tree over twelve values: threads 0..11 leave with the block's sum k in v[0]
-__device__ __forceinline__ void ru_block_sum12(double (&v)[12]) {
-    __shared__ double red[12][RU_BLOCK / 64];
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 12; k++) v[k] += __shfl_xor(v[k], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 12; k++) red[k][threadIdx.x >> 6] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        double s = 0.0;
-        for (int w = 0; w < RU_BLOCK / 64; w++) s += red[threadIdx.x][w];
-        v[0] = s;
-    }
-}
 
 __global__ void __launch_bounds__(RU_BLOCK)
 k_generate_rays_bwd(const float *__restrict__ pose, uint32_t w, float fx, float fy, float cx, float cy, int camera_flip,
                     const int32_t *__restrict__ pix, uint32_t N, const float *__restrict__ g_o, const float *__restrict__ g_d,
                     double *__restrict__ partials) {
     double R[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) R[r][c] = (double)pose[r * 4 + c];
-    }
+    ru_load_rotation(pose, R);
     const double f0 = (camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (camera_flip >> 0) & 1 ? -1.0 : 1.0;
     double acc[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) acc[k] = 0.0;
-    for (uint32_t n = blockIdx.x * RU_BLOCK + threadIdx.x; n < N; n += gridDim.x * RU_BLOCK) {
-        const uint32_t p = pix ? (uint32_t)pix[n] : n;
-        const uint32_t py = p / w, px = p - py * w;
-        const double c[3] = {(((double)px + 0.5 - (double)cx) / (double)fx) * f0, (((double)py + 0.5 - (double)cy) / (double)fy) * f1, f2};
-        double v[3], gd[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            v[r] = R[r][0] * c[0] + R[r][1] * c[1] + R[r][2] * c[2];
-            gd[r] = (double)g_d[(size_t)n * 3 + r];
-        }
-        const double inv = 1.0 / sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        const double d[3] = {v[0] * inv, v[1] * inv, v[2] * inv};
-        const double dg = d[0] * gd[0] + d[1] * gd[1] + d[2] * gd[2];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const double h = (gd[r] - d[r] * dg) * inv;
-#pragma unroll
-            for (int k = 0; k < 3; k++) acc[r * 4 + k] += h * c[k];
-            acc[r * 4 + 3] += (double)g_o[(size_t)n * 3 + r];
-        }
-    }
+    for (uint32_t n = blockIdx.x * RU_BLOCK + threadIdx.x; n < N; n += gridDim.x * RU_BLOCK)
+        ru_pose_term(R, f0, f1, f2, pix ? (uint32_t)pix[n] : n, w, fx, fy, cx, cy, g_o, g_d, n, acc);
     ru_block_sum12(acc);
     if (threadIdx.x < 12) partials[(size_t)blockIdx.x * 12 + threadIdx.x] = acc[0];
 }

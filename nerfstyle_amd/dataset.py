@@ -8,12 +8,17 @@ one device index op.
 
 File parsing (transforms JSON, PNG decode, segment .npz) is the caller's: `data/` is outside the hot path
  and is not rebuilt here.  `ResidentDataset` takes the decoded arrays."""
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
 import torch
 
 from .common import BBox, Intrinsics
+
+
+# a drawn mixed-frame batch: seg_frame [S] int32, pix [S*K] int32, rows [S*K] int64 (rows of target_rgb_rows / target_cls_rows)
+FrameBatch = namedtuple('FrameBatch', ('seg_frame', 'pix', 'rows', 'S', 'K'))
 
 
 class ResidentDataset:
@@ -42,6 +47,7 @@ class ResidentDataset:
         self.poses = torch.from_numpy(poses).to(device)
         self.intr, self.num_classes, self.bound = intr, int(num_classes), bound
         self.bbox = BBox.from_radius(bound)
+        self._rgb_rows = self._cls_rows = None
 
     def __len__(self):
         return self.poses.shape[0]
@@ -49,3 +55,50 @@ class ResidentDataset:
     def sample(self, frame: int, pix: torch.Tensor):
         """(pose [4,4], target [len(pix), C]) for pixel ids `pix` (row-major y * w + x) of frame `frame`"""
         return self.poses[frame], self.targets[frame].index_select(0, pix)
+
+    # ---- mixed-frame batches: rays of many frames in one step ------------------------------------------------------------------
+    @property
+    def target_rgb_rows(self):
+        """[F*HW, 3] f32 contiguous: row f * HW + p is pixel p of frame f.  Built once, on first use; with `rows` of a drawn
+        batch it is what recon_loss(target_rgb=..., pix=rows) takes."""
+        if self._rgb_rows is None:
+            self._rgb_rows = self.targets[:, :, :3].reshape(-1, 3).contiguous()
+        return self._rgb_rows
+
+    @property
+    def target_cls_rows(self):
+        """[F*HW] int64 segment ids, row order of target_rgb_rows; only when segment maps were given"""
+        if self.targets.shape[2] < 4:
+            raise AttributeError('target_cls_rows: the dataset was built without segment maps')
+        if self._cls_rows is None:
+            self._cls_rows = self.targets[:, :, 3].reshape(-1).to(torch.int64).contiguous()
+        return self._cls_rows
+
+    def draw(self, S: int, K: int, seed: int, sequence: int = 0, sequence_dev: Optional[torch.Tensor] = None, stream_id: int = 0,
+             frames: Optional[torch.Tensor] = None, advance: bool = False, out: Optional[FrameBatch] = None) -> FrameBatch:
+        """A batch of S segments of K rays drawn on the device (nsr_draw_frame_batch): per segment a frame, per ray a pixel of
+        it, UNIFORM WITH REPLACEMENT -> FrameBatch(seg_frame, pix, rows, S, K).  Counter-based: (seed, sequence
+        [+ sequence_dev[0], a uint32-valued int32 device word], stream_id = the data-parallel rank) name the batch.
+        frames [S] int32 on the device: the segments' frames, only the pixels are drawn.  advance: sequence_dev is incremented
+        after the draw, so a captured graph draws a fresh batch on every replay.  out: a previous batch of the same S and K,
+        rewritten in place (nothing is allocated)."""
+        from . import _lib as L
+        from . import profiling
+        dev = self.targets.device
+        n_frames, P = self.targets.shape[0], self.targets.shape[1]
+        if out is not None:
+            assert (out.S, out.K) == (S, K), 'out: a batch of the same S and K'
+            seg_frame, pix, rows = out.seg_frame, out.pix, out.rows
+        else:
+            seg_frame = torch.empty(S, dtype=torch.int32, device=dev)
+            pix = torch.empty(S * K, dtype=torch.int32, device=dev)
+            rows = torch.empty(S * K, dtype=torch.int64, device=dev)
+        if frames is not None:
+            assert frames.dtype == torch.int32 and frames.numel() == S, 'frames [S] int32'
+        if sequence_dev is not None:
+            assert sequence_dev.dtype == torch.int32 and sequence_dev.numel() >= 1, 'sequence_dev: an int32 device word'
+        with profiling.timed('draw_frame_batch'):
+            L.check(L.lib().nsr_draw_frame_batch(n_frames, P, S, K, int(seed) & (2 ** 64 - 1), int(sequence) & 0xffffffff,
+                                                 L.p(sequence_dev), int(stream_id), L.p(frames), int(bool(advance)), L.p(seg_frame),
+                                                 L.p(pix), L.p(rows), L.stream()), 'draw_frame_batch')
+        return out if out is not None else FrameBatch(seg_frame, pix, rows, S, K)

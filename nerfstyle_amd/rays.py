@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import profiling
 from .common import Box2D, Intrinsics, RayBatch
 
 
@@ -102,6 +103,64 @@ def generate_rays(pose, intr: Intrinsics, img=None, patch: Optional[Box2D] = Non
     rays = RayBatch.__new__(RayBatch)    # directions are already unit length (normalised in-kernel)
     rays.origins, rays.dirs = rays_o, rays_d
     return rays, target
+
+
+# ---- mixed-frame batches: S segments of K rays, segment s of frame seg_frame[s] (nsr_generate_rays_frames) ----------------------
+def _launch_generate_rays_frames(poses, W, H, fx, fy, cx, cy, camera_flip, seg_frame, pix, K):
+    F, S = poses.shape[0], seg_frame.shape[0]
+    N = S * K
+    rays_o = torch.empty(N, 3, dtype=torch.float32, device=poses.device)
+    rays_d = torch.empty(N, 3, dtype=torch.float32, device=poses.device)
+    with profiling.timed('generate_rays_frames'):
+        L.check(L.lib().nsr_generate_rays_frames(L.p(poses), F, W, H, fx, fy, cx, cy, camera_flip, L.p(seg_frame), L.p(pix), S, K,
+                                                 L.p(rays_o), L.p(rays_d), L.stream()), 'generate_rays_frames')
+    return rays_o, rays_d
+
+
+class _generate_rays_frames_fn(torch.autograd.Function):
+    """nsr_generate_rays_frames with a gradient for the poses (nsr_generate_rays_frames_backward): poses [F,3,4] or [F,4,4] ->
+    (rays_o, rays_d)."""
+
+    @staticmethod
+    def forward(ctx, poses, W, H, fx, fy, cx, cy, camera_flip, seg_frame, pix, K):
+        flat = poses.detach()[:, :3, :].contiguous()
+        ctx.save_for_backward(flat, seg_frame, pix)
+        ctx.args, ctx.K, ctx.rows = (W, H, fx, fy, cx, cy, camera_flip), K, poses.shape[1]
+        return _launch_generate_rays_frames(flat, W, H, fx, fy, cx, cy, camera_flip, seg_frame, pix, K)
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        poses, seg_frame, pix = ctx.saved_tensors
+        F, S, K, dev = poses.shape[0], seg_frame.shape[0], ctx.K, poses.device
+        g_o, g_d = g_o.to(torch.float32).contiguous(), g_d.to(torch.float32).contiguous()
+        ws = torch.empty(int(L.lib().nsr_generate_rays_frames_backward_workspace_bytes(F, S, K)) // 8, dtype=torch.float64, device=dev)
+        grad = torch.empty(F, 3, 4, dtype=torch.float32, device=dev)
+        with profiling.timed('generate_rays_frames_bwd'):
+            L.check(L.lib().nsr_generate_rays_frames_backward(L.p(poses), F, *ctx.args, L.p(seg_frame), L.p(pix), S, K, L.p(g_o),
+                                                              L.p(g_d), L.p(ws), L.p(grad), L.stream()), 'generate_rays_frames_backward')
+        if ctx.rows == 4:                        # [F,4,4] poses: their last rows never reach the rays
+            grad = torch.cat((grad, torch.zeros(F, 1, 4, dtype=torch.float32, device=dev)), dim=1)
+        return (grad,) + (None,) * 10
+
+
+def generate_rays_frames(poses, seg_frame, pix, K: int, intr: Intrinsics, camera_flip: int = 0, pose_grad: bool = False) -> RayBatch:
+    """Rays of a mixed-frame batch: poses [F,3,4] (or [F,4,4]), seg_frame [S] int32 and pix [S*K] int32 on the device (what
+    ResidentDataset.draw returns); ray n is pixel pix[n] of frame seg_frame[n // K], bit for bit the ray generate_rays makes
+    from that frame's pose.  One set of intrinsics for all frames.  A seg_frame entry outside [0, F) gives NaN rays.
+    pose_grad (Renderer.pose_gradients): the rays stay attached to a `poses` tensor that requires grad; its gradient is the
+    per-frame sum, zero rows for frames the batch does not name."""
+    assert poses.dim() == 3 and poses.shape[1] in (3, 4) and poses.shape[2] == 4, 'poses [F,3,4] or [F,4,4]'
+    assert seg_frame.dtype == torch.int32 and pix.dtype == torch.int32 and pix.numel() == seg_frame.numel() * K, \
+        'seg_frame [S] int32, pix [S*K] int32'
+    W, H = intr.size()
+    args = (W, H, float(intr.fx), float(intr.fy), float(intr.cx), float(intr.cy), int(camera_flip), seg_frame, pix, int(K))
+    if pose_grad and poses.requires_grad and torch.is_grad_enabled():
+        rays_o, rays_d = _generate_rays_frames_fn.apply(poses.to(torch.float32), *args)
+    else:
+        rays_o, rays_d = _launch_generate_rays_frames(poses.detach().to(torch.float32)[:, :3, :].contiguous(), *args)
+    rays = RayBatch.__new__(RayBatch)    # directions are already unit length (normalised in-kernel)
+    rays.origins, rays.dirs = rays_o, rays_d
+    return rays
 
 
 def tile_order(w: int, h: int, tile_w: int = 8, tile_h: int = 8, device=None) -> torch.Tensor:

@@ -19,7 +19,7 @@ import torch
 from . import raymarching
 from .common import Box2D, Intrinsics, RayBatch
 from .config import RendererConfig
-from .rays import generate_rays, pixel_window, tile_order
+from .rays import generate_rays, generate_rays_frames, pixel_window, tile_order
 from .style_nerf import StyleTCNerf
 
 STEP_CTR_SIZE = 16
@@ -607,6 +607,24 @@ class Renderer(torch.nn.Module):
         if geometry is not None:
             extra['geometry'] = geometry
         output['rgb_map'], output['trans_map'], output['classes'] = render_fn(rays, dense=dense, **extra)
+        output.update(geometry or {})
+        return output
+
+    def render_frames(self, poses, batch, training: bool = True) -> Dict[str, torch.Tensor]:
+        """A training render of a mixed-frame batch: poses [F,3,4] (PoseRefiner.forward_all(), or the dataset's), batch =
+        ResidentDataset.draw(...) (seg_frame, pix, rows, S, K): ray n is pixel pix[n] of frame seg_frame[n // K].  The output
+        dict of render(); 'target' is None -- the caller has batch.rows for recon_loss(..., pix=batch.rows).  From the rays on
+        it IS render_train: occupancy updates, geometry_terms, the sample order and, with `pose_gradients` and poses that
+        require grad, the camera gradient (one row of poses.grad per frame, zeros for frames outside the batch) with every
+        refusal of the single-pose path.  Training only; begin_train / GraphedRenderStep have no mixed-frame form."""
+        if not training:
+            raise NotImplementedError('render_frames is a training render: an image has one pose, use render(pose)')
+        rays = generate_rays_frames(poses, batch.seg_frame, batch.pix, batch.K, self.intr, camera_flip=self.cfg.flip_camera,
+                                    pose_grad=self._pose_grad_wanted(poses))
+        output = {'target': None}
+        geometry = {} if self.geometry_terms else None
+        extra = {} if geometry is None else {'geometry': geometry}
+        output['rgb_map'], output['trans_map'], output['classes'] = self.render_train(rays, dense=False, **extra)
         output.update(geometry or {})
         return output
 
