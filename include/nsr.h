@@ -186,6 +186,18 @@ int nsr_recon_loss(const float *rgb_map, const float *classes, uint32_t N, uint3
                    const int64_t *target_cls, const int64_t *pix, float ce_lambda, float factor, const float *scale,
                    float *grad_rgb_map, float *grad_classes, float *loss_out, void *workspace, nsr_stream_t stream);
 
+/* nsr_recon_loss with a weight per ray (importance sampling, nsr_draw_frame_batch_error below):
+ *   loss = (1/3N) sum_n w_n |rgb_map_n - target_n|^2 + ce_lambda * (1/N) sum_n w_n (logsumexp(classes_n) - classes_n[label_n])
+ * ray_weight [N] f32 (NULL: every weight 1) multiplies every per-ray term of the value and of both gradients; the means still
+ * divide by N.  ray_err [N] f32 (optional) receives the ray's UNWEIGHTED sum over the three channels of (rgb_map - target)^2
+ * (the fp32 differences, their squares summed in fp64 and rounded once), what nsr_error_map_accumulate takes.  Same grid, block tree, final pass, loss_out and workspace
+ * (nsr_recon_loss_workspace_bytes) as nsr_recon_loss; with every weight exactly 1.0f the value and the gradients are
+ * bit-identical to nsr_recon_loss's. */
+int nsr_recon_loss_weighted(const float *rgb_map, const float *classes, uint32_t N, uint32_t nc, const float *target_rgb,
+                            const int64_t *target_cls, const int64_t *pix, const float *ray_weight, float ce_lambda, float factor,
+                            const float *scale, float *grad_rgb_map, float *grad_classes, float *ray_err, float *loss_out,
+                            void *workspace, nsr_stream_t stream);
+
 /* Matting-Laplacian photorealism loss of Deep Photo Style Transfer, the reference's MattingLaplacian (loss.py:217-278,
  * win_rad r, eps): loss_out[0] (device fp64) = trace(V M V^T), M the matting Laplacian of `target` over every (2r+1)^2
  * window inside the image, V = v reshaped [3, H*W]; grad_v (may be NULL) [3,H,W] f32 = d loss / d v, rounded once.
@@ -628,6 +640,61 @@ int nsr_generate_rays_frames_backward(const float *poses, uint32_t F, uint32_t w
 int nsr_draw_frame_batch(uint32_t F, uint32_t P, uint32_t S, uint32_t K, uint64_t seed, uint32_t sequence,
                          uint32_t *sequence_dev, uint32_t stream_id, const int32_t *fixed_frames, int advance,
                          int32_t *seg_frame, int32_t *pix, int64_t *rows, nsr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Error-map importance sampling (instant-ngp's error map): pixels drawn in proportion to a coarse per-frame map of the running
+ * training error, every ray weighted by (uniform pdf) / (pdf of its draw), so that mean(weight * loss) still estimates the
+ * uniform mean loss.  Everything that decides a draw is INTEGER arithmetic (atomic integer sums are exact in any order): two
+ * runs, two ranks and a restatement on the host reach the same bits.  All calls are capture-safe and read nothing on the host.
+ *
+ * Grid: a w x h frame is cut into cell x cell pixel cells, gw = ceil(w / cell), gh = ceil(h / cell), G = gw * gh; cell g has
+ * column gx = g % gw and row gy = g / gw, real extent cw = min(cell, w - gx * cell) by ch = min(cell, h - gy * cell) and
+ * npix = cw * ch pixels; pixel p (row-major, y * w + x) lies in cell (y / cell) * gw + x / cell.  P = w * h.
+ * State, all on the device, caller-allocated: err [F,G] f32 (running squared error per cell), acc_sum [F,G] u64 and
+ * acc_cnt [F,G] u32 (this step's accumulators, zero between steps), prefix [F,G] u64, frame_prefix [F] u64 (8-byte aligned).
+ * cell == 0, F, w or h == 0, P or F * G past 31 bits -> NSR_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------------------------ */
+/* Adds the rays' errors to the accumulators.  Ray n (segment n / K, frame f = seg_frame[n / K], pixel p = pix[n]) is skipped when
+ * f is outside [0, F), p outside [0, P), or ray_err[n] is NaN or negative.  Otherwise, in fp32,
+ *   a = (u64) min(floor(ray_err[n] * 2^20), 2^22)
+ * is added to acc_sum[f, cell of p] and 1 to acc_cnt[f, cell of p] with integer atomics (a wave adds up the rays that share a
+ * cell first, for up to four distinct cells: a frame walked in 8 x 8 tiles makes one request per wave, not 64). */
+int nsr_error_map_accumulate(uint32_t F, uint32_t w, uint32_t h, uint32_t cell, const int32_t *seg_frame, const int32_t *pix,
+                             const float *ray_err, uint32_t S, uint32_t K, uint64_t *acc_sum, uint32_t *acc_cnt, nsr_stream_t stream);
+
+/* Folds the accumulators into err and rebuilds the prefixes (two launches: a workgroup per frame, then one workgroup over the
+ * frames' totals).  Per cell with acc_cnt > 0, no contraction, in this order:
+ *   mean = (f32)((f64)acc_sum / (f64)acc_cnt * 2^-20);   err = err + decay * (mean - err);   acc_sum = acc_cnt = 0
+ * (other cells keep err bit for bit).  Then for every cell  q = (u32) min(floor(err * quant_scale), 2^18)  in fp32, 0 when the
+ * product is NaN or negative; the cell's mass is npix * q (u64); prefix[f, g] = sum of the masses of cells 0..g of frame f
+ * (inclusive), the frame's total is prefix[f, G - 1], and frame_prefix[f] = sum of the totals of frames 0..f (inclusive).
+ * decay outside [0, 1] or quant_scale <= 0 -> NSR_ERR_INVALID_ARG. */
+int nsr_error_map_rebuild(uint32_t F, uint32_t w, uint32_t h, uint32_t cell, float decay, float quant_scale, float *err,
+                          uint64_t *acc_sum, uint32_t *acc_cnt, uint64_t *prefix, uint64_t *frame_prefix, nsr_stream_t stream);
+
+/* nsr_draw_frame_batch (same Philox calls, seed, seq, stream_id, fixed_frames, advance, seg_frame, pix, rows) with the pixels,
+ * and optionally the frames, drawn from the map; weights [N] f32.  u = uniform_mix in [0, 1] (else NSR_ERR_INVALID_ARG),
+ * t = round(u * 2^32) as a 64-bit integer, mulhi64(x, m) = (x * m) >> 64, total_f = prefix[f, G - 1],
+ * grand = frame_prefix[F - 1]; "first above" is the first index whose inclusive prefix exceeds the target.
+ *   segment s:  r = philox(s, seq, 2, stream_id), uniform frame fu = umulhi(r.x, F).
+ *       fixed_frames: seg_frame[s] = fixed_frames[s], frame factor 1.
+ *       frames_by_error == 0, or grand == 0: seg_frame[s] = fu, frame factor 1.
+ *       else: seg_frame[s] = fu if r.y < t, otherwise first above mulhi64(r.z * 2^32 + r.w, grand) in frame_prefix;
+ *             frame factor = 1 / (u + (1 - u) * ((f32)F * (f32)total_f) / (f32)grand).
+ *   ray n of frame f:  r = philox(n, seq, 3, stream_id), uniform pixel pu = umulhi(r.x, P).
+ *       f outside [0, F) (a fixed frame), or total_f == 0: pix[n] = pu, pixel factor 1.
+ *       else: pix[n] = pu if r.y < t; otherwise q = philox(n, seq, 4, stream_id), cell g = first above
+ *             mulhi64(q.x * 2^32 + q.y, total_f) in prefix[f, :], and pix[n] = (gy * cell + umulhi(q.w, ch)) * w + gx * cell +
+ *             umulhi(q.z, cw).  With g the cell of pix[n] (either branch) and q_g = (prefix[f, g] - prefix[f, g - 1]) / npix_g:
+ *             pixel factor = 1 / (u + (1 - u) * ((f32)q_g * (f32)P) / (f32)total_f).
+ *   weights[n] = pixel factor * frame factor; each factor in fp32, no contraction, evaluated as written: the product in the
+ *   inner parentheses, times (1 - u), divided, plus u, reciprocal.  rows[n] as in nsr_draw_frame_batch.
+ * u == 1 gives nsr_draw_frame_batch's seg_frame, pix and rows bit for bit and weights of exactly 1. */
+int nsr_draw_frame_batch_error(uint32_t F, uint32_t w, uint32_t h, uint32_t cell, const uint64_t *prefix,
+                               const uint64_t *frame_prefix, float uniform_mix, int frames_by_error, uint32_t S, uint32_t K,
+                               uint64_t seed, uint32_t sequence, uint32_t *sequence_dev, uint32_t stream_id,
+                               const int32_t *fixed_frames, int advance, int32_t *seg_frame, int32_t *pix, int64_t *rows,
+                               float *weights, nsr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,7 @@ SIGNATURES = {
     'nsr_ray_geometry_backward': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, i32, vp, vp]),
     'nsr_recon_loss_workspace_bytes': (u64, [u32]),
     'nsr_recon_loss': (i32, [vp, vp, u32, u32, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp]),
+    'nsr_recon_loss_weighted': (i32, [vp, vp, u32, u32, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
     'nsr_matting_laplacian_workspace_bytes': (u64, [u32, u32, u32]),
     'nsr_matting_laplacian': (i32, [vp, vp, u32, u32, u32, f64, vp, vp, vp, vp]),
     'nsr_march_rays': (i32, [u32, u32, vp, vp, vp, vp, vp, f32, f32, u32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp,
@@ -112,6 +113,10 @@ SIGNATURES = {
     'nsr_generate_rays_frames_backward_workspace_bytes': (u64, [u32, u32, u32]),
     'nsr_generate_rays_frames_backward': (i32, [vp, u32, u32, u32, f32, f32, f32, f32, i32, vp, vp, u32, u32, vp, vp, vp, vp, vp]),
     'nsr_draw_frame_batch': (i32, [u32, u32, u32, u32, u64, u32, vp, u32, vp, i32, vp, vp, vp, vp]),
+    'nsr_error_map_accumulate': (i32, [u32, u32, u32, u32, vp, vp, vp, u32, u32, vp, vp, vp]),
+    'nsr_error_map_rebuild': (i32, [u32, u32, u32, u32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    'nsr_draw_frame_batch_error': (i32, [u32, u32, u32, u32, vp, vp, f32, i32, u32, u32, u64, u32, vp, u32, vp, i32, vp, vp, vp, vp,
+                                         vp]),
 }
 
 _lib = None

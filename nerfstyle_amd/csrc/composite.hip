@@ -512,6 +512,54 @@ k_recon_loss_final(LossArgs a) {
     }
 }
 
+// k_recon_loss with a weight per ray (importance sampling: error_map.hip): every per-ray term of value and gradient times
+// ray_weight[n], the means still over N; ray_err (optional) gets the ray's unweighted sum of squared colour differences.  Written
+// so that a weight of exactly 1 leaves every operation of k_recon_loss with the same operands -- (1 * df) * df + mse contracts
+// like df * df + mse, 1 * (lse - logit) + ce like (lse - logit) + ce -- and the partials go through the same final pass.
+struct WLossArgs {
+    LossArgs l;
+    const float *ray_weight;              // [N] or NULL: 1
+    float *ray_err;                       // [N] or NULL
+};
+
+__global__ void __launch_bounds__(CP_BLOCK)
+k_recon_loss_weighted(WLossArgs wa) {
+    const LossArgs &a = wa.l;
+    const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
+    const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
+    float mse = 0.0f, ce = 0.0f;
+    for (uint32_t n = blockIdx.x * CP_BLOCK + threadIdx.x; n < a.N; n += gridDim.x * CP_BLOCK) {
+        const size_t row = a.pix ? (size_t)a.pix[n] : (size_t)n;
+        const float w = wa.ray_weight ? wa.ray_weight[n] : 1.0f;
+        double e = 0.0;                     // the fp32 differences' squares summed exactly, rounded once
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float df = a.rgb_map[(size_t)n * 3 + k] - a.target_rgb[row * 3 + k];
+            const float wdf = w * df;
+            mse += wdf * df;
+            e += (double)df * (double)df;
+            a.g_rgb[(size_t)n * 3 + k] = 2.0f * df * inv3n * s * w;
+        }
+        if (wa.ray_err) wa.ray_err[n] = (float)e;
+        if (a.classes && a.nc) {
+            const float *lg = a.classes + (size_t)n * a.nc;
+            const uint32_t label = (uint32_t)a.target_cls[row];
+            float mx = lg[0];
+            for (uint32_t k = 1; k < a.nc; k++) mx = fmaxf(mx, lg[k]);
+            float se = 0.0f;
+            for (uint32_t k = 0; k < a.nc; k++) se += expf(lg[k] - mx);
+            const float lse = mx + logf(se);
+            ce += w * (lse - lg[min(label, a.nc - 1u)]);
+            const float gk = a.ce_lambda * invn * s * w;
+            for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
+        }
+    }
+    if (cp_block_sum2(mse, ce)) {
+        a.partials[blockIdx.x * 2] = mse;
+        a.partials[blockIdx.x * 2 + 1] = ce;
+    }
+}
+
 // 256 CUs x 8 blocks of 4 waves: the persistent grid of the ray kernels, the cap of the loss grid and with it the loss workspace
 static constexpr uint32_t CP_MAX_BLOCKS = 2048u;
 static uint32_t cp_grid(uint32_t N) {       // fewer blocks when there are fewer rays
@@ -649,23 +697,45 @@ uint64_t nsr_recon_loss_workspace_bytes(uint32_t N) {
     return (uint64_t)CP_MAX_BLOCKS * 2 * sizeof(float);
 }
 
-int nsr_recon_loss(const float *rgb_map, const float *classes, uint32_t N, uint32_t nc, const float *target_rgb,
-                   const int64_t *target_cls, const int64_t *pix, float ce_lambda, float factor, const float *scale,
-                   float *grad_rgb_map, float *grad_classes, float *loss_out, void *workspace, nsr_stream_t stream) {
+// the checks and the argument block that the plain and the weighted loss share
+static int cp_loss_args(LossArgs &a, const float *rgb_map, const float *classes, uint32_t N, uint32_t nc, const float *target_rgb,
+                        const int64_t *target_cls, const int64_t *pix, float ce_lambda, float factor, const float *scale,
+                        float *grad_rgb_map, float *grad_classes, float *loss_out, void *workspace) {
     NSR_CHECK_PTR(loss_out);
     if (N == 0) return NSR_ERR_INVALID_ARG;
     NSR_CHECK_PTR(rgb_map); NSR_CHECK_PTR(target_rgb); NSR_CHECK_PTR(grad_rgb_map); NSR_CHECK_PTR(workspace);
     const bool with_ce = classes != nullptr && nc > 0 && ce_lambda != 0.0f;
     if (with_ce && (target_cls == nullptr || grad_classes == nullptr)) return NSR_ERR_INVALID_ARG;
-    LossArgs a;
     a.rgb_map = rgb_map; a.classes = with_ce ? classes : nullptr; a.target_rgb = target_rgb; a.target_cls = target_cls; a.pix = pix;
     a.N = N; a.nc = with_ce ? nc : 0u; a.ce_lambda = ce_lambda; a.factor = factor; a.scale = scale;
     a.g_rgb = grad_rgb_map; a.g_classes = grad_classes; a.partials = (float *)workspace; a.out = loss_out;
     uint32_t nb = nsr_div_up(N, CP_BLOCK);
     if (nb > CP_MAX_BLOCKS) nb = CP_MAX_BLOCKS;
     a.nblocks = nb;
-    hipLaunchKernelGGL(k_recon_loss, dim3(nb), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
+    return NSR_OK;
+}
+
+int nsr_recon_loss(const float *rgb_map, const float *classes, uint32_t N, uint32_t nc, const float *target_rgb,
+                   const int64_t *target_cls, const int64_t *pix, float ce_lambda, float factor, const float *scale,
+                   float *grad_rgb_map, float *grad_classes, float *loss_out, void *workspace, nsr_stream_t stream) {
+    LossArgs a;
+    if (const int e = cp_loss_args(a, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
+                                   grad_classes, loss_out, workspace)) return e;
+    hipLaunchKernelGGL(k_recon_loss, dim3(a.nblocks), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
+    return nsr_launch_status();
+}
+
+int nsr_recon_loss_weighted(const float *rgb_map, const float *classes, uint32_t N, uint32_t nc, const float *target_rgb,
+                            const int64_t *target_cls, const int64_t *pix, const float *ray_weight, float ce_lambda, float factor,
+                            const float *scale, float *grad_rgb_map, float *grad_classes, float *ray_err, float *loss_out,
+                            void *workspace, nsr_stream_t stream) {
+    WLossArgs wa;
+    if (const int e = cp_loss_args(wa.l, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
+                                   grad_classes, loss_out, workspace)) return e;
+    wa.ray_weight = ray_weight; wa.ray_err = ray_err;
+    hipLaunchKernelGGL(k_recon_loss_weighted, dim3(wa.l.nblocks), dim3(CP_BLOCK), 0, (hipStream_t)stream, wa);
+    hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, wa.l);
     return nsr_launch_status();
 }
 

@@ -102,3 +102,134 @@ class ResidentDataset:
                                                  L.p(sequence_dev), int(stream_id), L.p(frames), int(bool(advance)), L.p(seg_frame),
                                                  L.p(pix), L.p(rows), L.stream()), 'draw_frame_batch')
         return out if out is not None else FrameBatch(seg_frame, pix, rows, S, K)
+
+
+class ErrorMap:
+    """Error-map importance sampling of training rays (instant-ngp's error map) on top of ResidentDataset.draw.
+
+    Every frame is cut into cell x cell pixel cells (gw = ceil(w / cell), gh = ceil(h / cell), G = gw * gh; the edge cells are
+    ragged).  `err` [F,G] f32 is the running mean squared RGB error (summed over the channels) of the rays drawn in a cell,
+    `init` at the start.  draw() picks pixels in proportion to it, mixed with `uniform_mix` of the uniform draw so that no pixel
+    starves, and returns per ray the weight (uniform pdf) / (pdf of the draw): mean(weight * loss) still estimates the uniform
+    mean loss, recon_loss(..., ray_weight=weights) is that mean.  update() folds the step's per-ray errors into the map:
+    err += decay * (mean error of the step's rays in the cell - err).
+
+    Determinism: everything that decides a draw is integer arithmetic.  The per-ray errors are accumulated as fixed-point
+    integers (`acc_sum` [F,G], `acc_cnt` [F,G], zero between steps), err is quantised to q = min(floor(err * quant_scale), 2^18)
+    and the sampling CDF is the 64-bit prefix sum of the masses npix * q (`prefix` [F,G], `frame_prefix` [F]); integer sums do
+    not depend on the order atomics arrive in, so runs and ranks agree bit for bit and include/nsr.h states the arithmetic
+    precisely enough to restate it.  The 64-bit unsigned state lives in int64 tensors, the 32-bit in int32.
+    Data-parallel: torch.distributed.all_reduce(SUM) of acc_sum and acc_cnt between the loss and update() gives every rank the
+    map of all ranks' rays, bit-identical on every rank.
+
+    Nothing is read on the host and nothing is allocated with out=: a captured graph replays the loop
+
+        batch, wts = emap.draw(S, K, seed, sequence_dev=seq, advance=True)
+        out = renderer.render_frames(poses, batch)
+        loss = recon_loss(out['rgb_map'], out['classes'], ds.target_rgb_rows, ds.target_cls_rows, batch.rows,
+                          ray_weight=wts, ray_err_out=err_buf)
+        loss.backward(); emap.update(batch, err_buf)
+    """
+
+    def __init__(self, dataset: ResidentDataset, cell: int = 16, decay: float = 0.05, uniform_mix: float = 0.1, init: float = 1.0,
+                 quant_scale: float = 65536.0):
+        if cell < 1 or not 0.0 <= decay <= 1.0 or not 0.0 <= uniform_mix <= 1.0 or not quant_scale > 0.0:
+            raise ValueError('ErrorMap: cell >= 1, decay and uniform_mix in [0, 1], quant_scale > 0')
+        self.cell, self.decay, self.uniform_mix, self.init, self.quant_scale = int(cell), float(decay), float(uniform_mix), float(init), float(quant_scale)
+        self.F, self.w, self.h = len(dataset), dataset.intr.w, dataset.intr.h
+        self.gw, self.gh = -(-self.w // self.cell), -(-self.h // self.cell)
+        self.G, self.P = self.gw * self.gh, self.w * self.h
+        dev = dataset.targets.device
+        self.err = torch.full((self.F, self.G), self.init, dtype=torch.float32, device=dev)
+        self.acc_sum = torch.zeros(self.F, self.G, dtype=torch.int64, device=dev)
+        self.acc_cnt = torch.zeros(self.F, self.G, dtype=torch.int32, device=dev)
+        self.prefix = torch.zeros(self.F, self.G, dtype=torch.int64, device=dev)
+        self.frame_prefix = torch.zeros(self.F, dtype=torch.int64, device=dev)
+        self.rebuild()
+
+    def _grid(self):
+        return self.F, self.w, self.h, self.cell
+
+    def rebuild(self):
+        """Folds the accumulators into err (cells that got rays) and rebuilds prefix and frame_prefix from err: two launches.
+        Call it after writing err by hand."""
+        from . import _lib as L
+        from . import profiling
+        with profiling.timed('error_map_rebuild'):
+            L.check(L.lib().nsr_error_map_rebuild(*self._grid(), self.decay, self.quant_scale, L.p(self.err), L.p(self.acc_sum),
+                                                  L.p(self.acc_cnt), L.p(self.prefix), L.p(self.frame_prefix), L.stream()), 'error_map_rebuild')
+
+    def draw(self, S: int, K: int, seed: int, sequence: int = 0, sequence_dev: Optional[torch.Tensor] = None, stream_id: int = 0,
+             frames: Optional[torch.Tensor] = None, frames_by_error: bool = False, advance: bool = False, out=None):
+        """ResidentDataset.draw with the pixels drawn from the map -> (FrameBatch, weights [S*K] f32); the arguments of
+        ResidentDataset.draw mean what they mean there (nsr_draw_frame_batch_error makes the same Philox calls: uniform_mix = 1
+        draws the very batch of ResidentDataset.draw, with weights 1).  frames_by_error: the segments' frames too are drawn in
+        proportion to their total error (mixed with the uniform draw likewise), and the weights carry that factor.
+        out: a previous (FrameBatch, weights) pair of the same S and K, rewritten in place."""
+        from . import _lib as L
+        from . import profiling
+        dev = self.err.device
+        if out is not None:
+            batch, weights = out
+            assert (batch.S, batch.K) == (S, K), 'out: a batch of the same S and K'
+        else:
+            batch = FrameBatch(torch.empty(S, dtype=torch.int32, device=dev), torch.empty(S * K, dtype=torch.int32, device=dev),
+                               torch.empty(S * K, dtype=torch.int64, device=dev), S, K)
+            weights = torch.empty(S * K, dtype=torch.float32, device=dev)
+        if frames is not None:
+            assert frames.dtype == torch.int32 and frames.numel() == S, 'frames [S] int32'
+        if sequence_dev is not None:
+            assert sequence_dev.dtype == torch.int32 and sequence_dev.numel() >= 1, 'sequence_dev: an int32 device word'
+        assert weights.dtype == torch.float32 and weights.numel() == S * K, 'weights [S*K] float32'
+        with profiling.timed('draw_frame_batch_error'):
+            L.check(L.lib().nsr_draw_frame_batch_error(*self._grid(), L.p(self.prefix), L.p(self.frame_prefix), self.uniform_mix,
+                                                       int(bool(frames_by_error)), S, K, int(seed) & (2 ** 64 - 1),
+                                                       int(sequence) & 0xffffffff, L.p(sequence_dev), int(stream_id), L.p(frames),
+                                                       int(bool(advance)), L.p(batch.seg_frame), L.p(batch.pix), L.p(batch.rows),
+                                                       L.p(weights), L.stream()), 'draw_frame_batch_error')
+        return out if out is not None else (batch, weights)
+
+    def accumulate(self, batch: FrameBatch, ray_err: torch.Tensor):
+        """Adds the batch's per-ray errors (recon_loss's ray_err_out) to acc_sum / acc_cnt: one launch.  update() without the
+        rebuild, for a data-parallel all-reduce of the two tensors in between."""
+        from . import _lib as L
+        from . import profiling
+        assert ray_err.dtype == torch.float32 and ray_err.numel() == batch.S * batch.K, 'ray_err [S*K] float32'
+        with profiling.timed('error_map_accumulate'):
+            L.check(L.lib().nsr_error_map_accumulate(*self._grid(), L.p(batch.seg_frame), L.p(batch.pix), L.p(ray_err), batch.S, batch.K,
+                                                     L.p(self.acc_sum), L.p(self.acc_cnt), L.stream()), 'error_map_accumulate')
+
+    def update(self, batch: FrameBatch, ray_err: torch.Tensor):
+        """accumulate() + rebuild(): three launches, no host read."""
+        self.accumulate(batch, ray_err)
+        self.rebuild()
+
+    def pdf(self, frame: int) -> torch.Tensor:
+        """[h, w] float64 on the host: the probability with which draw() picks each pixel of `frame`, given the frame (for
+        inspection and tests; it reads the device)."""
+        prefix = self.prefix[frame].cpu().numpy().astype(np.uint64)
+        mass = np.diff(prefix, prepend=np.uint64(0)).astype(np.float64).reshape(self.gh, self.gw)
+        total = float(prefix[-1])
+        cw = np.minimum(self.cell, self.w - np.arange(self.gw) * self.cell)
+        ch = np.minimum(self.cell, self.h - np.arange(self.gh) * self.cell)
+        uniform = np.full((self.h, self.w), 1.0 / self.P)
+        if total == 0.0:
+            return torch.from_numpy(uniform)
+        u = float(np.float32(self.uniform_mix))
+        per_pixel = mass / total / (ch[:, None] * cw[None, :])
+        ys, xs = np.arange(self.h) // self.cell, np.arange(self.w) // self.cell
+        return torch.from_numpy(u * uniform + (1.0 - u) * per_pixel[ys[:, None], xs[None, :]])
+
+    def state_dict(self):
+        return {'err': self.err.detach().cpu().clone(), 'cell': self.cell, 'decay': self.decay, 'uniform_mix': self.uniform_mix,
+                'init': self.init, 'quant_scale': self.quant_scale}
+
+    def load_state_dict(self, state):
+        if int(state['cell']) != self.cell or tuple(state['err'].shape) != (self.F, self.G):
+            raise ValueError('ErrorMap.load_state_dict: the map was saved for another grid')
+        self.decay, self.uniform_mix = float(state['decay']), float(state['uniform_mix'])
+        self.init, self.quant_scale = float(state['init']), float(state['quant_scale'])
+        self.err.copy_(state['err'])
+        self.acc_sum.zero_()
+        self.acc_cnt.zero_()
+        self.rebuild()

@@ -14,7 +14,7 @@ from . import _lib as L
 
 class _recon_loss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale):
+    def forward(ctx, rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale, ray_weight=None, ray_err_out=None):
         ctx.set_materialize_grads(False)
         N = rgb_map.shape[0]
         dev = rgb_map.device
@@ -33,9 +33,16 @@ class _recon_loss(torch.autograd.Function):
             assert pix.dtype == torch.int64 and pix.is_contiguous() and pix.numel() == N
         else:
             assert target_rgb.shape[0] == N
-        L.check(L.lib().nsr_recon_loss(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls) if with_ce else None, L.p(pix),
-                                       float(ce_lambda), float(factor), L.p(scale), L.p(g_rgb), L.p(g_cls), L.p(out), L.p(ws),
-                                       L.stream()), 'recon_loss')
+        if ray_weight is None and ray_err_out is None:
+            L.check(L.lib().nsr_recon_loss(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls) if with_ce else None, L.p(pix),
+                                           float(ce_lambda), float(factor), L.p(scale), L.p(g_rgb), L.p(g_cls), L.p(out), L.p(ws),
+                                           L.stream()), 'recon_loss')
+        else:
+            for t in (ray_weight, ray_err_out):
+                assert t is None or (t.dtype == torch.float32 and t.numel() == N and not t.requires_grad), 'ray_weight / ray_err_out: [N] float32'
+            L.check(L.lib().nsr_recon_loss_weighted(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls) if with_ce else None,
+                                                    L.p(pix), L.p(ray_weight), float(ce_lambda), float(factor), L.p(scale), L.p(g_rgb),
+                                                    L.p(g_cls), L.p(ray_err_out), L.p(out), L.p(ws), L.stream()), 'recon_loss_weighted')
         ctx.save_for_backward(g_rgb, g_cls)
         ctx.terms = out
         return out[0]
@@ -44,19 +51,23 @@ class _recon_loss(torch.autograd.Function):
     def backward(ctx, go):
         g_rgb, g_cls = ctx.saved_tensors
         if go is None:
-            return (None,) * 8
+            return (None,) * 10
         # the stored gradients already carry scale * factor; `go` is 1 for loss.backward()
-        return g_rgb * go, (g_cls * go if g_cls is not None else None), None, None, None, None, None, None
+        return g_rgb * go, (g_cls * go if g_cls is not None else None), None, None, None, None, None, None, None, None
 
 
-def recon_loss(rgb_map, classes, target_rgb, target_cls=None, pix=None, ce_lambda=1e-3, factor=1.0, scale=None, backward=False):
+def recon_loss(rgb_map, classes, target_rgb, target_cls=None, pix=None, ce_lambda=1e-3, factor=1.0, scale=None, backward=False,
+               ray_weight=None, ray_err_out=None):
     """-> 0-dim loss tensor = factor * scale * (mse + ce_lambda * ce).  rgb_map [N,3], classes [N,nc] (or None) from
     Renderer.render(training=True); target_rgb [P,3] f32 / target_cls [P] int64 resident on the device, pix [N] int64 their rows
     (None: P == N, row n).  scale: 0-dim float32 device tensor (LossScaler.scale_tensor) or None.
     backward=True: the gradient the kernel has just written is back-propagated from here -- autograd.backward(outputs of the
     renderer, d loss / d outputs) -- and the returned loss is detached: `loss.backward()` on the plain form costs a ones-fill and
-    one multiply per stored gradient (three launches, 1.5 % of a 4 096-ray captured step) to apply a factor that is 1."""
-    loss = _recon_loss.apply(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale)
+    one multiply per stored gradient (three launches, 1.5 % of a 4 096-ray captured step) to apply a factor that is 1.
+    ray_weight [N] f32 (ErrorMap.draw's weights): every ray's terms, value and gradient, times its weight, the means still over
+    N (nsr_recon_loss_weighted).  ray_err_out [N] f32: written with the ray's unweighted sum of squared colour differences, what
+    ErrorMap.update takes.  Both are constants of differentiation; with both None the plain kernel runs."""
+    loss = _recon_loss.apply(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale, ray_weight, ray_err_out)
     if not backward or loss.grad_fn is None:
         return loss
     g_rgb, g_cls = loss.grad_fn.saved_tensors
