@@ -198,6 +198,40 @@ int nsr_recon_loss_weighted(const float *rgb_map, const float *classes, uint32_t
                             const float *scale, float *grad_rgb_map, float *grad_classes, float *ray_err, float *loss_out,
                             void *workspace, nsr_stream_t stream);
 
+/* nsr_recon_loss_weighted with a gain per frame and colour channel (per-frame exposure and white balance of a mixed-frame batch).
+ * exposure [F,3] f32: log2 gains, zero is identity.  The batch is S segments of K rays (N == S * K), ray n belongs to segment
+ * s = n / K and frame f = seg_frame[s] (seg_frame [S] i32, nsr_draw_frame_batch).  With w = ray_weight[n] (NULL: 1),
+ * s_ = scale * factor, inv3n = 1 / (3N), row = pix[n] (NULL: n), per ray and channel c in fp32:
+ *   gain = 0 <= f < F ? exp2f(exposure[f,c]) : 1          a frame outside [0, F) reads no exposure row
+ *   p    = rgb_map[n,c] * gain                            what frame f is modelled to have observed (a product rounded on its own)
+ *   df   = p - target_rgb[row,c]
+ *   mse += (w * df) * df                                  the MSE term of loss_out, as in nsr_recon_loss_weighted
+ *   gp   = 2 * df * inv3n * s_ * w                        d loss / d p
+ *   grad_rgb_map[n,c] = gp * gain
+ *   ray_err[n] (optional) = sum_c (f64)df * (f64)df, rounded once: the exposure-corrected error
+ *   term[n,c] = gp * p                                    fp32, staged in the workspace
+ *   grad_exposure[f,c] = (f32)(ln2 * sum over the rays n of frame f of (f64)term[n,c])
+ * The cross-entropy term, grad_classes, loss_out[0..2], the grid, the block tree and the final pass are nsr_recon_loss_weighted's.
+ * grad_exposure [F,3] f32 is WRITTEN for every frame and carries scale * factor as grad_rgb_map does; a frame that no segment
+ * names gets +0.0, a segment whose frame is outside [0, F) contributes to no row.
+ * Order of the per-frame sum (fp64 throughout, rounded to fp32 once; no atomics, no counters; two calls and the replays of a
+ * captured graph give the same bits), that of nsr_generate_rays_frames_backward:
+ *   per segment, K < 64:  one thread adds the segment's rays in ascending n.
+ *   per segment, K >= 64: B = min(ceil(K / 256), 64) blocks of 256 threads; thread t of block b adds rays k = b * 256 + t,
+ *                         k += B * 256, of the segment in that order; a wave adds its 64 lanes by a butterfly (lane ^ 32, 16, 8,
+ *                         4, 2, 1), the block its four waves in ascending order; then the B block sums in ascending b.
+ *   per frame:            the sums of the segments naming it, in ascending s.
+ * With exposure all zero, loss_out, grad_rgb_map, grad_classes and ray_err are bit-identical to nsr_recon_loss_weighted's.
+ * workspace: nsr_recon_loss_exposure_workspace_bytes(N, F, S, K) bytes, 8-byte aligned; nothing of it is read that this call did
+ * not write.  N == 0, F == 0, S == 0, K == 0 or N != S * K -> NSR_ERR_INVALID_ARG before any pointer is looked at; the other
+ * checks are nsr_recon_loss's, and exposure, seg_frame and grad_exposure must not be NULL. */
+uint64_t nsr_recon_loss_exposure_workspace_bytes(uint32_t N, uint32_t F, uint32_t S, uint32_t K);
+int nsr_recon_loss_exposure(const float *rgb_map, const float *classes, uint32_t N, uint32_t nc, const float *target_rgb,
+                            const int64_t *target_cls, const int64_t *pix, const float *ray_weight, const float *exposure, uint32_t F,
+                            const int32_t *seg_frame, uint32_t S, uint32_t K, float ce_lambda, float factor, const float *scale,
+                            float *grad_rgb_map, float *grad_classes, float *grad_exposure, float *ray_err, float *loss_out,
+                            void *workspace, nsr_stream_t stream);
+
 /* Matting-Laplacian photorealism loss of Deep Photo Style Transfer, the reference's MattingLaplacian (loss.py:217-278,
  * win_rad r, eps): loss_out[0] (device fp64) = trace(V M V^T), M the matting Laplacian of `target` over every (2r+1)^2
  * window inside the image, V = v reshaped [3, H*W]; grad_v (may be NULL) [3,H,W] f32 = d loss / d v, rounded once.

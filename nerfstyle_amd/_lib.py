@@ -58,6 +58,9 @@ SIGNATURES = {
     'nsr_recon_loss_workspace_bytes': (u64, [u32]),
     'nsr_recon_loss': (i32, [vp, vp, u32, u32, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp]),
     'nsr_recon_loss_weighted': (i32, [vp, vp, u32, u32, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+    'nsr_recon_loss_exposure_workspace_bytes': (u64, [u32, u32, u32, u32]),
+    'nsr_recon_loss_exposure': (i32, [vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, vp, u32, u32, f32, f32, vp, vp, vp, vp, vp, vp, vp,
+                                      vp]),
     'nsr_matting_laplacian_workspace_bytes': (u64, [u32, u32, u32]),
     'nsr_matting_laplacian': (i32, [vp, vp, u32, u32, u32, f64, vp, vp, vp, vp]),
     'nsr_march_rays': (i32, [u32, u32, vp, vp, vp, vp, vp, f32, f32, u32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp,

@@ -560,6 +560,149 @@ k_recon_loss_weighted(WLossArgs wa) {
     }
 }
 
+// k_recon_loss_weighted with a gain per frame and colour channel (per-frame exposure and white balance): ray n of segment n / K,
+// frame f = seg_frame[n / K], is modelled to have been observed as p = rgb_map * exp2(exposure[f]); the difference, the value and
+// the per-ray error are those of p, the gradient towards rgb_map is the gradient towards p times the gain, and term = (d loss /
+// d p) * p, staged per ray and channel, is what the kernels below add up per frame (d p / d exposure = ln2 * p).  p is a product
+// rounded on its own (__fmul_rn: a contraction into the difference would leave term without its operand); every other
+// expression has the shape it has in k_recon_loss_weighted, so that exposure 0 (gain exactly 1) leaves that kernel's operands.
+struct ELossArgs {
+    WLossArgs w;
+    const float *exposure;                // [F,3] log2 gains
+    const int32_t *seg_frame;             // [N / K]
+    uint32_t F, K;
+    float *term;                          // [N,3]
+};
+
+__global__ void __launch_bounds__(CP_BLOCK)
+k_recon_loss_exposure(ELossArgs ea) {
+    const LossArgs &a = ea.w.l;
+    const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
+    const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
+    float mse = 0.0f, ce = 0.0f;
+    for (uint32_t n = blockIdx.x * CP_BLOCK + threadIdx.x; n < a.N; n += gridDim.x * CP_BLOCK) {
+        const size_t row = a.pix ? (size_t)a.pix[n] : (size_t)n;
+        const float w = ea.w.ray_weight ? ea.w.ray_weight[n] : 1.0f;
+        const uint32_t f = (uint32_t)ea.seg_frame[n / ea.K];
+        const bool named = f < ea.F;       // a frame outside [0, F) reads no exposure row: gain 1
+        double e = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float gain = named ? exp2f(ea.exposure[(size_t)f * 3 + k]) : 1.0f;
+            const float p = __fmul_rn(a.rgb_map[(size_t)n * 3 + k], gain);
+            const float df = p - a.target_rgb[row * 3 + k];
+            const float wdf = w * df;
+            mse += wdf * df;
+            e += (double)df * (double)df;
+            const float gp = 2.0f * df * inv3n * s * w;
+            a.g_rgb[(size_t)n * 3 + k] = gp * gain;
+            ea.term[(size_t)n * 3 + k] = gp * p;
+        }
+        if (ea.w.ray_err) ea.w.ray_err[n] = (float)e;
+        if (a.classes && a.nc) {
+            const float *lg = a.classes + (size_t)n * a.nc;
+            const uint32_t label = (uint32_t)a.target_cls[row];
+            float mx = lg[0];
+            for (uint32_t k = 1; k < a.nc; k++) mx = fmaxf(mx, lg[k]);
+            float se = 0.0f;
+            for (uint32_t k = 0; k < a.nc; k++) se += expf(lg[k] - mx);
+            const float lse = mx + logf(se);
+            ce += w * (lse - lg[min(label, a.nc - 1u)]);
+            const float gk = a.ce_lambda * invn * s * w;
+            for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
+        }
+    }
+    if (cp_block_sum2(mse, ce)) {
+        a.partials[blockIdx.x * 2] = mse;
+        a.partials[blockIdx.x * 2 + 1] = ce;
+    }
+}
+
+// grad_exposure[f] = ln2 * sum of term over the rays of the segments naming f, in fp64, in the order of the pose backward of
+// frame_batch.hip (k_frames_bwd_*) with three sums for its twelve.  seg_partials is [S][B][3] f64, B = cp_exp_seg_blocks(K):
+//   K <  CP_EXP_THREAD_K   k_exposure_seg_thread: a thread per segment adds its K rays in order (B = 1)
+//   K >= CP_EXP_THREAD_K   k_exposure_seg_block: block s * B + b takes rays b * 256 + t, strided by B * 256, of segment s; per
+//                          thread in that order, then the xor tree over the wave (offsets 32 .. 1), then the four waves in order;
+//                          B = ceil(K / 256) capped at CP_EXP_MAX_SEG_BLOCKS
+// k_exposure_final, a wave per frame: the segments in ascending s, 64 at a time (a ballot of seg_frame[s] == f, then the set
+// bits from the lowest); for a segment naming the frame, lanes 0..2 add its B partials in order and then that sum to the
+// frame's; the frame's sum times ln2 is rounded to fp32 once.  A frame no segment names meets no add and gets +0.0; a segment
+// naming no frame writes no partial and none of it is read.  No atomics, no counters; every term and partial read was written
+// earlier in this call.
+#define CP_EXP_THREAD_K 64u
+#define CP_EXP_MAX_SEG_BLOCKS 64u
+static inline uint32_t cp_exp_seg_blocks(uint32_t K) {
+    if (K < CP_EXP_THREAD_K) return 1u;
+    const uint32_t b = nsr_div_up(K, CP_BLOCK);
+    return b < CP_EXP_MAX_SEG_BLOCKS ? b : CP_EXP_MAX_SEG_BLOCKS;
+}
+
+__global__ void __launch_bounds__(CP_BLOCK)
+k_exposure_seg_thread(const float *__restrict__ term, const int32_t *__restrict__ seg_frame, uint32_t F, uint32_t S, uint32_t K,
+                      double *__restrict__ seg_partials) {
+    const uint32_t s = blockIdx.x * CP_BLOCK + threadIdx.x;
+    if (s >= S) return;
+    if ((uint32_t)seg_frame[s] >= F) return;
+    double acc[3] = {0.0, 0.0, 0.0};
+    const float *t = term + (size_t)s * K * 3;
+    for (uint32_t k = 0; k < K; k++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) acc[c] += (double)t[(size_t)k * 3 + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) seg_partials[(size_t)s * 3 + c] = acc[c];
+}
+
+__global__ void __launch_bounds__(CP_BLOCK)
+k_exposure_seg_block(const float *__restrict__ term, const int32_t *__restrict__ seg_frame, uint32_t F, uint32_t K, uint32_t B,
+                     double *__restrict__ seg_partials) {
+    __shared__ double red[3][CP_BLOCK / 64];
+    const uint32_t s = blockIdx.x / B, b = blockIdx.x - s * B;
+    if ((uint32_t)seg_frame[s] >= F) return;                   // the whole block: nobody waits at the barrier
+    double acc[3] = {0.0, 0.0, 0.0};
+    const float *t = term + (size_t)s * K * 3;
+    for (uint32_t k = b * CP_BLOCK + threadIdx.x; k < K; k += B * CP_BLOCK) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) acc[c] += (double)t[(size_t)k * 3 + c];
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) acc[c] += __shfl_xor(acc[c], off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) red[c][threadIdx.x >> 6] = acc[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double sum = 0.0;
+        for (int w = 0; w < CP_BLOCK / 64; w++) sum += red[threadIdx.x][w];
+        seg_partials[(size_t)blockIdx.x * 3 + threadIdx.x] = sum;
+    }
+}
+
+__global__ void __launch_bounds__(64)
+k_exposure_final(const double *__restrict__ seg_partials, const int32_t *__restrict__ seg_frame, uint32_t S, uint32_t B,
+                 float *__restrict__ grad_exposure) {
+    const int32_t f = (int32_t)blockIdx.x;
+    const uint32_t lane = threadIdx.x;
+    double acc = 0.0;
+    for (uint32_t base = 0; base < S; base += 64u) {
+        const uint32_t mine = base + lane;
+        uint64_t named = __ballot(mine < S && seg_frame[mine] == f);
+        while (named) {
+            const uint32_t s = base + (uint32_t)__ffsll((long long)named) - 1u;
+            named &= named - 1u;
+            if (lane < 3u) {
+                double t = 0.0;
+                for (uint32_t b = 0; b < B; b++) t += seg_partials[((size_t)s * B + b) * 3 + lane];
+                acc += t;
+            }
+        }
+    }
+    if (lane < 3u) grad_exposure[(size_t)f * 3 + lane] = (float)(0.6931471805599453 * acc);
+}
+
 // 256 CUs x 8 blocks of 4 waves: the persistent grid of the ray kernels, the cap of the loss grid and with it the loss workspace
 static constexpr uint32_t CP_MAX_BLOCKS = 2048u;
 static uint32_t cp_grid(uint32_t N) {       // fewer blocks when there are fewer rays
@@ -736,6 +879,47 @@ int nsr_recon_loss_weighted(const float *rgb_map, const float *classes, uint32_t
     wa.ray_weight = ray_weight; wa.ray_err = ray_err;
     hipLaunchKernelGGL(k_recon_loss_weighted, dim3(wa.l.nblocks), dim3(CP_BLOCK), 0, (hipStream_t)stream, wa);
     hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, wa.l);
+    return nsr_launch_status();
+}
+
+// the exposure loss's workspace: the loss's block partials, then seg_partials [S][B][3] f64, then term [N,3] f32
+static constexpr uint64_t CP_EXP_WS_SEG = (uint64_t)CP_MAX_BLOCKS * 2 * sizeof(float);
+static_assert(CP_EXP_WS_SEG % 8 == 0, "seg_partials are doubles");
+static uint64_t cp_exp_ws_term(uint32_t S, uint32_t K) {
+    return CP_EXP_WS_SEG + (uint64_t)S * cp_exp_seg_blocks(K) * 3 * sizeof(double);
+}
+
+uint64_t nsr_recon_loss_exposure_workspace_bytes(uint32_t N, uint32_t F, uint32_t S, uint32_t K) {
+    (void)F;
+    return (cp_exp_ws_term(S, K) + (uint64_t)N * 3 * sizeof(float) + 7u) & ~(uint64_t)7u;
+}
+
+int nsr_recon_loss_exposure(const float *rgb_map, const float *classes, uint32_t N, uint32_t nc, const float *target_rgb,
+                            const int64_t *target_cls, const int64_t *pix, const float *ray_weight, const float *exposure, uint32_t F,
+                            const int32_t *seg_frame, uint32_t S, uint32_t K, float ce_lambda, float factor, const float *scale,
+                            float *grad_rgb_map, float *grad_classes, float *grad_exposure, float *ray_err, float *loss_out,
+                            void *workspace, nsr_stream_t stream) {
+    if (N == 0 || F == 0 || S == 0 || K == 0 || (uint64_t)S * K != (uint64_t)N) return NSR_ERR_INVALID_ARG;
+    ELossArgs ea;
+    if (const int e = cp_loss_args(ea.w.l, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
+                                   grad_classes, loss_out, workspace)) return e;
+    NSR_CHECK_PTR(exposure); NSR_CHECK_PTR(seg_frame); NSR_CHECK_PTR(grad_exposure);
+    const uint32_t B = cp_exp_seg_blocks(K);
+    if (((uintptr_t)workspace & 7u) != 0 || F > 0x7fffffffu || (uint64_t)S * B > 0x7fffffffull) return NSR_ERR_INVALID_ARG;
+    double *seg_partials = (double *)((char *)workspace + CP_EXP_WS_SEG);
+    ea.w.ray_weight = ray_weight; ea.w.ray_err = ray_err;
+    ea.exposure = exposure; ea.seg_frame = seg_frame; ea.F = F; ea.K = K;
+    ea.term = (float *)((char *)workspace + cp_exp_ws_term(S, K));
+    hipLaunchKernelGGL(k_recon_loss_exposure, dim3(ea.w.l.nblocks), dim3(CP_BLOCK), 0, (hipStream_t)stream, ea);
+    hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, ea.w.l);
+    if (K < CP_EXP_THREAD_K)
+        hipLaunchKernelGGL(k_exposure_seg_thread, dim3(nsr_div_up(S, CP_BLOCK)), dim3(CP_BLOCK), 0, (hipStream_t)stream,
+                           (const float *)ea.term, seg_frame, F, S, K, seg_partials);
+    else
+        hipLaunchKernelGGL(k_exposure_seg_block, dim3(S * B), dim3(CP_BLOCK), 0, (hipStream_t)stream, (const float *)ea.term, seg_frame, F,
+                           K, B, seg_partials);
+    hipLaunchKernelGGL(k_exposure_final, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double *)seg_partials, seg_frame, S, B,
+                       grad_exposure);
     return nsr_launch_status();
 }
 
