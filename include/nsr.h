@@ -660,6 +660,39 @@ int nsr_generate_rays_frames_backward(const float *poses, uint32_t F, uint32_t w
                                       uint32_t K, const float *grad_rays_o, const float *grad_rays_d, void *workspace,
                                       float *grad_poses, nsr_stream_t stream);
 
+/* Lens refinement: the rays of a mixed-frame batch through a lens that lives in device memory and may change between the
+ * replays of a captured graph.  lens [6] f32 = (fx, fy, cx, cy, k1, k2).  Per ray, with (i, j) the pixel centre and f0..f2 the
+ * camera flip's signs as in nsr_generate_rays, in fp32 without contraction, in this order:
+ *   x  = (i - cx) / fx;  y = (j - cy) / fy
+ *   r2 = x*x + y*y
+ *   s  = 1.0f + r2 * (k1 + r2 * k2)
+ *   c  = ((x*s)*f0, (y*s)*f1, f2)             then R c and the normalisation of nsr_generate_rays
+ * The polynomial radial model applied in the UNPROJECTION direction (pixel to ray): closed form, no iterative undistortion.
+ * k1, k2 are therefore NOT OpenCV's forward (ray to pixel) coefficients.  With k1 = k2 = 0, s is exactly 1 and every row is
+ * bit-identical to nsr_generate_rays_frames with the same fx, fy, cx, cy.  Segments as there: an entry of seg_frame outside
+ * [0, F) gives NaN rows and reads no pose.  A single pose is F = S = 1, K = N with seg_frame = {0}. */
+int nsr_generate_rays_lens(const float *poses, uint32_t F, uint32_t w, uint32_t h, const float *lens, int camera_flip,
+                           const int32_t *seg_frame, const int32_t *pix, uint32_t S, uint32_t K, float *rays_o, float *rays_d,
+                           nsr_stream_t stream);
+
+/* Its backward (same leading arguments).  grad_lens [6] f32 is WRITTEN; grad_poses [F,3,4] f32 is written for every frame
+ * unless it is NULL (only the lens gradient is wanted).  Per ray in fp64, from the f32 inputs: x, y, r2, s and c as above,
+ * v = R c, d = v / |v|, h = (I - d d^T) g_d / |v|; the twelve pose terms are h c^T and g_o as in nsr_generate_rays_backward.
+ * With q = R^T h, gX = q0 f0, gY = q1 f1, m = gX x + gY y, s' = k1 + 2 k2 r2, gx = gX s + 2 m s' x, gy = gY s + 2 m s' y:
+ *   d fx = -gx x / fx   d fy = -gy y / fy   d cx = -gx / fx   d cy = -gy / fy   d k1 = m r2   d k2 = m r2^2
+ * Reduction: the segment-to-block mapping and the order of nsr_generate_rays_frames_backward with eighteen sums per block; the
+ * pose rows per frame over the segments naming it in ascending s, the lens row over every segment naming a frame in [0, F) in
+ * ascending s; fp64 throughout, rounded to fp32 once.  A segment outside [0, F) adds nothing to either result; a frame no
+ * segment names gets exact zeros.  With k1 = k2 = 0 the pose rows are nsr_generate_rays_frames_backward's bit for bit.  No
+ * atomics, no counters, nothing of the workspace is read that this call did not write: two calls and the replays of a
+ * captured graph give the same bits.
+ * workspace: nsr_generate_rays_lens_backward_workspace_bytes(F, S, K) bytes, 8-byte aligned. */
+uint64_t nsr_generate_rays_lens_backward_workspace_bytes(uint32_t F, uint32_t S, uint32_t K);
+int nsr_generate_rays_lens_backward(const float *poses, uint32_t F, uint32_t w, uint32_t h, const float *lens, int camera_flip,
+                                    const int32_t *seg_frame, const int32_t *pix, uint32_t S, uint32_t K,
+                                    const float *grad_rays_o, const float *grad_rays_d, void *workspace, float *grad_poses,
+                                    float *grad_lens, nsr_stream_t stream);
+
 /* Draws a batch on the device: UNIFORM WITH REPLACEMENT (the reference draws without replacement inside one frame; duplicates
  * in a 4 096-of-762 048 draw do not matter to a mean loss).  P = w * h pixels per frame.  Philox4x32-10 keyed by `seed`, with
  * seq = sequence + (sequence_dev ? sequence_dev[0] : 0):

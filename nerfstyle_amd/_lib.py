@@ -115,6 +115,9 @@ SIGNATURES = {
     'nsr_generate_rays_frames': (i32, [vp, u32, u32, u32, f32, f32, f32, f32, i32, vp, vp, u32, u32, vp, vp, vp]),
     'nsr_generate_rays_frames_backward_workspace_bytes': (u64, [u32, u32, u32]),
     'nsr_generate_rays_frames_backward': (i32, [vp, u32, u32, u32, f32, f32, f32, f32, i32, vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    'nsr_generate_rays_lens': (i32, [vp, u32, u32, u32, vp, i32, vp, vp, u32, u32, vp, vp, vp]),
+    'nsr_generate_rays_lens_backward_workspace_bytes': (u64, [u32, u32, u32]),
+    'nsr_generate_rays_lens_backward': (i32, [vp, u32, u32, u32, vp, i32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
     'nsr_draw_frame_batch': (i32, [u32, u32, u32, u32, u64, u32, vp, u32, vp, i32, vp, vp, vp, vp]),
     'nsr_error_map_accumulate': (i32, [u32, u32, u32, u32, vp, vp, vp, u32, u32, vp, vp, vp]),
     'nsr_error_map_rebuild': (i32, [u32, u32, u32, u32, f32, f32, vp, vp, vp, vp, vp, vp]),

@@ -7,11 +7,7 @@
 #include "philox.h"
 #include "ray_pose.h"
 
-#define FB_BLOCK 256
-// k_frames_bwd_block: at most this many blocks per segment (each strides over the segment's rays)
-#define FB_MAX_SEG_BLOCKS 64u
-// below this K a thread owns a whole segment (k_frames_bwd_thread), from it on a segment owns blocks (k_frames_bwd_block)
-#define FB_THREAD_K 64u
+// FB_BLOCK, FB_THREAD_K, FB_MAX_SEG_BLOCKS and fb_seg_blocks, the segments-to-blocks mapping of the backward, are ray_pose.h's
 
 // ---------------------------------------------------------------------------------------------
 // the draw: uniform with replacement
@@ -72,12 +68,6 @@ k_generate_rays_frames(const float *__restrict__ poses, uint32_t F, uint32_t w, 
 // bits from the lowest); for a segment naming the frame, lanes 0..11 add its B partials in order and then that sum to the
 // frame's.  A frame no segment names, and a segment naming no frame, meet no add: exact zeros, and nothing of such a segment is
 // read.  No atomics, no counters; every partial read was written by the launch before, in this call.
-static inline uint32_t fb_seg_blocks(uint32_t K) {
-    if (K < FB_THREAD_K) return 1u;
-    const uint32_t b = nsr_div_up(K, FB_BLOCK);
-    return b < FB_MAX_SEG_BLOCKS ? b : FB_MAX_SEG_BLOCKS;
-}
-
 struct FbCam { uint32_t F, w; float fx, fy, cx, cy; int camera_flip; };
 
 __global__ void __launch_bounds__(FB_BLOCK)
@@ -142,8 +132,6 @@ k_frames_bwd_final(const double *__restrict__ partials, const int32_t *__restric
     }
     if (lane < 12u) grad_poses[(size_t)f * 12 + lane] = (float)acc;
 }
-
-static_assert(FB_BLOCK == RU_BLOCK, "ru_block_sum12 is a tree over RU_BLOCK threads");
 
 // ---------------------------------------------------------------------------------------------
 // C ABI

@@ -1,6 +1,7 @@
-// Per-ray arithmetic of device ray generation and of its backward towards the pose, shared by the single-pose kernels
-// (ray_util.hip) and the mixed-frame ones (frame_batch.hip): one ray from a pose and a pixel id, one ray's twelve fp64 terms of
-// the pose gradient, and the fixed-order block tree over twelve sums.
+// Per-ray arithmetic of device ray generation and of its backward towards the camera, shared by the single-pose kernels
+// (ray_util.hip), the mixed-frame ones (frame_batch.hip) and the lens ones (lens.hip): one ray from a pose and a pixel id, one
+// ray's fp64 terms of the pose gradient (and of the lens gradient), the fixed-order block tree over those sums, and the mapping
+// of a batch's segments to blocks.
 #pragma once
 #include "nsr_common.h"
 
@@ -9,6 +10,19 @@
 struct RuPose { float r00, r01, r02, tx, r10, r11, r12, ty, r20, r21, r22, tz; };
 __device__ __forceinline__ RuPose ru_load_pose(const float *__restrict__ pose) {
     return RuPose{pose[0], pose[1], pose[2], pose[3], pose[4], pose[5], pose[6], pose[7], pose[8], pose[9], pose[10], pose[11]};
+}
+
+// row n from the camera-frame direction (d0, d1, d2): rotated by the pose and normalised (common.py:139-147)
+template <typename Idx>
+__device__ __forceinline__ void ru_write_dir(const RuPose &P, float d0, float d1, float d2, Idx n, float *__restrict__ rays_o,
+                                             float *__restrict__ rays_d) {
+#pragma clang fp contract(off)
+    const float wx = P.r00 * d0 + P.r01 * d1 + P.r02 * d2;
+    const float wy = P.r10 * d0 + P.r11 * d1 + P.r12 * d2;
+    const float wz = P.r20 * d0 + P.r21 * d1 + P.r22 * d2;
+    const float nrm = sqrtf(wx * wx + wy * wy + wz * wz);
+    rays_d[n * 3 + 0] = wx / nrm; rays_d[n * 3 + 1] = wy / nrm; rays_d[n * 3 + 2] = wz / nrm;
+    rays_o[n * 3 + 0] = P.tx; rays_o[n * 3 + 1] = P.ty; rays_o[n * 3 + 2] = P.tz;
 }
 
 // ray n of pixel id p (nerf_lib.py:114-122, common.py:139-147); f0..f2 the camera flip's signs.  Idx: the caller's index type
@@ -20,13 +34,27 @@ __device__ __forceinline__ void ru_write_ray(const RuPose &P, float f0, float f1
     const uint32_t py = p / w, px = p - py * w;
     // np.linspace(0, w, 2w+1)[1::2] == x + 0.5 exactly in fp32 for w < 2^22
     const float i = (float)px + 0.5f, j = (float)py + 0.5f;
-    const float d0 = ((i - cx) / fx) * f0, d1 = ((j - cy) / fy) * f1, d2 = f2;
-    const float wx = P.r00 * d0 + P.r01 * d1 + P.r02 * d2;
-    const float wy = P.r10 * d0 + P.r11 * d1 + P.r12 * d2;
-    const float wz = P.r20 * d0 + P.r21 * d1 + P.r22 * d2;
-    const float nrm = sqrtf(wx * wx + wy * wy + wz * wz);
-    rays_d[n * 3 + 0] = wx / nrm; rays_d[n * 3 + 1] = wy / nrm; rays_d[n * 3 + 2] = wz / nrm;
-    rays_o[n * 3 + 0] = P.tx; rays_o[n * 3 + 1] = P.ty; rays_o[n * 3 + 2] = P.tz;
+    ru_write_dir(P, ((i - cx) / fx) * f0, ((j - cy) / fy) * f1, f2, n, rays_o, rays_d);
+}
+
+// the lens of include/nsr.h ("Lens refinement"): six f32 in device memory
+struct RuLens { float fx, fy, cx, cy, k1, k2; };
+__device__ __forceinline__ RuLens ru_load_lens(const float *__restrict__ lens) {
+    return RuLens{lens[0], lens[1], lens[2], lens[3], lens[4], lens[5]};
+}
+
+// ru_write_ray through the lens: the pinhole coordinates scaled by s = 1 + r2 (k1 + r2 k2).  With k1 = k2 = 0, s is exactly 1 and
+// the row is ru_write_ray's bit for bit.
+template <typename Idx>
+__device__ __forceinline__ void ru_write_ray_lens(const RuPose &P, float f0, float f1, float f2, uint32_t p, uint32_t w, const RuLens &L,
+                                                  Idx n, float *__restrict__ rays_o, float *__restrict__ rays_d) {
+#pragma clang fp contract(off)
+    const uint32_t py = p / w, px = p - py * w;
+    const float i = (float)px + 0.5f, j = (float)py + 0.5f;
+    const float x = (i - L.cx) / L.fx, y = (j - L.cy) / L.fy;
+    const float r2 = x * x + y * y;
+    const float s = 1.0f + r2 * (L.k1 + r2 * L.k2);
+    ru_write_dir(P, (x * s) * f0, (y * s) * f1, f2, n, rays_o, rays_d);
 }
 
 __device__ __forceinline__ void ru_load_rotation(const float *__restrict__ pose, double (&R)[3][3]) {
@@ -37,13 +65,13 @@ __device__ __forceinline__ void ru_load_rotation(const float *__restrict__ pose,
     }
 }
 
-// ray n's terms of the pose gradient, added to acc [3][4] row-major: with c the pixel's camera-frame direction (after the flip),
-// v = R c, d = v / |v|:  acc[:, :3] += ((I - d d^T) g_d[n] / |v|) c^T,  acc[:, 3] += g_o[n]; all in fp64
-__device__ __forceinline__ void ru_pose_term(const double (&R)[3][3], double f0, double f1, double f2, uint32_t p, uint32_t w, float fx,
-                                             float fy, float cx, float cy, const float *__restrict__ g_o, const float *__restrict__ g_d,
-                                             size_t n, double (&acc)[12]) {
-    const uint32_t py = p / w, px = p - py * w;
-    const double c[3] = {(((double)px + 0.5 - (double)cx) / (double)fx) * f0, (((double)py + 0.5 - (double)cy) / (double)fy) * f1, f2};
+// ray n's terms of the pose gradient for the camera-frame direction c (after the flip), added to acc[0..11] ([3][4] row-major):
+// with v = R c, d = v / |v| and h = (I - d d^T) g_d[n] / |v|:  acc[:, :3] += h c^T,  acc[:, 3] += g_o[n]; all in fp64.  h is
+// left for the caller (the gradient towards c is R^T h).
+template <int NA>
+__device__ __forceinline__ void ru_pose_term_dir(const double (&R)[3][3], const double (&c)[3], const float *__restrict__ g_o,
+                                                 const float *__restrict__ g_d, size_t n, double (&acc)[NA], double (&h)[3]) {
+    static_assert(NA >= 12, "twelve pose sums");
     double v[3], gd[3];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
@@ -55,28 +83,77 @@ __device__ __forceinline__ void ru_pose_term(const double (&R)[3][3], double f0,
     const double dg = d[0] * gd[0] + d[1] * gd[1] + d[2] * gd[2];
 #pragma unroll
     for (int r = 0; r < 3; r++) {
-        const double h = (gd[r] - d[r] * dg) * inv;
+        h[r] = (gd[r] - d[r] * dg) * inv;
 #pragma unroll
-        for (int k = 0; k < 3; k++) acc[r * 4 + k] += h * c[k];
+        for (int k = 0; k < 3; k++) acc[r * 4 + k] += h[r] * c[k];
         acc[r * 4 + 3] += (double)g_o[n * 3 + r];
     }
 }
 
-// fixed-order block tree over twelve values: threads 0..11 leave with the block's sum k in v[0]
-__device__ __forceinline__ void ru_block_sum12(double (&v)[12]) {
-    __shared__ double red[12][RU_BLOCK / 64];
+// ray n's terms of the pose gradient, added to acc [3][4] row-major: ru_pose_term_dir with the pinhole direction of pixel id p
+__device__ __forceinline__ void ru_pose_term(const double (&R)[3][3], double f0, double f1, double f2, uint32_t p, uint32_t w, float fx,
+                                             float fy, float cx, float cy, const float *__restrict__ g_o, const float *__restrict__ g_d,
+                                             size_t n, double (&acc)[12]) {
+    const uint32_t py = p / w, px = p - py * w;
+    const double c[3] = {(((double)px + 0.5 - (double)cx) / (double)fx) * f0, (((double)py + 0.5 - (double)cy) / (double)fy) * f1, f2};
+    double h[3];
+    ru_pose_term_dir(R, c, g_o, g_d, n, acc, h);
+}
+
+// ray n's eighteen terms through the lens L = (fx, fy, cx, cy, k1, k2): the twelve of ru_pose_term with the distorted direction
+// in acc[0..11], and in acc[12..17] the gradient towards L in that order (include/nsr.h states the closed form); all in fp64
+__device__ __forceinline__ void ru_lens_term(const double (&R)[3][3], double f0, double f1, double f2, uint32_t p, uint32_t w,
+                                             const double (&L)[6], const float *__restrict__ g_o, const float *__restrict__ g_d, size_t n,
+                                             double (&acc)[18]) {
+    const uint32_t py = p / w, px = p - py * w;
+    const double x = ((double)px + 0.5 - L[2]) / L[0], y = ((double)py + 0.5 - L[3]) / L[1];
+    const double r2 = x * x + y * y;
+    const double s = 1.0 + r2 * (L[4] + r2 * L[5]), ds = L[4] + 2.0 * L[5] * r2;
+    const double c[3] = {(x * s) * f0, (y * s) * f1, f2};
+    double h[3];
+    ru_pose_term_dir(R, c, g_o, g_d, n, acc, h);
+    const double gX = (R[0][0] * h[0] + R[1][0] * h[1] + R[2][0] * h[2]) * f0;
+    const double gY = (R[0][1] * h[0] + R[1][1] * h[1] + R[2][1] * h[2]) * f1;
+    const double m = gX * x + gY * y;
+    const double gx = gX * s + 2.0 * m * ds * x, gy = gY * s + 2.0 * m * ds * y;
+    acc[12] += -gx * x / L[0];
+    acc[13] += -gy * y / L[1];
+    acc[14] += -gx / L[0];
+    acc[15] += -gy / L[1];
+    acc[16] += m * r2;
+    acc[17] += m * r2 * r2;
+}
+
+// fixed-order block tree over NV values: threads 0..NV-1 leave with the block's sum k in v[0]
+template <int NV>
+__device__ __forceinline__ void ru_block_sum(double (&v)[NV]) {
+    __shared__ double red[NV][RU_BLOCK / 64];
     for (int off = 32; off >= 1; off >>= 1) {
 #pragma unroll
-        for (int k = 0; k < 12; k++) v[k] += __shfl_xor(v[k], off, 64);
+        for (int k = 0; k < NV; k++) v[k] += __shfl_xor(v[k], off, 64);
     }
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-        for (int k = 0; k < 12; k++) red[k][threadIdx.x >> 6] = v[k];
+        for (int k = 0; k < NV; k++) red[k][threadIdx.x >> 6] = v[k];
     }
     __syncthreads();
-    if (threadIdx.x < 12) {
+    if (threadIdx.x < NV) {
         double s = 0.0;
         for (int w = 0; w < RU_BLOCK / 64; w++) s += red[threadIdx.x][w];
         v[0] = s;
     }
 }
+__device__ __forceinline__ void ru_block_sum12(double (&v)[12]) { ru_block_sum<12>(v); }
+
+// Segments of a mixed-frame batch to blocks, in every backward that sums per segment (frame_batch.hip, lens.hip): below
+// FB_THREAD_K rays a thread owns a whole segment, from it on a segment owns B = fb_seg_blocks(K) blocks of FB_BLOCK threads,
+// each striding over the segment's rays.
+#define FB_BLOCK 256
+#define FB_MAX_SEG_BLOCKS 64u
+#define FB_THREAD_K 64u
+static inline uint32_t fb_seg_blocks(uint32_t K) {
+    if (K < FB_THREAD_K) return 1u;
+    const uint32_t b = nsr_div_up(K, FB_BLOCK);
+    return b < FB_MAX_SEG_BLOCKS ? b : FB_MAX_SEG_BLOCKS;
+}
+static_assert(FB_BLOCK == RU_BLOCK, "ru_block_sum is a tree over RU_BLOCK threads");

@@ -68,13 +68,17 @@ class _generate_rays_fn(torch.autograd.Function):
 
 
 def generate_rays(pose, intr: Intrinsics, img=None, patch: Optional[Box2D] = None, precrop: float = 1.,
-                  bsize: Optional[int] = None, camera_flip: int = 0, pix_subset=None, device=None, pose_grad: bool = False):
+                  bsize: Optional[int] = None, camera_flip: int = 0, pix_subset=None, device=None, pose_grad: bool = False,
+                  lens=None):
     """Same arguments and returns as the reference (RayBatch, target).  bsize: that many pixels
     drawn without replacement with np.random.choice, exactly like nerf_lib.py:134 (pass
     `pix_subset`, positions into the cropped pixel list, to supply your own / device-side draw).
     img: [C, H, W] tensor -> target [K, C].
     pose_grad (Renderer.pose_gradients): the rays stay attached to a pose tensor that requires grad; by default the pose
-    is a constant, as in the reference."""
+    is a constant, as in the reference.
+    lens ([6] float32 on the device, LensRefiner.forward()): the rays go through that lens instead of intr's four values
+    (nsr_generate_rays_lens with one frame and one segment), and with pose_grad stay attached to it as well."""
+    _check_lens(lens)
     device = device or (pose.device if torch.is_tensor(pose) else None)
     pose_in = pose
     pose = torch.as_tensor(pose, dtype=torch.float32, device=device).contiguous()
@@ -91,7 +95,11 @@ def generate_rays(pose, intr: Intrinsics, img=None, patch: Optional[Box2D] = Non
         if pix_subset is not None:
             ids = ids[pix_subset.long()].contiguous()
     args = (W, H, float(intr.fx), float(intr.fy), float(intr.cx), float(intr.cy), int(camera_flip), ids)
-    if pose_grad and torch.is_tensor(pose_in) and pose_in.requires_grad and torch.is_grad_enabled():
+    if lens is not None:
+        attached = pose_in if torch.is_tensor(pose_in) and pose_in.requires_grad else pose
+        rays_o, rays_d = _rays_lens(attached.to(device=device, dtype=torch.float32)[None], lens, W, H, int(camera_flip),
+                                    torch.zeros(1, dtype=torch.int32, device=device), ids, ids.shape[0], pose_grad)
+    elif pose_grad and torch.is_tensor(pose_in) and pose_in.requires_grad and torch.is_grad_enabled():
         rays_o, rays_d = _generate_rays_fn.apply(pose_in.to(device=device, dtype=torch.float32), *args)
     else:
         rays_o, rays_d = _launch_generate_rays(pose, *args)
@@ -143,24 +151,84 @@ class _generate_rays_frames_fn(torch.autograd.Function):
         return (grad,) + (None,) * 10
 
 
-def generate_rays_frames(poses, seg_frame, pix, K: int, intr: Intrinsics, camera_flip: int = 0, pose_grad: bool = False) -> RayBatch:
+def generate_rays_frames(poses, seg_frame, pix, K: int, intr: Intrinsics, camera_flip: int = 0, pose_grad: bool = False,
+                         lens=None) -> RayBatch:
     """Rays of a mixed-frame batch: poses [F,3,4] (or [F,4,4]), seg_frame [S] int32 and pix [S*K] int32 on the device (what
     ResidentDataset.draw returns); ray n is pixel pix[n] of frame seg_frame[n // K], bit for bit the ray generate_rays makes
     from that frame's pose.  One set of intrinsics for all frames.  A seg_frame entry outside [0, F) gives NaN rays.
     pose_grad (Renderer.pose_gradients): the rays stay attached to a `poses` tensor that requires grad; its gradient is the
-    per-frame sum, zero rows for frames the batch does not name."""
+    per-frame sum, zero rows for frames the batch does not name.
+    lens ([6] float32 on the device, LensRefiner.forward()): one lens for all frames instead of intr's four values
+    (nsr_generate_rays_lens); with pose_grad the rays stay attached to it as well, one autograd node for both gradients."""
+    _check_lens(lens)
     assert poses.dim() == 3 and poses.shape[1] in (3, 4) and poses.shape[2] == 4, 'poses [F,3,4] or [F,4,4]'
     assert seg_frame.dtype == torch.int32 and pix.dtype == torch.int32 and pix.numel() == seg_frame.numel() * K, \
         'seg_frame [S] int32, pix [S*K] int32'
     W, H = intr.size()
     args = (W, H, float(intr.fx), float(intr.fy), float(intr.cx), float(intr.cy), int(camera_flip), seg_frame, pix, int(K))
-    if pose_grad and poses.requires_grad and torch.is_grad_enabled():
+    if lens is not None:
+        rays_o, rays_d = _rays_lens(poses.to(torch.float32), lens, W, H, int(camera_flip), seg_frame, pix, int(K), pose_grad)
+    elif pose_grad and poses.requires_grad and torch.is_grad_enabled():
         rays_o, rays_d = _generate_rays_frames_fn.apply(poses.to(torch.float32), *args)
     else:
         rays_o, rays_d = _launch_generate_rays_frames(poses.detach().to(torch.float32)[:, :3, :].contiguous(), *args)
     rays = RayBatch.__new__(RayBatch)    # directions are already unit length (normalised in-kernel)
     rays.origins, rays.dirs = rays_o, rays_d
     return rays
+
+
+# ---- lens refinement: the same batches through a lens in device memory (nsr_generate_rays_lens) ---------------------------------
+def _check_lens(lens):
+    if lens is not None and not (torch.is_tensor(lens) and tuple(lens.shape) == (6,) and lens.dtype == torch.float32):
+        raise ValueError('lens: a [6] float32 tensor (fx, fy, cx, cy, k1, k2), LensRefiner.forward()')
+
+
+def _launch_generate_rays_lens(poses, lens, W, H, camera_flip, seg_frame, pix, K):
+    F, S = poses.shape[0], seg_frame.shape[0]
+    N = S * K
+    rays_o = torch.empty(N, 3, dtype=torch.float32, device=poses.device)
+    rays_d = torch.empty(N, 3, dtype=torch.float32, device=poses.device)
+    with profiling.timed('generate_rays_lens'):
+        L.check(L.lib().nsr_generate_rays_lens(L.p(poses), F, W, H, L.p(lens), camera_flip, L.p(seg_frame), L.p(pix), S, K, L.p(rays_o),
+                                               L.p(rays_d), L.stream()), 'generate_rays_lens')
+    return rays_o, rays_d
+
+
+class _generate_rays_lens_fn(torch.autograd.Function):
+    """nsr_generate_rays_lens with gradients for the poses and the lens (nsr_generate_rays_lens_backward): poses [F,3,4] or
+    [F,4,4], lens [6] -> (rays_o, rays_d).  The pose gradient is computed only when the poses want one."""
+
+    @staticmethod
+    def forward(ctx, poses, lens, W, H, camera_flip, seg_frame, pix, K):
+        flat, lens = poses.detach()[:, :3, :].contiguous(), lens.detach().contiguous()
+        ctx.save_for_backward(flat, lens, seg_frame, pix)
+        ctx.size, ctx.flip, ctx.K, ctx.rows = (W, H), camera_flip, K, poses.shape[1]
+        return _launch_generate_rays_lens(flat, lens, W, H, camera_flip, seg_frame, pix, K)
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        poses, lens, seg_frame, pix = ctx.saved_tensors
+        F, S, K, dev = poses.shape[0], seg_frame.shape[0], ctx.K, poses.device
+        g_o, g_d = g_o.to(torch.float32).contiguous(), g_d.to(torch.float32).contiguous()
+        ws = torch.empty(int(L.lib().nsr_generate_rays_lens_backward_workspace_bytes(F, S, K)) // 8, dtype=torch.float64, device=dev)
+        grad = torch.empty(F, 3, 4, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        grad_lens = torch.empty(6, dtype=torch.float32, device=dev)
+        with profiling.timed('generate_rays_lens_bwd'):
+            L.check(L.lib().nsr_generate_rays_lens_backward(L.p(poses), F, *ctx.size, L.p(lens), ctx.flip, L.p(seg_frame), L.p(pix), S, K,
+                                                            L.p(g_o), L.p(g_d), L.p(ws), L.p(grad), L.p(grad_lens), L.stream()),
+                    'generate_rays_lens_backward')
+        if grad is not None and ctx.rows == 4:   # [F,4,4] poses: their last rows never reach the rays
+            grad = torch.cat((grad, torch.zeros(F, 1, 4, dtype=torch.float32, device=dev)), dim=1)
+        return (grad, grad_lens if ctx.needs_input_grad[1] else None) + (None,) * 6
+
+
+def _rays_lens(poses, lens, W, H, camera_flip, seg_frame, pix, K, pose_grad):
+    """poses [F,3,4] or [F,4,4] float32 -> (rays_o, rays_d), attached to poses and lens when pose_grad is set and one of them
+    requires grad"""
+    if pose_grad and torch.is_grad_enabled() and (poses.requires_grad or lens.requires_grad):
+        return _generate_rays_lens_fn.apply(poses, lens, W, H, camera_flip, seg_frame, pix, K)
+    return _launch_generate_rays_lens(poses.detach()[:, :3, :].contiguous(), lens.detach().contiguous(), W, H, camera_flip, seg_frame,
+                                      pix, K)
 
 
 def tile_order(w: int, h: int, tile_w: int = 8, tile_h: int = 8, device=None) -> torch.Tensor:

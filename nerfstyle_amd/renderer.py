@@ -588,13 +588,16 @@ class Renderer(torch.nn.Module):
         return out
 
     def render(self, pose, image=None, patch: Optional[Box2D] = None, num_rays: Optional[int] = None,
-               training: bool = False, pix_subset=None, dense: Optional[bool] = None) -> Dict[str, torch.Tensor]:
-        """renderer.py:295-313.  `dense` overrides the guess below for callers that pass a patch as `pix_subset`."""
+               training: bool = False, pix_subset=None, dense: Optional[bool] = None, lens=None) -> Dict[str, torch.Tensor]:
+        """renderer.py:295-313.  `dense` overrides the guess below for callers that pass a patch as `pix_subset`.
+        lens ([6], LensRefiner.forward()): the rays go through that lens instead of the fixed intrinsics; in a training render it
+        is a camera tensor like the pose (`pose_gradients`, the same refusals), a test render uses it without a gradient."""
         output = {}
         precrop_frac = self.precrop_frac if self._use_precrop else 1.
+        self._refuse_lens(lens)
         rays, output['target'] = generate_rays(pose, self.intr, image, patch=patch, precrop=precrop_frac, bsize=num_rays,
-                                               camera_flip=self.cfg.flip_camera, pix_subset=pix_subset,
-                                               device=self.device, pose_grad=training and self._pose_grad_wanted(pose))
+                                               camera_flip=self.cfg.flip_camera, pix_subset=pix_subset, device=self.device,
+                                               pose_grad=training and self._pose_grad_wanted(pose, lens), lens=lens)
         render_fn = self.render_train if training else self.render_test
         # a full frame, a patch or a centre crop is a dense pixel set: neighbouring rays share hash-table rows
         if dense is None:
@@ -610,17 +613,24 @@ class Renderer(torch.nn.Module):
         output.update(geometry or {})
         return output
 
-    def render_frames(self, poses, batch, training: bool = True) -> Dict[str, torch.Tensor]:
+    def _refuse_lens(self, lens):
+        if lens is not None and self.cfg.use_ndc:
+            raise NotImplementedError('lens: use_ndc: the NDC warp reads the focal length of the fixed intrinsics, not the lens')
+
+    def render_frames(self, poses, batch, training: bool = True, lens=None) -> Dict[str, torch.Tensor]:
         """A training render of a mixed-frame batch: poses [F,3,4] (PoseRefiner.forward_all(), or the dataset's), batch =
         ResidentDataset.draw(...) (seg_frame, pix, rows, S, K): ray n is pixel pix[n] of frame seg_frame[n // K].  The output
         dict of render(); 'target' is None -- the caller has batch.rows for recon_loss(..., pix=batch.rows).  From the rays on
         it IS render_train: occupancy updates, geometry_terms, the sample order and, with `pose_gradients` and poses that
         require grad, the camera gradient (one row of poses.grad per frame, zeros for frames outside the batch) with every
-        refusal of the single-pose path.  Training only; begin_train / GraphedRenderStep have no mixed-frame form."""
+        refusal of the single-pose path.  Training only; begin_train / GraphedRenderStep have no mixed-frame form.
+        lens ([6], LensRefiner.forward()): one lens for all frames, a camera tensor like the poses; lens.grad arrives with
+        poses.grad from one backward launch sequence."""
         if not training:
             raise NotImplementedError('render_frames is a training render: an image has one pose, use render(pose)')
+        self._refuse_lens(lens)
         rays = generate_rays_frames(poses, batch.seg_frame, batch.pix, batch.K, self.intr, camera_flip=self.cfg.flip_camera,
-                                    pose_grad=self._pose_grad_wanted(poses))
+                                    pose_grad=self._pose_grad_wanted(poses, lens), lens=lens)
         output = {'target': None}
         geometry = {} if self.geometry_terms else None
         extra = {} if geometry is None else {'geometry': geometry}
