@@ -27,7 +27,10 @@ struct AdamArgs {
 enum { SC_SCALE = 0, SC_TRACKER = 1, SC_FOUND = 2, SC_STEP = 3, SC_SKIPPED = 4, SC_EMA_N = 5, SC_SKIP = 8, SC_STEP_SIZE = 9,
        SC_INV_BC2 = 10, SC_INV_SCALE = 11, SC_LR = 12, SC_EMA_DECAY = 13 };
 
+// No FMA contraction in adam_one / ema_move: left to the compiler, k_adam and k_lanes_adam fused different products of
+// b1 * m + (1 - b1) * g, and the two kernels differed in the last bits where the addends cancel.
 __device__ __forceinline__ float adam_one(float &p, float g, float &m, float &v, const AdamScalars &a) {
+#pragma clang fp contract(off)
     g *= a.grad_scale_inv;
     m = a.beta1 * m + (1.0f - a.beta1) * g;          // torch: exp_avg.lerp_(grad, 1 - beta1)
     v = a.beta2 * v + (1.0f - a.beta2) * g * g;      // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
@@ -47,7 +50,10 @@ __device__ __forceinline__ bool adam_scalars(AdamScalars &a) {
 }
 
 // torch_ema: shadow.sub_((1 - decay) * (shadow - param)), k = 1 - decay
-__device__ __forceinline__ void ema_move(float &e, float p, float k) { e -= k * (e - p); }
+__device__ __forceinline__ void ema_move(float &e, float p, float k) {
+#pragma clang fp contract(off)
+    e -= k * (e - p);
+}
 
 __device__ __forceinline__ void ema_move(float *ema, uint64_t i, const float4 &p, float decay) {
     float4 e = reinterpret_cast<float4 *>(ema)[i];
@@ -350,6 +356,7 @@ extern "C" int nsr_lanes_adam(float *arena, void *half_copy, const float *grad, 
 extern "C" int nsr_lanes_adam_scaled(float *arena, void *half_copy, const float *grad, float *exp_avg, float *exp_avg_sq,
                                      float *ema, float *packed_out, uint64_t row_lo, uint64_t row_hi, uint32_t lane_mask,
                                      float beta1, float beta2, float eps, const void *scaler_state, nsr_stream_t stream) {
+    if (row_hi == row_lo) return NSR_OK;             // an empty shard is a no-op, as in nsr_lanes_adam and nsr_adam_step_scaled
     NSR_CHECK_PTR(scaler_state);
     if ((uintptr_t)scaler_state & 3u) return NSR_ERR_INVALID_ARG;
     return lanes_adam_launch(arena, half_copy, grad, exp_avg, exp_avg_sq, ema, packed_out, row_lo, row_hi, lane_mask,
