@@ -591,7 +591,8 @@ int nsr_lanes_unpack(const float *packed, uint64_t row_lo, uint64_t row_hi, uint
  * `nonzero(density_grid > 0)`).  One update = nsr_occ_sample_points -> nsr_field_forward (sigma only,
  * rgbs = NULL, on the returned positions) -> nsr_occ_update.  Nothing is read on the host; every call is
  * capture-safe.  Cells are flat indices cas * H^3 + morton(x, y, z): the layout of density_grid [C, H^3]
- * (renderer.py:62-63).  H^3 must be a multiple of 256, C <= 8.
+ * (renderer.py:62-63).  H must be a power of two in 8..512 (a Morton index is below H^3 only then), C <= 8 and
+ * C * H^3 < 2^31; any other shape is refused (0 bytes / 0 points / NSR_ERR_INVALID_ARG).
  * ------------------------------------------------------------------------------------------ */
 /* device scratch for both calls (the same buffer must be passed to both calls of one update) */
 uint64_t nsr_occ_workspace_bytes(uint32_t C, uint32_t H);

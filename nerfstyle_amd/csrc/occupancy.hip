@@ -237,9 +237,10 @@ static OccLayout occ_layout(uint32_t C, uint32_t H) {
     return l;
 }
 static bool occ_dims_ok(uint32_t C, uint32_t H) {
-    // H^3 a multiple of the block size (and of 8 for packbits); cells fit int32 flat indices
-    return C >= 1 && C <= 8 && H >= 8 && H <= 512 && ((uint64_t)H * H * H) % OCC_BLOCK == 0 &&
-           (uint64_t)C * H * H * H < (1ull << 31);
+    // H a power of two: cells are addressed by Morton index, which stays below H^3 only then (at H = 24,
+    // morton(23, 23, 23) = 29183 >= 13824).  H^3 is then a multiple of the block size (and of 8 for packbits) from H = 8 on;
+    // cells fit int32 flat indices
+    return C >= 1 && C <= 8 && H >= 8 && H <= 512 && (H & (H - 1u)) == 0u && (uint64_t)C * H * H * H < (1ull << 31);
 }
 
 extern "C" {

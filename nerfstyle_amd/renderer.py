@@ -168,7 +168,7 @@ class Renderer(torch.nn.Module):
             dev = self.device
             nbytes = int(L.lib().nsr_occ_workspace_bytes(self.cascade, self.cfg.grid_size))
             if nbytes == 0:
-                raise RuntimeError('occupancy grid of size {} x {}^3 is not supported (H^3 must be a multiple of 256)'.format(
+                raise RuntimeError('occupancy grid of size {} x {}^3 is not supported (H a power of two, 8..512)'.format(
                     self.cascade, self.cfg.grid_size))
             self._occ_ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
             self._occ_xyzs = torch.empty(P, 3, dtype=torch.float32, device=dev)
