@@ -615,6 +615,45 @@ int nsr_occ_update(float *density_grid, const float *sigmas, const int32_t *indi
                    uint32_t H, int full_update, float density_decay, float density_thresh, uint8_t *bitfield,
                    float *mean_density, uint32_t *sequence_dev, void *workspace, nsr_stream_t stream);
 
+/* Untrained cells: marks every cell that fewer than min_views of the F training cameras see with density_grid = -1, the
+ * state nsr_occ_update never leaves (its valid mask is grid >= 0) and the occupied-cell list never names, and clears the
+ * cell's bit in `bitfield` (optional; the other bits of the byte are kept).  torch-ngp's mark_untrained_grid /
+ * instant-ngp's mark_untrained_density_grid; the reference has the state but no producer.
+ *
+ * poses [F,3,4] f32 row-major (device), [R | t] with R taken as ORTHONORMAL (camera to world, as nsr_generate_rays_frames
+ * reads them); camera_flip as there.  The frustum is x_lo <= x' / z' <= x_hi, y_lo <= y' / z' <= y_hi in the pinhole
+ * coordinates of the frame's outer pixel edges ((0 - cx) / fx .. (w - cx) / fx, likewise y); no near or far limit.
+ *
+ * Geometry, all fp64, no contraction, every operation an IEEE + - x (sqrt on the host) in this order:
+ *   cell cas * H^3 + morton(ix, iy, iz):  b = min(2^cas, (double)bound), half = b / H,
+ *     centre X_a = b (2 i_a + 1 - H) / H  (the centre of the march's cell and of the update's),
+ *     rho = (margin_cells * half) * sqrt(3.0);
+ *   frame [R | t] (f32 widened):  d = X - t,  q_k = (R[0][k] d_0 + R[1][k] d_1) + R[2][k] d_2  (q = R^T (X - t)),
+ *     x' = q_0 f0, y' = q_1 f1, z' = q_2 f2 with f0, f1, f2 = +-1 from camera_flip bits 2, 1, 0: the inverse of the ray
+ *     direction R (x f0, y f1, f2) of nsr_generate_rays;
+ *   the frame SEES the cell iff   z' + rho > 0
+ *                            and  x' - x_hi z' <= rho sqrt(1 + x_hi^2)   and  x_lo z' - x' <= rho sqrt(1 + x_lo^2)
+ *                            and  y' - y_hi z' <= rho sqrt(1 + y_hi^2)   and  y_lo z' - y' <= rho sqrt(1 + y_lo^2),
+ *   i.e. the sphere of radius rho around the centre reaches into every half-space of the frustum.
+ * Conservative: with margin_cells = 1, rho is the cell's half-diagonal, so every point of the cell lies within rho of the
+ * centre; R is orthonormal, so q = R^T (X - t) keeps distances; a point of the cell inside the frustum lies inside every
+ * half-space, and the centre is then at most rho outside each (the right-hand sides divide by the normals' lengths).  So a
+ * cell with any point inside a frustum is seen; cells near a frustum's edges or corners may be seen without touching it.
+ *
+ * count = the number of frames that see the cell (all F are counted); counts [C*H^3] i32 (optional) receives it.
+ *   count <  min_views: grid = -1.0f, bit cleared;
+ *   count >= min_views: a grid value < 0 becomes 0.0f (a cell the cameras now see is trainable again), every other value
+ *     keeps its bits (NaN and -0.0f included) and the bit is kept.
+ * A second call with the same arguments changes nothing.  n_untrained [C] u32 (optional) is WRITTEN with the number of
+ * cells per cascade this call left at -1 (zeroed by a kernel of the call, then integer atomics of block sums: the same
+ * value on every run).  Reads nothing on the host, uses no workspace, capture-safe.  Shapes as for every nsr_occ_* call;
+ * also refused (NSR_ERR_INVALID_ARG): F == 0, min_views == 0, margin_cells < 0 or NaN, x_lo >= x_hi, y_lo >= y_hi or a
+ * frustum bound that is not finite, density_grid or counts not 16-byte aligned. */
+int nsr_occ_mark_untrained(float *density_grid, uint8_t *bitfield, uint32_t C, uint32_t H, float bound, const float *poses,
+                           uint32_t F, double x_lo, double x_hi, double y_lo, double y_hi, int camera_flip,
+                           double margin_cells, uint32_t min_views, int32_t *counts, uint32_t *n_untrained,
+                           nsr_stream_t stream);
+
 /* Ray generation on the device (nerf_lib.py:69-142 + common.py:139-147): pixel centres
  * (x + 0.5), camera-frame direction ((i-cx)/fx, (j-cy)/fy, 1) * flip, R * d, normalise.
  * pose [4,4] f32 row-major (device).  pix [N] i32 1-D pixel ids (row-major, y * w + x) or NULL

@@ -107,6 +107,7 @@ SIGNATURES = {
     'nsr_occ_num_points': (u32, [u32, u32, i32]),
     'nsr_occ_sample_points': (i32, [vp, u32, u32, f32, i32, u64, u32, vp, vp, vp, vp, vp, vp]),
     'nsr_occ_update': (i32, [vp, vp, vp, u32, u32, u32, i32, f32, f32, vp, vp, vp, vp, vp]),
+    'nsr_occ_mark_untrained': (i32, [vp, vp, u32, u32, f32, vp, u32, f64, f64, f64, f64, i32, f64, u32, vp, vp, vp]),
     'nsr_generate_rays': (i32, [vp, u32, u32, f32, f32, f32, f32, i32, vp, u32, vp, vp, vp]),
     'nsr_field_position_gradient': (i32, [ctypes.POINTER(FieldDesc), vp, vp, u32, vp, vp, vp, vp, vp]),
     'nsr_rays_position_backward': (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),

@@ -80,6 +80,37 @@ def packbits(grid, thresh, bitfield=None):
     return bitfield
 
 
+def mark_untrained_grid(density_grid, bitfield, poses, frustum, camera_flip, bound, cascade, grid_size, margin_cells, min_views,
+                        counts=None):
+    """nsr_occ_mark_untrained (no reference counterpart; torch-ngp's mark_untrained_grid): cells that fewer than `min_views` of
+    the cameras see get density_grid = -1 and a cleared bit, in place; cells seen again that held a negative value get 0.
+    density_grid [C, H^3] float32 and bitfield uint8 [C*H^3/8] (or None) are written in place and must be contiguous device
+    tensors; poses [F,3,4] float32 on the device; frustum = (x_lo, x_hi, y_lo, y_hi) host floats, the pinhole coordinates of the
+    frame's outer edges; counts (optional int32 [C*H^3]) receives the number of frames that see each cell.
+    Returns n_untrained, int32 [C] on the device: the cells per cascade left at -1.  No host read."""
+    if density_grid.dtype != torch.float32 or (bitfield is not None and bitfield.dtype != torch.uint8):
+        raise ValueError('mark_untrained_grid: density_grid float32, bitfield uint8')
+    L.p(density_grid)            # a CPU tensor raises before anything is allocated
+    if int(min_views) < 1:
+        raise ValueError('mark_untrained_grid: min_views >= 1')
+    C, H = int(cascade), int(grid_size)
+    cells = C * H ** 3
+    poses = poses.detach().to(torch.float32)
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4):
+        raise ValueError('mark_untrained_grid: poses [F,3,4]')
+    poses = poses.contiguous()
+    if density_grid.numel() != cells or (bitfield is not None and bitfield.numel() != cells // 8) or \
+            (counts is not None and (counts.numel() != cells or counts.dtype != torch.int32)):
+        raise ValueError('mark_untrained_grid: density_grid [C, H^3], bitfield [C*H^3/8], counts int32 [C*H^3]')
+    n_untrained = torch.empty(C, dtype=torch.int32, device=density_grid.device)
+    x_lo, x_hi, y_lo, y_hi = (float(v) for v in frustum)
+    with profiling.timed('mark_untrained'):
+        L.check(L.lib().nsr_occ_mark_untrained(
+            L.p(density_grid), L.p(bitfield), C, H, float(bound), L.p(poses), poses.shape[0], x_lo, x_hi, y_lo, y_hi,
+            int(camera_flip), float(margin_cells), int(min_views), L.p(counts), L.p(n_untrained), L.stream()), 'occ_mark_untrained')
+    return n_untrained
+
+
 def _march_workspace(N, device, bound, max_steps):
     nbytes = int(L.lib().nsr_march_rays_train_workspace_bytes(N, float(bound), int(max_steps)))
     return torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=device)

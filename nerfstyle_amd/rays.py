@@ -231,6 +231,23 @@ def _rays_lens(poses, lens, W, H, camera_flip, seg_frame, pix, K, pose_grad):
                                       pix, K)
 
 
+def frustum_bounds(w: int, h: int, fx, fy, cx, cy, k1=0.0, k2=0.0):
+    """(x_lo, x_hi, y_lo, y_hi), host floats computed in fp64: the rectangle in pinhole coordinates that holds every ray of a
+    w x h frame, for the frustum test of raymarching.mark_untrained_grid.  Pinhole: the frame's outer pixel edges,
+    (0 - cx) / fx .. (w - cx) / fx and likewise y.  With a radial term the bounding rectangle of (x s, y s),
+    s = 1 + r2 (k1 + r2 k2) (the lens of nsr_generate_rays_lens), over the four corners of every border pixel; with
+    k1 = k2 = 0 exactly the pinhole rectangle."""
+    fx, fy, cx, cy, k1, k2 = (np.float64(v) for v in (fx, fy, cx, cy, k1, k2))
+    if k1 == 0 and k2 == 0:
+        return float((0 - cx) / fx), float((w - cx) / fx), float((0 - cy) / fy), float((h - cy) / fy)
+    u, v = np.meshgrid(np.arange(w + 1, dtype=np.float64), np.arange(h + 1, dtype=np.float64))
+    border = (u <= 1) | (u >= w - 1) | (v <= 1) | (v >= h - 1)
+    x, y = (u[border] - cx) / fx, (v[border] - cy) / fy
+    r2 = x * x + y * y
+    s = 1 + r2 * (k1 + r2 * k2)
+    return float((x * s).min()), float((x * s).max()), float((y * s).min()), float((y * s).max())
+
+
 def tile_order(w: int, h: int, tile_w: int = 8, tile_h: int = 8, device=None) -> torch.Tensor:
     """Every pixel id of a w x h frame once, visited tile by tile (tile_w x tile_h pixels, row-major inside a tile and over the
     tiles; edge tiles are partial).  For batches that cover the whole frame: `np.random.choice(w * h, w * h, replace=False)`

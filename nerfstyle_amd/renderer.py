@@ -202,6 +202,42 @@ class Renderer(torch.nn.Module):
                                        L.p(ws), L.stream()), 'occ_update')
         self._mean_count_stale = True
 
+    @torch.no_grad()
+    def mark_untrained_grid(self, poses, lens=None, margin_cells: float = 1.5, min_views: int = 1, return_counts: bool = False):
+        """Marks the occupancy cells that fewer than `min_views` of the training cameras see as untrained: density_grid = -1,
+        which update_state never changes and never lists as occupied, and a cleared bit in density_bitfield (torch-ngp's
+        mark_untrained_grid; raymarching.mark_untrained_grid states the test).  Opt-in: a trainer calls it once after loading
+        the dataset; nothing calls it otherwise.  The marks are part of density_grid and so of state_dict().
+        poses: [F,3,4] or [F,4,4], a tensor or NumPy, the poses generate_rays takes (all training frames, one set of intrinsics).
+        The frustum is the outer pixel edges of `self.intr`, computed on the host in fp64; with lens ([6], LensRefiner.forward())
+        that lens instead, read back ONCE here -- a setup call that synchronises, not for use inside a captured step -- and with
+        k1, k2 the bounding rectangle of the distorted border (rays.frustum_bounds).
+        margin_cells: a cell counts as seen when the sphere of margin_cells half-diagonals around its centre reaches into the
+        frustum.  1 is already conservative for exact positions; the default of 1.5 also covers the fp32 rounding of the march's
+        own cell index and small pose corrections.  With a PoseRefiner raise it, or call again with the refined poses: a call
+        re-opens (sets to 0) marked cells that are now seen and leaves learnt densities alone.
+        It works on density_grid / density_bitfield, never on a pinned bitfield, and is deterministic: ranks that call it with the
+        same poses hold the same grid.  Returns n_untrained (int32 [cascade] on the device), with return_counts also the number
+        of frames that see each cell (int32 [cascade, H^3])."""
+        if self.cfg.use_ndc:
+            raise NotImplementedError('mark_untrained_grid: use_ndc: the frustum test is in world space, NDC rays are warped')
+        from .rays import _check_lens, frustum_bounds
+        _check_lens(lens)
+        poses = torch.as_tensor(poses, dtype=torch.float32, device=self.device)
+        if poses.dim() != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
+            raise ValueError('mark_untrained_grid: poses [F,3,4] or [F,4,4]')
+        w, h = self.intr.size()
+        cam = (self.intr.fx, self.intr.fy, self.intr.cx, self.intr.cy)
+        if lens is not None:
+            cam = tuple(lens.detach().cpu().tolist())        # the one host read
+        C, H = self.cascade, self.cfg.grid_size
+        if not self.density_grid.is_contiguous():
+            self.density_grid = self.density_grid.contiguous()
+        counts = torch.empty(C, H ** 3, dtype=torch.int32, device=self.device) if return_counts else None
+        n_untrained = raymarching.mark_untrained_grid(self.density_grid, self.density_bitfield, poses[:, :3, :], frustum_bounds(w, h, *cam),
+                                                      self.cfg.flip_camera, self.bound, C, H, margin_cells, min_views, counts=counts)
+        return (n_untrained, counts) if return_counts else n_untrained
+
     def pin_march_bitfield(self, bitfield: Optional[torch.Tensor]):
         """Benchmark / debugging hook: march through THIS bitfield while update_state keeps maintaining density_grid,
         mean_density and density_bitfield from the model as usual (None: back to density_bitfield).  Synthetic
