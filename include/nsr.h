@@ -85,6 +85,8 @@ int nsr_packbits(const float *grid, uint32_t N, float density_thresh, uint8_t *b
  * counter [2] i32, noises [N] f32 or NULL (= zeros: perturb is force-disabled,
  * raymarching.py:247), z_hats [N] or NULL when !is_ndc.
  * Rays with offset+count >= M are dropped like the reference does (raymarching.cu:517).
+ * grid: the bitfield of C cascades of H^3 cells, C * H^3 / 8 bytes.  H must be a power of two in 8..512 (a Morton index is
+ * below H^3 only then: any other H would be read past the bitfield) and C <= 8; anything else -> NSR_ERR_INVALID_ARG.
  * workspace: nsr_march_rays_train_workspace_bytes(N, bound, max_steps) bytes of device scratch (per-ray counts, block sums
  * and, for batches marched one thread per ray, a bit mask of bound * max_steps step indices per ray: the counting pass marks
  * the samples, the emitting pass replays the t sequence without probing the grid again; batches marched one wave per ray
@@ -243,7 +245,8 @@ uint64_t nsr_matting_laplacian_workspace_bytes(uint32_t H, uint32_t W, uint32_t 
 int nsr_matting_laplacian(const float *target, const float *v, uint32_t H, uint32_t W, uint32_t win_rad, double eps,
                           double *loss_out, float *grad_v, void *workspace, nsr_stream_t stream);
 
-/* replaces march_rays (raymarching.h:17, raymarching.cu:1004-1130), inference. */
+/* replaces march_rays (raymarching.h:17, raymarching.cu:1004-1130), inference.  noises [n_alive] f32 or NULL (= zeros).
+ * C, H as for nsr_march_rays_train: H a power of two in 8..512, C <= 8, else NSR_ERR_INVALID_ARG. */
 int nsr_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t,
                    const float *rays_o, const float *rays_d, const float *z_hats, float bound,
                    float dt_gamma, uint32_t max_steps, int is_ndc, uint32_t C, uint32_t H,
@@ -482,7 +485,8 @@ int nsr_sample_order(const float *xyzs, uint32_t M, const int32_t *m_dev, uint32
  * order: optional device [N] u32, the ray handled k-th (a permutation of 0..N-1; NULL = identity) -- outputs always land in
  * the ray's own row.  weights_sum [N], depth [N], image [N, 3 + desc->num_classes] f32 are written, not accumulated; rays
  * that miss the box (near == far == FLT_MAX) or meet no occupied cell get zeros.  stats: optional device u32[2] that is
- * ACCUMULATED into: {samples shaded, rays finished}.  C, H: cascades and resolution of `grid` (nsr_march_rays_train's).
+ * ACCUMULATED into: {samples shaded, rays finished}.  C, H: cascades and resolution of `grid` (nsr_march_rays_train's; H that
+ * is no power of two in 8..512 -> NSR_ERR_INVALID_ARG).
  * No workspace, no host read, capture-safe.  is_ndc != 0, C > 16 or num_classes > 13 -> NSR_ERR_UNSUPPORTED. */
 int nsr_render_rays_infer(const nsr_field_desc *desc, const void *tables, const float *mlp_params, const float *rays_o,
                           const float *rays_d, const uint32_t *order, uint32_t N, const float *nears, const float *fars,

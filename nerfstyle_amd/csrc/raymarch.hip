@@ -68,12 +68,17 @@ __device__ __forceinline__ bool rm_wave_ray_begin(uint32_t n, uint32_t lane, uin
     return true;
 }
 
-// Constant step (LLFF: dt_gamma = 0): t_{j+1} = fl(t_j + dt).  Inside one binade every t_j is a multiple of the
-// binade's ulp u, so the rounded sum advances the BIT PATTERN by a constant c = dt / u rounded to an integer (ties
-// to even make the very first step the only possible exception: after it the mantissa parity repeats).  Two real
-// additions give t_1 and t_2, c = bits(t_2) - bits(t_1), and t_j = bits(t_1) + (j - 1) c for j = 1..span -- the same
-// floats as `span` serial additions, as long as t_1 .. t_span share an exponent.  Returns whether that holds for the
-// sequence that starts at t, with b1 = bits(t_1) and cc = c; otherwise the caller adds serially.
+// Constant step (LLFF: dt_gamma = 0): t_{j+1} = fl(t_j + dt).  Inside one binade every t_j is an integer multiple m_j of the
+// binade's ulp u, and with f = dt / u the rounded sum is m_{j+1} = rne(m_j + f).  When the fractional part of f is not 1/2
+// that is m_j + rne(f) for every integer m_j: a constant advance of the BIT PATTERN.  When it is exactly 1/2, every sum is a
+// tie and goes to the EVEN neighbour: m_{j+1} is even whatever m_j was, and from an even m_j the advance is the even one of
+// floor(f), floor(f) + 1 -- constant again, but only from the first even m_j on.  So the advance t_1 -> t_2 is the advance of
+// every later step PROVIDED t_1 is itself the rounded result of an addition in this binade, i.e. t_0 is a multiple of u too:
+// t_0 .. t_span must share an exponent, t_0 included.  (A t_0 in the binade below is a multiple of u / 2 only; t_0 + dt can
+// then be an ODD multiple of u with no rounding at all, and t_1 -> t_2 rounds the other way from t_2 -> t_3: at max_steps =
+// 257, t_0 = 0x407ff003 the sums go +0x6e6b, +0x6e6c, +0x6e6c, ...)  Two real additions give t_1 and t_2, c = bits(t_2) -
+// bits(t_1), and t_j = bits(t_1) + (j - 1) c for j = 1..span -- the same floats as `span` serial additions.  Returns whether
+// that holds for the sequence that starts at t, with b1 = bits(t_1) and cc = c; otherwise the caller adds serially.
 __device__ __forceinline__ bool rm_const_step(const RmCfg &c, float t, uint32_t span, uint32_t &b1, uint32_t &cc) {
     bool closed = false;
     b1 = 0; cc = 0;
@@ -85,7 +90,8 @@ __device__ __forceinline__ bool rm_const_step(const RmCfg &c, float t, uint32_t 
         const uint32_t b2 = __float_as_uint(t2);
         cc = b2 - b1;
         const uint32_t b_last = b1 + (span - 1u) * cc;
-        closed = b2 > b1 && (b1 >> 23) == (b_last >> 23) && cc < (1u << 23);
+        // (bits(t) <= b1 <= b_last: with the ends in one binade, t_1 is in it too)
+        closed = b2 > b1 && (__float_as_uint(t) >> 23) == (b_last >> 23) && cc < (1u << 23);
     }
     return closed;
 }
@@ -528,7 +534,7 @@ int nsr_march_rays_train(const float *rays_o, const float *rays_d, const float *
     NSR_CHECK_PTR(rays_o); NSR_CHECK_PTR(rays_d); NSR_CHECK_PTR(grid); NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars);
     NSR_CHECK_PTR(xyzs); NSR_CHECK_PTR(deltas); NSR_CHECK_PTR(rays); NSR_CHECK_PTR(counter); NSR_CHECK_PTR(workspace);
     if (is_ndc && z_hats == nullptr) return NSR_ERR_INVALID_ARG;
-    if (max_steps == 0 || C == 0 || C > 8 || H == 0 || H > 1024) return NSR_ERR_INVALID_ARG;
+    if (max_steps == 0 || C == 0 || C > 8 || !rm_grid_size_ok(H)) return NSR_ERR_INVALID_ARG;
     if (((uintptr_t)deltas & 15u) != 0) return NSR_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t nblocks = (N + RM_BLOCK - 1) / RM_BLOCK;

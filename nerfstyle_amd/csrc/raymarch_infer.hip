@@ -203,7 +203,7 @@ int nsr_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive,
     NSR_CHECK_PTR(fars); NSR_CHECK_PTR(xyzs); NSR_CHECK_PTR(deltas);
     (void)nears;
     if (is_ndc && z_hats == nullptr) return NSR_ERR_INVALID_ARG;
-    if (max_steps == 0 || C == 0 || C > 8 || H == 0 || H > 1024) return NSR_ERR_INVALID_ARG;
+    if (max_steps == 0 || C == 0 || C > 8 || !rm_grid_size_ok(H)) return NSR_ERR_INVALID_ARG;
     hipLaunchKernelGGL(k_march_rays, dim3(nsr_div_up(n_alive, RM_BLOCK)), dim3(RM_BLOCK), 0, (hipStream_t)stream, n_alive,
                        n_step, rays_alive, rays_t, rays_o, rays_d, z_hats, bound, dt_gamma, max_steps, is_ndc, C, H, grid, fars,
                        xyzs, dirs, deltas, noises);

@@ -216,7 +216,7 @@ static int render_stream(const nsr_field_desc *desc, const void *tables, const f
     NSR_CHECK_PTR(desc); NSR_CHECK_PTR(tables); NSR_CHECK_PTR(mlp_params); NSR_CHECK_PTR(rays_o); NSR_CHECK_PTR(rays_d);
     NSR_CHECK_PTR(nears); NSR_CHECK_PTR(fars); NSR_CHECK_PTR(grid); NSR_CHECK_PTR(weights_sum); NSR_CHECK_PTR(depth);
     NSR_CHECK_PTR(image);
-    if (max_steps == 0 || C == 0 || H == 0 || H > 1024 || !(bound > 0.0f)) return NSR_ERR_INVALID_ARG;
+    if (max_steps == 0 || C == 0 || !rm_grid_size_ok(H) || !(bound > 0.0f)) return NSR_ERR_INVALID_ARG;
     RenderInferArgs a;
     uint32_t field_blocks;
     const int st = field_fill_args(desc, tables, mlp_params, a.f, N, field_blocks);      // num_classes > 13 -> NSR_ERR_UNSUPPORTED

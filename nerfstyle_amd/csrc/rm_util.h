@@ -26,6 +26,11 @@ __device__ __forceinline__ uint32_t rm_morton3d_invert(uint32_t x) {
     return x;
 }
 
+// The grid resolutions every march entry point accepts -- the rule of the nsr_occ_* calls (occupancy.hip, occ_dims_ok): the probe
+// addresses bit level * H^3 + morton(nx, ny, nz) of a C * H^3 / 8 byte bitfield, and a Morton index stays below H^3 only for a
+// power of two (at H = 24, morton(23, 23, 23) = 29183 >= 13824: a read past the bitfield).
+static inline bool rm_grid_size_ok(uint32_t H) { return H >= 8 && H <= 512 && (H & (H - 1u)) == 0u; }
+
 // wave64 inclusive scan by shuffles, then a block scan over the (<= 16) wave totals in LDS.
 // Returns the exclusive prefix of v inside the block and the block total in `total`.
 __device__ __forceinline__ uint32_t rm_block_exclusive_scan(uint32_t v, uint32_t *lds_wave_sums, uint32_t &total) {

@@ -112,10 +112,11 @@ def packbits(grid, thresh):
 
 
 def march_rays_train(rays_o, rays_d, bound, bitfield, C, H, nears, fars, max_steps=1024,
-                     dt_gamma=0.0, M=None, align=-1, counter=None, want_dirs=True, z_hats=None, is_ndc=False):
+                     dt_gamma=0.0, M=None, align=-1, counter=None, want_dirs=True, z_hats=None, is_ndc=False, noises=None):
     """raymarching.py:174-288 (force_all_rays semantics: M = N * max_steps, perturb disabled
     :247, slice to the emitted count padded to `align` :275-281) / raymarching.cu:410-599.
-    is_ndc fills deltas[:, 2:] from the per-ray z_hats (:563-570)."""
+    is_ndc fills deltas[:, 2:] from the per-ray z_hats (:563-570).  noises [N]: the fraction of a step every ray's
+    start is moved by (:452); None = zeros, which is what perturb-disabled gives."""
     o, po = _f(rays_o)
     d, pd = _f(rays_d)
     g, pg = _u8(bitfield)
@@ -130,14 +131,15 @@ def march_rays_train(rays_o, rays_d, bound, bitfield, C, H, nears, fars, max_ste
     rays = np.empty((N, 3), np.int32)
     if counter is None:
         counter = np.zeros(2, np.int32)
-    noises = np.zeros(N, np.float32)
+    no, pno = _f(np.zeros(N, np.float32) if noises is None else noises)
+    assert no.shape == (N,)
     assert not is_ndc or z_hats is not None
     zh, pzh = _f(z_hats) if is_ndc else (None, None)
     lib().ora_march_rays_train(po, pd, pzh, pg, F(bound), F(dt_gamma), U(max_steps), I(int(bool(is_ndc))), U(N), U(C),
                                U(H), U(M), pne, pfa, xyzs.ctypes.data_as(c_f),
                                dirs.ctypes.data_as(c_f) if want_dirs else None,
                                deltas.ctypes.data_as(c_f), rays.ctypes.data_as(c_i),
-                               counter.ctypes.data_as(c_i), noises.ctypes.data_as(c_f))
+                               counter.ctypes.data_as(c_i), pno)
     m = int(counter[0])
     if align > 0:
         m += align - m % align
@@ -184,9 +186,9 @@ def composite_rays_train_backward(grad_ws, grad_image, sigmas, rgbs, deltas, ray
 
 
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, bitfield, C, H, nears, fars,
-               align=-1, max_steps=1024, dt_gamma=0.0, is_ndc=False, z_hats=None):
+               align=-1, max_steps=1024, dt_gamma=0.0, is_ndc=False, z_hats=None, noises=None):
     """raymarching.py:357-424 / raymarching.cu:1004-1130.  With is_ndc, rays_t is [N, 2] (the march reads column 0)
-    and deltas[:, 2:] are filled from the per-ray z_hats (:1094)."""
+    and deltas[:, 2:] are filled from the per-ray z_hats (:1094).  noises [n_alive] (per alive slot, :1053); None = zeros."""
     ra, pra = _i(rays_alive)
     rt, prt = _f(rays_t)
     o, po = _f(rays_o)
@@ -200,12 +202,13 @@ def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, bitfi
     xyzs = np.zeros((M, 3), np.float32)
     dirs = np.zeros((M, 3), np.float32)
     deltas = np.zeros((M, 4), np.float32)
-    noises = np.zeros(n_alive, np.float32)
+    no, pno = _f(np.zeros(n_alive, np.float32) if noises is None else noises)
+    assert no.shape == (n_alive,)
     assert not is_ndc or (z_hats is not None and rt.ndim == 2 and rt.shape[1] == 2)
     zh, pzh = _f(z_hats) if is_ndc else (None, None)
     lib().ora_march_rays(U(n_alive), U(n_step), pra, prt, po, pd, pzh, F(bound), F(dt_gamma), U(max_steps),
                          I(int(bool(is_ndc))), U(C), U(H), pg, pne, pfa, xyzs.ctypes.data_as(c_f),
-                         dirs.ctypes.data_as(c_f), deltas.ctypes.data_as(c_f), noises.ctypes.data_as(c_f))
+                         dirs.ctypes.data_as(c_f), deltas.ctypes.data_as(c_f), pno)
     return xyzs, dirs, deltas
 
 
