@@ -245,6 +245,36 @@ uint64_t nsr_matting_laplacian_workspace_bytes(uint32_t H, uint32_t W, uint32_t 
 int nsr_matting_laplacian(const float *target, const float *v, uint32_t H, uint32_t W, uint32_t win_rad, double eps,
                           double *loss_out, float *grad_v, void *workspace, nsr_stream_t stream);
 
+/* Colour transfer of pixel rows to a style image (ARF's colour matching, the reference's match_colors_for_image_set,
+ * utils/__init__.py:262-295): the two passes over the rows; the 3x3 eigen-solve between them is host code
+ * (nerfstyle_amd/color_match.py).  rows / src / dst: n rows of `stride` f32, stride 3 (R, G, B) or 4 (R, G, B and one float
+ * that is never read as colour); 4-byte aligned, 16-byte aligned for stride 4.
+ *
+ * nsr_color_moments: moments [9] (device fp64, 8-byte aligned) = sum r, sum g, sum b, sum rr, sum rg, sum rb, sum gg, sum gb,
+ * sum bb over the n rows.  Every value is converted to fp64 first (the products are then exact) and every sum is fp64.
+ * Order of summation, a function of n and stride only (no atomics, nothing depends on the device or on timing; two calls give
+ * the same 72 bytes):
+ *   unit:    stride 4: one row, U = n units.  stride 3: four consecutive rows 4u .. 4u+3 (the last unit may hold fewer), added
+ *            in ascending order, U = ceil(n / 4) units.
+ *   grid:    B = clamp(ceil(U / 1024), 1, 2048) blocks of 256 threads, T = 256 B.
+ *   thread:  thread t of the grid adds units t, t + T, t + 2T, ... in that order into nine accumulators that start at +0.
+ *   wave:    butterfly over the 64 lanes (lane ^ 32, 16, 8, 4, 2, 1).
+ *   block:   its four wave sums in ascending order, starting from +0 -> partial[b] in the workspace.
+ *   final:   one block of 256 threads; thread t adds partial[t], partial[t + 256], ... in that order, then wave and block as above.
+ * workspace: nsr_color_moments_workspace_bytes(n) bytes (enough for either stride), 8-byte aligned; nothing of it is read that
+ * this call did not write.  n == 0, stride outside {3, 4}, a NULL or misaligned pointer -> NSR_ERR_INVALID_ARG, nothing written.
+ *
+ * nsr_color_apply: with tf [4,4] f32 row-major in DEVICE memory (read by the kernel: a captured graph sees what was last written
+ * there; its last row is not read), per row and c in 0..2, in f32:
+ *   dst[i,c] = fmaf(tf[c,2], b, fmaf(tf[c,1], g, fmaf(tf[c,0], r, tf[c,3])))        (r, g, b) = src[i,0..2]
+ *   clamp != 0:  dst[i,c] = fminf(fmaxf(dst[i,c], 0), 1)
+ * stride 4: dst[i,3] = src[i,3] bit for bit.  dst == src (in place) is allowed; src and dst that overlap otherwise are refused.
+ * n == 0, stride outside {3, 4}, a NULL or misaligned pointer, such an overlap -> NSR_ERR_INVALID_ARG, nothing written.
+ * Neither call reads the host or allocates; both are capture-safe. */
+uint64_t nsr_color_moments_workspace_bytes(uint64_t n);
+int nsr_color_moments(const float *rows, uint64_t n, uint32_t stride, double *moments, void *workspace, nsr_stream_t stream);
+int nsr_color_apply(const float *src, float *dst, uint64_t n, uint32_t stride, const float *tf, int clamp, nsr_stream_t stream);
+
 /* replaces march_rays (raymarching.h:17, raymarching.cu:1004-1130), inference.  noises [n_alive] f32 or NULL (= zeros).
  * C, H as for nsr_march_rays_train: H a power of two in 8..512, C <= 8, else NSR_ERR_INVALID_ARG. */
 int nsr_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t,

@@ -48,6 +48,7 @@ class ResidentDataset:
         self.intr, self.num_classes, self.bound = intr, int(num_classes), bound
         self.bbox = BBox.from_radius(bound)
         self._rgb_rows = self._cls_rows = None
+        self.color_tf = None            # [4,4] f32 on the device once match_colors() has run
 
     def __len__(self):
         return self.poses.shape[0]
@@ -64,6 +65,30 @@ class ResidentDataset:
         if self._rgb_rows is None:
             self._rgb_rows = self.targets[:, :, :3].reshape(-1, 3).contiguous()
         return self._rgb_rows
+
+    def match_colors(self, style_image: torch.Tensor) -> torch.Tensor:
+        """Matches the colours of every frame's targets to `style_image` [3,H,W] f32 in [0,1] (what StyleCriterion.init_style takes;
+        any size): the reference's `ct_image` step (data/base_dataset.py:97-105, color_match.py), to be called after the dataset
+        is built and before the stylisation stage.  One mean and covariance over all frames' pixels, read from `targets` where it
+        lies ([F, H*W, C] rows, no RGB copy); the affine map is applied to `targets` IN PLACE and clamped to [0, 1]; the segment
+        channel is not touched, bit for bit.  -> color_tf [4,4] f32 on the device, kept as `self.color_tf`: apply it to rendered
+        rgb rows with color_match.apply_color_transform.  The solve reads 18 doubles on the host: set-up, not a training step.
+
+        A `target_rgb_rows` handed out before the call is UPDATED IN PLACE (copied anew from the targets), so whoever holds it
+        sees the new colours; target_cls_rows, draw, ErrorMap and sample read what they read before.
+        Calling it again matches the current, already matched and clamped, targets to the new image: transforms do not compose
+        into `color_tf`, which holds the last one only."""
+        from . import color_match as CM
+        if style_image.dim() != 3 or style_image.shape[0] != 3:
+            raise ValueError('match_colors: style_image must be [3,H,W]; got {}'.format(tuple(style_image.shape)))
+        dev = self.targets.device
+        style = style_image.detach().to(dev, torch.float32).permute(1, 2, 0).contiguous()
+        n = self.targets.shape[0] * self.targets.shape[1]
+        self.color_tf = CM.solve_color_transform(CM.color_moments(self.targets), n, CM.color_moments(style), style.numel() // 3)
+        CM.apply_color_transform(self.targets, self.color_tf, clamp=True, out=self.targets)
+        if self._rgb_rows is not None and self._rgb_rows.data_ptr() != self.targets.data_ptr():       # C == 3: one storage
+            self._rgb_rows.copy_(self.targets[:, :, :3].reshape(-1, 3))
+        return self.color_tf
 
     @property
     def target_cls_rows(self):
