@@ -837,6 +837,50 @@ int nsr_draw_frame_batch_error(uint32_t F, uint32_t w, uint32_t h, uint32_t cell
                                const int32_t *fixed_frames, int advance, int32_t *seg_frame, int32_t *pix, int64_t *rows,
                                float *weights, nsr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Total variation of the hash-grid tables (torch-ngp's GridEncoder.grad_total_variation): the gradient of a squared-difference
+ * smoothness term between neighbouring lattice vertices, added into the table gradient after the backward and before the
+ * optimiser step; optionally the term's value.  Additive: the ABI version stays.
+ *
+ * Table: `rows` rows of row_floats fp32 lanes (1, 2, 4 or 8): 4 for the fused model's arena ([row][enc][feat]), C for a
+ * stand-alone GridEncoder.  Levels are (offsets, L, S, H, gridtype) as everywhere else (nsr_grid_resolutions gives res_l); the
+ * vertices of level l are (x, y, z) with 0 <= x, y, z <= res_l, V_l = (res_l + 1)^3 of them (64-bit on the host), and the row
+ * of a vertex is offsets[l] + the row the forward gathers it from (dense or hashed, style 0).
+ *
+ * Loss, with lambda [row_floats] HOST floats, one weight per lane k:
+ *   TV_{l,k} = (1 / V_l) * sum over the edges (a, a + e_d) inside the lattice of (t[row(a)][k] - t[row(a + e_d)][k])^2
+ *   loss     = sum_l sum_k lambda_k * TV_{l,k}
+ * Estimator: level l makes n_l = min(n_samples, V_l) draws of a vertex a.
+ *   sweep   (n_samples >= V_l): draw i is x = i % (res+1), y = (i / (res+1)) % (res+1), z = i / (res+1)^2: every vertex once,
+ *           the gradient is exact
+ *   sampled (otherwise): r = philox(i, seq, 5, (stream_id << 8) | l) keyed by `seed` (the Philox4x32-10 of nsr_draw_frame_batch,
+ *           whose calls use counter words 0..4), x = umulhi(r.x, res+1), y = umulhi(r.y, res+1), z = umulhi(r.z, res+1)
+ *   seq = sequence + (sequence_dev ? sequence_dev[0] : 0); advance != 0 (needs sequence_dev): after the draws, on the same
+ *   stream, a kernel of its own increments sequence_dev[0], so a captured graph draws afresh on every replay.  stream_id: the
+ *   data-parallel rank.
+ * Gradient: each draw a adds, to grad[row(a)][k] only (the fp32 atomic of nsr_grid_encode_backward),
+ *   c_{l,k} * scale * sum over d and s = +-1 with 0 <= a_d + s <= res_l of (t[row(a)][k] - t[row(a + s e_d)][k])
+ *   c_{l,k} = (float)(2.0 * lambda_k / n_l), formed in fp64 on the host and rounded once;
+ *   scale = scale_host * (scale_dev ? scale_dev[0] : 1), scale_dev the device loss scale.
+ *   Unbiased; summed over all vertices it is exactly d loss / d t[row], collisions included (each edge is seen once from
+ *   either end).  In fp32: the differences, summed as ((x- + x+) + (y- + y+)) + (z- + z+), times the rounded c * scale.
+ *   Lanes with lambda_k == 0 are not written (their bits stay); levels whose bit of level_mask is clear are skipped.
+ * value (optional, device double [L][row_floats], 8-byte aligned):
+ *   value[l][k] = (1 / n_l) * sum over the draws and the d with a_d + 1 <= res_l of (t[row(a)][k] - t[row(a + e_d)][k])^2,
+ *   differences and squares in fp64 from the fp32 entries, summed without atomics in an order fixed by (L, n_samples, the
+ *   levels): per-workgroup partials in `workspace` (nsr_grid_tv_workspace_bytes(L, n_samples, row_floats) bytes, 8-byte
+ *   aligned, needed iff value), then one ordered pass.  Two calls give the same bits.  Lanes with lambda_k == 0 and masked
+ *   levels report 0.  grad_tables == NULL with value given computes the value only.
+ * tables must be aligned to a row (16 bytes from row_floats = 4 on).  NULL tables, lambda or offsets, neither grad_tables nor
+ * value, value without workspace, row_floats outside {1, 2, 4, 8}, L == 0 or L > 32, n_samples == 0, gridtype > 1, or advance
+ * without sequence_dev -> NSR_ERR_INVALID_ARG before anything touches a device.  Capture-safe, no host read.
+ * ------------------------------------------------------------------------------------------ */
+uint64_t nsr_grid_tv_workspace_bytes(uint32_t L, uint32_t n_samples, uint32_t row_floats);
+int nsr_grid_tv(const float *tables, float *grad_tables, uint32_t row_floats, const float *lambda, const int32_t *offsets,
+                uint32_t L, float S, uint32_t H, uint32_t gridtype, uint32_t level_mask, uint32_t n_samples, uint64_t seed,
+                uint32_t sequence, uint32_t *sequence_dev, uint32_t stream_id, int advance, float scale_host,
+                const float *scale_dev, double *value, void *workspace, nsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

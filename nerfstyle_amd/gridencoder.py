@@ -134,3 +134,15 @@ class GridEncoder(nn.Module):
         outputs = grid_encode(inputs, self.embeddings, self.offsets, self.per_level_scale, self.base_resolution,
                               inputs.requires_grad, self.gridtype_id, self.align_corners, style)
         return outputs.view(prefix_shape + [self.output_dim])
+
+    def grad_total_variation(self, weight=1e-7, n_samples=1 << 18, seed=0):
+        """torch-ngp's entry point of this name: adds the gradient of weight * TV of the table (include/nsr.h, "Total
+        variation"; nerfstyle_amd/tv.py) to embeddings.grad -- a zero fp32 .grad is allocated if there is none.  After the
+        backward, before the optimiser step; every call draws afresh."""
+        from .tv import TVRegulariser
+        key = (float(weight), int(n_samples), int(seed), self.embeddings.device)
+        tv = self.__dict__.get('_tv')
+        if tv is None or tv[0] != key:
+            tv = (key, TVRegulariser(self, weight=weight, n_samples=n_samples, seed=seed))
+            self.__dict__['_tv'] = tv
+        tv[1].add_grad()
