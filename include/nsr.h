@@ -881,6 +881,52 @@ int nsr_grid_tv(const float *tables, float *grad_tables, uint32_t row_floats, co
                 uint32_t sequence, uint32_t *sequence_dev, uint32_t stream_id, int advance, float scale_host,
                 const float *scale_dev, double *value, void *workspace, nsr_stream_t stream);
 
+/* Structural similarity (Wang et al. 2004 in the form 3DGS and pytorch-ssim use) of two H x W RGB images, and its gradient
+ * towards the first: value, optional map, optional gradient in one call.
+ * Layout: both images are pixel-major rows read where they are: channel c of pixel (y, x) is
+ *   img[(y * img_pitch + x) * img_stride + c]            stride in {3, 4} floats a pixel (the fourth is never read),
+ *   target[(y * target_pitch + x) * target_stride + c]   pitch >= W pixels an image row (a patch of a larger frame in place)
+ * 4-byte aligned, 16-byte aligned for stride 4.
+ * Definition, per channel, data range 1, C1 = 0.01^2, C2 = 0.03^2, x = img, y = target:
+ *   window  g[i] = exp(-(i-5)^2 / (2 * 1.5^2)), i = 0..10, normalised to sum 1 in fp64, then rounded to f32; G* is the
+ *           separable 11x11 convolution with these weights, zero padding of 5; rows first, then columns, each sum an f32 fmaf
+ *           chain over the taps in ascending order
+ *   mu_x = G*x, mu_y = G*y, sxx = G*(x x) - mu_x^2, syy = G*(y y) - mu_y^2, sxy = G*(x y) - mu_x mu_y     (no clamping)
+ *   m = ((2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1)) * ((2 sxy + C2) / (sxx + syy + C2))                  (f32)
+ *   The window sums are taken of x' = x - 1/2 and y' = y - 1/2 inside the image (zero outside, as the padding of x is) and the
+ *   same quantities formed from them, with g1 = G*1 the window mass inside the image (fp64) and d = 1 - g1:
+ *   mu_x = G*x' + g1/2, sxx = [G*(x'x') - (G*x')^2] + (G*x') d + g1 d/4, sxy = [G*(x'y') - G*x' G*y'] + (G*x' + G*y') d/2 + g1 d/4:
+ *   the cancellation in the variances, which sets the f32 error of m, is then between numbers of size 1/4 at most.
+ *   valid == 0 ('same'):  every pixel is counted, count = 3 H W
+ *   valid == 1 ('valid'): pixels whose whole window lies inside the image, 5 <= x < W - 5 and 5 <= y < H - 5,
+ *                         count = 3 (H - 10)(W - 10); needs H, W >= 11
+ * out [4] (device fp64, 8-byte aligned): the mean of m over the counted pixels of all channels, then the three channel means.
+ * ssim_map (optional) [H*W, 3] f32, rows in image order: m, 0 where the pixel is not counted.
+ * grad (optional) [H*W, 3] f32: with A = dm/dmu_x - 2 mu_x dm/dsxx - mu_y dm/dsxy, B = dm/dsxx, C = dm/dsxy at the counted
+ *   pixels and 0 elsewhere,
+ *   unit(q) = ((G*A)(q) + 2 x(q) (G*B)(q) + y(q) (G*C)(q)) * (float)(1 / count)        = dSSIM / dx(q), in f32, uncontracted
+ *   grad(q) = (coef * (scale ? scale[0] : 1)) * unit(q)                                two f32 products
+ *   scale: 0-dim f32 DEVICE pointer or NULL (LossScaler.scale_tensor, as in nsr_recon_loss); a D-SSIM loss
+ *   lambda * (1 - SSIM) passes coef = -lambda * factor.  No gradient towards target.  For identical images m == 1 and
+ *   grad == 0 exactly.
+ * Order of the sums of m (fp64; no atomics; two calls and the replays of a captured graph give the same bits in value, map
+ * and gradient): one workgroup of 256 threads per 32x32 tile and channel; thread t owns column t % 32 and rows
+ * 4 (t / 32) .. + 3 of the tile and adds its pixels in ascending row; butterfly over the 64 lanes (lane ^ 32, 16, 8, 4, 2, 1);
+ * the four waves in ascending order -> partial[c][tile], tiles in row-major order.  Final pass, one block of 256 threads:
+ * thread t adds partial[c][t], partial[c][t + 256], ... in that order, then wave and block as above; out[1 + c] =
+ * s_c / (count / 3), out[0] = ((s_0 + s_1) + s_2) / (count / 3) / 3.
+ * workspace: nsr_ssim_workspace_bytes(H, W, want_grad) bytes, 8-byte aligned (want_grad != 0 iff grad is given: the
+ * partials, then A, B, C as nine f32 planes); nothing of it is read that this call did not write.  The size is 0 for a
+ * shape that nsr_ssim refuses.
+ * Refused with NSR_ERR_INVALID_ARG, before any pointer is looked at: H == 0, W == 0, H * W > 2^30 or H > 32 * 65535,
+ * valid > 1, a stride outside {3, 4}, a pitch < W, valid with H < 11 or W < 11; then a NULL img, target, out or workspace,
+ * a misaligned pointer, grad or ssim_map overlapping an input or each other.  Nothing is written then.
+ * No host read, no allocation, capture-safe. */
+uint64_t nsr_ssim_workspace_bytes(uint32_t H, uint32_t W, uint32_t want_grad);
+int nsr_ssim(const float *img, uint32_t img_stride, uint32_t img_pitch, const float *target, uint32_t target_stride,
+             uint32_t target_pitch, uint32_t H, uint32_t W, uint32_t valid, float coef, const float *scale, double *out,
+             float *ssim_map, float *grad, void *workspace, nsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

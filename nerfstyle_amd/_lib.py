@@ -130,6 +130,8 @@ SIGNATURES = {
     'nsr_grid_tv_workspace_bytes': (u64, [u32, u32, u32]),
     'nsr_grid_tv': (i32, [vp, vp, u32, ctypes.POINTER(f32), ctypes.POINTER(ctypes.c_int32), u32, f32, u32, u32, u32, u32, u64, u32,
                           vp, u32, i32, f32, vp, vp, vp, vp]),
+    'nsr_ssim_workspace_bytes': (u64, [u32, u32, u32]),
+    'nsr_ssim': (i32, [vp, u32, u32, vp, u32, u32, u32, u32, u32, f32, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -1,0 +1,318 @@
+// Structural similarity (Wang et al. 2004, in the form 3DGS and pytorch-ssim use) of two images held as pixel-major rows,
+// value, optional map and optional gradient towards the first image (nsr_ssim, include/nsr.h).
+//
+// Per colour channel, G* the separable 11-tap Gaussian window (sigma 1.5, the eleven f32 weights of ss_window()):
+//   mu_x = G*x, mu_y = G*y, sxx = G*(x x) - mu_x^2, syy = G*(y y) - mu_y^2, sxy = G*(x y) - mu_x mu_y
+//   m = ((2 mu_x mu_y + C1)(2 sxy + C2)) / ((mu_x^2 + mu_y^2 + C1)(sxx + syy + C2))
+// and, at every counted pixel, A = dm/dmu_x - 2 mu_x dm/dsxx - mu_y dm/dsxy, B = dm/dsxx, C = dm/dsxy, so that
+//   dSSIM/dx(q) = [(G*A)(q) + 2 x(q) (G*B)(q) + y(q) (G*C)(q)] / count
+// (the window is symmetric: the adjoint of the zero-padded convolution is the same convolution).
+//
+// Two kernels of one skeleton.  A workgroup of 256 threads owns a 32x32 tile of one channel (grid.z): it stages the tile
+// plus a 5-pixel halo in LDS (zero outside the image), runs the horizontal 11-tap pass over all 42 staged rows into LDS and
+// the vertical pass with four consecutive output rows per thread (14 LDS reads feed 44 taps).
+//   k_ssim_fwd   stages x' = x - 1/2, y' = y - 1/2 (ss_eval says why); passes over x', y', x'x', y'y', x'y'; evaluates m, A,
+//                B, C; writes A, B, C as planes of the workspace (only when a gradient is wanted), the map (optional) and
+//                one fp64 partial of m per block
+//   k_ssim_bwd   stages A, B, C; passes over them; reads x, y of its own pixel and writes the gradient
+//   k_ssim_final one block: the partials of each channel in a fixed order -> out[4]
+// No atomics: value, map and gradient are the same bits from call to call.  LDS per workgroup: 41 024 B forward, 37 296 B
+// backward.  Traffic per pixel and channel, halo re-reads (served by L2) aside: forward 8 B read, 12 B written for A, B, C
+// (+ 4 B map); backward 12 + 8 B read, 4 B written.
+#include <math.h>
+
+#include "nsr_common.h"
+
+#define SS_T 32                          // tile edge (nerfstyle_amd/ssim.py: TILE)
+#define SS_R 5                           // window radius
+#define SS_K (2 * SS_R + 1)
+#define SS_P (SS_T + 2 * SS_R)           // staged edge
+#define SS_BLOCK 256
+#define SS_ROWS (SS_T * SS_T / SS_BLOCK) // output rows per thread in the vertical pass
+#define SS_MAX_PIXELS (1u << 30)
+
+struct SsWindow {
+    float g[SS_K];
+};
+
+struct SsimArgs {
+    const float *img, *target;
+    uint32_t img_stride, img_pitch, target_stride, target_pitch;
+    uint32_t H, W, valid, nblocks;       // nblocks: tiles per channel
+    float coef;
+    const float *scale;                  // 0-dim device f32 or NULL
+    float inv_count;                     // 1 / (3 * counted pixels)
+    double inv_plane;                    // 1 / counted pixels
+    double *partials;                    // [3][nblocks]
+    float *abc;                          // [3 channels][A, B, C][H*W] or NULL
+    double *out;                         // [4]
+    float *ssim_map, *grad;              // [H*W, 3] or NULL
+    SsWindow w;
+};
+
+// g[i] = exp(-(i-5)^2 / (2 * 1.5^2)), normalised to sum 1 in fp64, then rounded to f32
+static SsWindow ss_window() {
+    double g[SS_K], s = 0.0;
+    for (int i = 0; i < SS_K; i++) {
+        g[i] = exp(-(double)((i - SS_R) * (i - SS_R)) / (2.0 * 1.5 * 1.5));
+        s += g[i];
+    }
+    SsWindow w;
+    for (int i = 0; i < SS_K; i++) w.g[i] = (float)(g[i] / s);
+    return w;
+}
+
+// vertical pass: column tx, output rows 4 * tq .. 4 * tq + 3 of the tile from the 14 staged rows below them; every output
+// adds its taps in ascending order
+template <int NQ>
+__device__ __forceinline__ void ss_vertical(const float (*s_h)[SS_P * SS_T], const SsWindow &w, int tx, int tq,
+                                            float (*acc)[SS_ROWS]) {
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+#pragma unroll
+        for (int o = 0; o < SS_ROWS; o++) acc[q][o] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < SS_ROWS + SS_K - 1; j++) {
+            const float v = s_h[q][(SS_ROWS * tq + j) * SS_T + tx];
+#pragma unroll
+            for (int o = 0; o < SS_ROWS; o++)
+                if (j - o >= 0 && j - o < SS_K) acc[q][o] = fmaf(w.g[j - o], v, acc[q][o]);
+        }
+    }
+}
+
+// window mass inside [0, n) of the window centred at p: the sum of its in-image weights, ascending, in fp64
+__device__ __forceinline__ double ss_mass(const SsWindow &w, int p, int n) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < SS_K; k++)
+        if (p + k - SS_R >= 0 && p + k - SS_R < n) s += (double)w.g[k];
+    return s;
+}
+
+// m and the three per-pixel gradient coefficients from the five window sums of the SHIFTED images x' = x - 1/2, y' = y - 1/2
+// (zero outside the image as before), g1 = G*1 the window mass inside the image and d = 1 - g1:
+//   mu_x = G*x' + g1/2,   sxx = [G*(x'x') - (G*x')^2] + (G*x') d + g1 d / 4,   sxy = [G*(x'y') - G*x' G*y'] + (G*x' + G*y') d / 2 + g1 d / 4
+// the same quantities (G is linear), but the cancellation G*(x x) - mu_x^2 that dominates the f32 error of m happens between
+// numbers of size x'^2 <= 1/4 instead of x^2 <= 1; d is formed in fp64 and is ~1e-8 away from the border.
+// The quotients are formed as a1/b1 and a2/b2 (the same m): for identical images a1 == b1 and a2 == b2 bit for bit, so
+// m == 1, A == 0 and C == -2 B exactly, and the gradient vanishes instead of carrying the rounding of 1/(b1 b2).  No
+// contraction: a fused multiply-add would keep the exact product on one side of such a cancellation only.
+__device__ __forceinline__ void ss_eval(float gx, float gy, float exx, float eyy, float exy, float g1, float d, float &m,
+                                        float &A, float &B, float &C) {
+#pragma clang fp contract(off)
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    const float mx = gx + 0.5f * g1, my = gy + 0.5f * g1;
+    const float t = (0.25f * g1) * d;
+    const float sxx = (exx - gx * gx) + (gx * d + t);
+    const float syy = (eyy - gy * gy) + (gy * d + t);
+    const float sxy = (exy - gx * gy) + ((0.5f * (gx + gy)) * d + t);
+    const float mxx = mx * mx, myy = my * my, mxy = mx * my;
+    const float a1 = 2.0f * mxy + C1, a2 = 2.0f * sxy + C2;
+    const float b1 = mxx + myy + C1, b2 = sxx + syy + C2;
+    const float r1 = a1 / b1, r2 = a2 / b2;
+    m = r1 * r2;
+    B = -m / b2;                                         // dm/dsxx
+    C = 2.0f * r1 / b2;                                  // dm/dsxy
+    const float dmx = 2.0f * (my * r2 - mx * m) / b1;    // dm/dmu_x
+    A = (dmx - (2.0f * mx) * B) - my * C;
+}
+
+__global__ void __launch_bounds__(SS_BLOCK)
+k_ssim_fwd(SsimArgs a) {
+    __shared__ float s_in[2][SS_P * SS_P];               // x - 1/2, y - 1/2 of the tile + halo
+    __shared__ float s_h[5][SS_P * SS_T];                // horizontal sums of x, y, xx, yy, xy
+    __shared__ double s_red[SS_BLOCK / 64];
+    const int tid = threadIdx.x, c = blockIdx.z;
+    const int x0 = blockIdx.x * SS_T, y0 = blockIdx.y * SS_T;
+    const int H = (int)a.H, W = (int)a.W;
+
+    for (int i = tid; i < SS_P * SS_P; i += SS_BLOCK) {
+        const int gx = x0 - SS_R + i % SS_P, gy = y0 - SS_R + i / SS_P;
+        const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
+        s_in[0][i] = in ? a.img[((size_t)gy * a.img_pitch + gx) * a.img_stride + c] - 0.5f : 0.0f;
+        s_in[1][i] = in ? a.target[((size_t)gy * a.target_pitch + gx) * a.target_stride + c] - 0.5f : 0.0f;
+    }
+    __syncthreads();
+    for (int i = tid; i < SS_P * SS_T; i += SS_BLOCK) {
+        const int p = (i / SS_T) * SS_P + i % SS_T;
+        float sx = 0.0f, sy = 0.0f, sxx = 0.0f, syy = 0.0f, sxy = 0.0f;
+#pragma unroll
+        for (int k = 0; k < SS_K; k++) {
+            const float g = a.w.g[k], x = s_in[0][p + k], y = s_in[1][p + k];
+            sx = fmaf(g, x, sx); sy = fmaf(g, y, sy);
+            sxx = fmaf(g, x * x, sxx); syy = fmaf(g, y * y, syy); sxy = fmaf(g, x * y, sxy);
+        }
+        s_h[0][i] = sx; s_h[1][i] = sy; s_h[2][i] = sxx; s_h[3][i] = syy; s_h[4][i] = sxy;
+    }
+    __syncthreads();
+
+    const int tx = tid % SS_T, tq = tid / SS_T;
+    float acc[5][SS_ROWS];
+    ss_vertical<5>(s_h, a.w, tx, tq, acc);
+    const size_t plane = (size_t)a.H * a.W;
+    const int px = x0 + tx;
+    const int lo = a.valid ? SS_R : 0;
+    const double wx = ss_mass(a.w, px, W);
+    double val = 0.0;
+#pragma unroll
+    for (int o = 0; o < SS_ROWS; o++) {
+        const int py = y0 + SS_ROWS * tq + o;
+        if (px >= W || py >= H) continue;
+        float m = 0.0f, A = 0.0f, B = 0.0f, C = 0.0f;
+        if (px >= lo && px < W - lo && py >= lo && py < H - lo) {
+            const double g1 = wx * ss_mass(a.w, py, H);
+            ss_eval(acc[0][o], acc[1][o], acc[2][o], acc[3][o], acc[4][o], (float)g1, (float)(1.0 - g1), m, A, B, C);
+        }
+        val += (double)m;
+        const size_t pix = (size_t)py * a.W + px;
+        if (a.abc) {
+            float *q = a.abc + (size_t)c * 3 * plane + pix;
+            q[0] = A; q[plane] = B; q[2 * plane] = C;
+        }
+        if (a.ssim_map) a.ssim_map[pix * 3 + c] = m;
+    }
+    // block partial, fixed order
+    for (int off = 32; off >= 1; off >>= 1) val += __shfl_xor(val, off, 64);
+    if ((tid & 63) == 0) s_red[tid >> 6] = val;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int w = 0; w < SS_BLOCK / 64; w++) s += s_red[w];
+        a.partials[(size_t)c * a.nblocks + blockIdx.y * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+__global__ void __launch_bounds__(SS_BLOCK)
+k_ssim_bwd(SsimArgs a) {
+    __shared__ float s_in[3][SS_P * SS_P];               // A, B, C of the tile + halo
+    __shared__ float s_h[3][SS_P * SS_T];
+    const int tid = threadIdx.x, c = blockIdx.z;
+    const int x0 = blockIdx.x * SS_T, y0 = blockIdx.y * SS_T;
+    const int H = (int)a.H, W = (int)a.W;
+    const size_t plane = (size_t)a.H * a.W;
+    const float *abc = a.abc + (size_t)c * 3 * plane;
+
+    for (int i = tid; i < SS_P * SS_P; i += SS_BLOCK) {
+        const int gx = x0 - SS_R + i % SS_P, gy = y0 - SS_R + i / SS_P;
+        const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
+        const size_t pix = in ? (size_t)gy * a.W + gx : 0;
+#pragma unroll
+        for (int q = 0; q < 3; q++) s_in[q][i] = in ? abc[q * plane + pix] : 0.0f;
+    }
+    __syncthreads();
+    for (int i = tid; i < SS_P * SS_T; i += SS_BLOCK) {
+        const int p = (i / SS_T) * SS_P + i % SS_T;
+        float s[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < SS_K; k++) {
+#pragma unroll
+            for (int q = 0; q < 3; q++) s[q] = fmaf(a.w.g[k], s_in[q][p + k], s[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; q++) s_h[q][i] = s[q];
+    }
+    __syncthreads();
+
+    const int tx = tid % SS_T, tq = tid / SS_T;
+    float acc[3][SS_ROWS];
+    ss_vertical<3>(s_h, a.w, tx, tq, acc);
+    const int px = x0 + tx;
+    if (px >= W) return;
+    const float cs = a.coef * (a.scale ? a.scale[0] : 1.0f);
+#pragma unroll
+    for (int o = 0; o < SS_ROWS; o++) {
+#pragma clang fp contract(off)
+        const int py = y0 + SS_ROWS * tq + o;
+        if (py >= H) continue;
+        const float x = a.img[((size_t)py * a.img_pitch + px) * a.img_stride + c];
+        const float y = a.target[((size_t)py * a.target_pitch + px) * a.target_stride + c];
+        const float unit = ((acc[0][o] + (2.0f * x) * acc[1][o]) + y * acc[2][o]) * a.inv_count;
+        a.grad[((size_t)py * a.W + px) * 3 + c] = cs * unit;
+    }
+}
+
+// one block: thread t adds partial[c][t], partial[c][t + 256], ... in that order; butterfly over the 64 lanes; the four
+// waves in ascending order; out = {(s0 + s1 + s2) / 3, s0, s1, s2} / counted pixels
+__global__ void __launch_bounds__(SS_BLOCK)
+k_ssim_final(SsimArgs a) {
+    __shared__ double red[3][SS_BLOCK / 64];
+    for (int c = 0; c < 3; c++) {
+        double s = 0.0;
+        for (uint32_t b = threadIdx.x; b < a.nblocks; b += SS_BLOCK) s += a.partials[(size_t)c * a.nblocks + b];
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+        if ((threadIdx.x & 63) == 0) red[c][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t[3];
+        for (int c = 0; c < 3; c++) {
+            t[c] = 0.0;
+            for (int w = 0; w < SS_BLOCK / 64; w++) t[c] += red[c][w];
+        }
+        a.out[0] = ((t[0] + t[1]) + t[2]) * a.inv_plane / 3.0;
+        for (int c = 0; c < 3; c++) a.out[1 + c] = t[c] * a.inv_plane;
+    }
+}
+
+static inline uint64_t ss_tiles(uint32_t H, uint32_t W) { return (uint64_t)nsr_div_up(W, SS_T) * nsr_div_up(H, SS_T); }
+
+// bytes from the first to one past the last float the kernels touch of an image
+static inline uint64_t ss_extent(uint32_t H, uint32_t W, uint32_t stride, uint32_t pitch) {
+    return ((((uint64_t)H - 1) * pitch + (W - 1)) * stride + 3) * sizeof(float);
+}
+
+static inline bool ss_overlap(const void *p, uint64_t np, const void *q, uint64_t nq) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + nq && b < a + np;
+}
+
+extern "C" {
+
+uint64_t nsr_ssim_workspace_bytes(uint32_t H, uint32_t W, uint32_t want_grad) {
+    if (H == 0 || W == 0 || (uint64_t)H * W > SS_MAX_PIXELS || H > 65535u * SS_T) return 0;
+    const uint64_t abc = want_grad ? (uint64_t)H * W * 9 * sizeof(float) : 0;
+    return ss_tiles(H, W) * 3 * sizeof(double) + ((abc + 7) & ~(uint64_t)7);
+}
+
+int nsr_ssim(const float *img, uint32_t img_stride, uint32_t img_pitch, const float *target, uint32_t target_stride,
+             uint32_t target_pitch, uint32_t H, uint32_t W, uint32_t valid, float coef, const float *scale, double *out,
+             float *ssim_map, float *grad, void *workspace, nsr_stream_t stream) {
+    if (H == 0 || W == 0 || (uint64_t)H * W > SS_MAX_PIXELS || H > 65535u * SS_T || valid > 1) return NSR_ERR_INVALID_ARG;
+    if ((img_stride != 3 && img_stride != 4) || (target_stride != 3 && target_stride != 4)) return NSR_ERR_INVALID_ARG;
+    if (img_pitch < W || target_pitch < W) return NSR_ERR_INVALID_ARG;
+    if (valid && (H < SS_K || W < SS_K)) return NSR_ERR_INVALID_ARG;
+    NSR_CHECK_PTR(img); NSR_CHECK_PTR(target); NSR_CHECK_PTR(out); NSR_CHECK_PTR(workspace);
+    if (((uintptr_t)img & (img_stride == 4 ? 15u : 3u)) || ((uintptr_t)target & (target_stride == 4 ? 15u : 3u)))
+        return NSR_ERR_INVALID_ARG;
+    if (((uintptr_t)out & 7u) || ((uintptr_t)workspace & 7u) || ((uintptr_t)scale & 3u) || ((uintptr_t)ssim_map & 3u) ||
+        ((uintptr_t)grad & 3u))
+        return NSR_ERR_INVALID_ARG;
+    const uint64_t ni = ss_extent(H, W, img_stride, img_pitch), nt = ss_extent(H, W, target_stride, target_pitch);
+    const uint64_t no = (uint64_t)H * W * 3 * sizeof(float);
+    for (float *o : {grad, ssim_map})
+        if (o && (ss_overlap(o, no, img, ni) || ss_overlap(o, no, target, nt))) return NSR_ERR_INVALID_ARG;
+    if (grad && ssim_map && ss_overlap(grad, no, ssim_map, no)) return NSR_ERR_INVALID_ARG;
+
+    SsimArgs a;
+    a.img = img; a.target = target;
+    a.img_stride = img_stride; a.img_pitch = img_pitch; a.target_stride = target_stride; a.target_pitch = target_pitch;
+    a.H = H; a.W = W; a.valid = valid;
+    const dim3 g(nsr_div_up(W, SS_T), nsr_div_up(H, SS_T), 3);
+    a.nblocks = g.x * g.y;
+    const double npix = valid ? (double)(H - 2 * SS_R) * (double)(W - 2 * SS_R) : (double)H * (double)W;
+    a.inv_plane = 1.0 / npix;
+    a.inv_count = (float)(1.0 / (3.0 * npix));
+    a.coef = coef; a.scale = scale;
+    a.partials = (double *)workspace;
+    a.abc = grad ? (float *)((double *)workspace + (size_t)a.nblocks * 3) : nullptr;
+    a.out = out; a.ssim_map = ssim_map; a.grad = grad;
+    a.w = ss_window();
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ssim_fwd, g, dim3(SS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_ssim_final, dim3(1), dim3(SS_BLOCK), 0, s, a);
+    if (grad) hipLaunchKernelGGL(k_ssim_bwd, g, dim3(SS_BLOCK), 0, s, a);
+    return nsr_launch_status();
+}
+
+}   // extern "C"

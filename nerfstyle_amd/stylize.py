@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from . import parallel as P
 from .common import Box2D
 from .matting import MattingLaplacian
+from .ssim import ssim
 
 
 class StyleCriterion:
@@ -37,10 +38,14 @@ class StyleCriterion:
 
     photo_lambda != 0 adds the photorealism term photo_lambda * MattingLaplacian(target, rendered) (the reference's
     commented-out style.py:98,102; photo_lambda in config.py:440), evaluated in fp64 by matting.py and cast to the dtype of
-    the other terms.  0 (the default, cfgs/training/style.yaml:11) launches nothing."""
+    the other terms.  0 (the default, cfgs/training/style.yaml:11) launches nothing.
+
+    ssim_lambda != 0 adds the structure-preservation term ssim_lambda * (1 - SSIM(rendered, target)) (ssim.py: one fused launch
+    on the [H,W,3] frame as it is, fp64 value), a cheap companion of the VGG content loss; not in the reference.  0 (the
+    default) launches nothing and leaves every returned value bit for bit as it was."""
 
     def __init__(self, fx, style_loss, content_lambda: float = 0.001, style_lambda: float = 1.0, content_feat: str = 'relu3',
-                 amp_dtype=None, photo_lambda: float = 0.0):
+                 amp_dtype=None, photo_lambda: float = 0.0, ssim_lambda: float = 0.0):
         """amp_dtype: torch.float16 / torch.bfloat16 runs the loss under torch.autocast, as the reference does with
         enable_amp (cfgs/training/default.yaml:16, style.py:182-184: convolutions and the feature products in half
         precision, reductions in fp32); None = fp32."""
@@ -50,6 +55,8 @@ class StyleCriterion:
         self.photo_lambda = float(photo_lambda)
         self.photo_loss = MattingLaplacian() if self.photo_lambda != 0.0 else None       # style.py:54
         self.last_photo = None      # detached fp64 device tensor photo_lambda * L of the last call (never read on the host)
+        self.ssim_lambda = float(ssim_lambda)
+        self.last_ssim = None       # detached fp64 device tensor ssim_lambda * (1 - SSIM) of the last call, likewise
         self._target_feats = {}
 
     def _autocast(self, device):
@@ -79,6 +86,10 @@ class StyleCriterion:
             photo = self.photo_loss(target_chw, rgb_hw3.permute(2, 0, 1)) * self.photo_lambda      # style.py:98,102 (fp64)
             self.last_photo = photo.detach()
             total = total + photo.to(total.dtype)
+        if self.ssim_lambda != 0.0:
+            struct = (1.0 - ssim(rgb_hw3, target_chw.permute(1, 2, 0))) * self.ssim_lambda
+            self.last_ssim = struct.detach()
+            total = total + struct.to(total.dtype)
         return total, content.detach(), style.detach()
 
 
