@@ -927,6 +927,56 @@ int nsr_ssim(const float *img, uint32_t img_stride, uint32_t img_pitch, const fl
              uint32_t target_pitch, uint32_t H, uint32_t W, uint32_t valid, float coef, const float *scale, double *out,
              float *ssim_map, float *grad, void *workspace, nsr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh export: the iso-surface of a scalar volume by naive surface nets (Gibson 1998), as an indexed triangle mesh
+ * (csrc/surface_nets.hip; torch-ngp's save_mesh does this with marching cubes on the host).  Additive: the ABI version stays.
+ * The output is a pure function of the input: no atomics, two calls give the same bits.
+ *
+ * Volume vol[i,j,k] f32, C-contiguous [R0,R1,R2] (k fastest), 2 <= R_a <= 1024.  Lattice point p(i,j,k) = lo + (i step_x,
+ * j step_y, k step_z), each coordinate lo_a + (float)i * step_a in f32 without contraction; lo [3], step [3] are HOST floats,
+ * step = (hi - lo) / (R - 1) formed by the caller in f32.
+ * A point is INSIDE iff vol > iso (strict): a NaN and a value equal to iso are outside.
+ * Cell (cx,cy,cz), 0 <= c_a <= R_a - 2, linear index (cx (R1-1) + cy)(R2-1) + cz; its corner q = 4 dx + 2 dy + dz is the point
+ * (cx+dx, cy+dy, cz+dz).  A cell is ACTIVE iff its 8 corners are neither all inside nor all outside.
+ *
+ * Vertices.  Every active cell has one vertex; its id is the rank of the cell among the active cells in linear cell order.
+ *   The 12 edges as (corner, corner), in this order:
+ *     along x (0,4) (1,5) (2,6) (3,7), along y (0,2) (1,3) (4,6) (5,7), along z (0,1) (2,3) (4,5) (6,7).
+ *   An edge whose ends differ in inside-ness crosses: with a its outside end, b its inside end and va, vb their values,
+ *     t = (iso - va) / (vb - va); if not 0 <= t <= 1 (va a NaN, or -inf against +inf): t = 1/2
+ *     crossing point: the coordinate along the edge's axis is pa + t * (pb - pa), the two others are the corners' own.
+ *   vertex = (sum of the crossing points, added to +0 in edge order, coordinate by coordinate) / (float)(their number).
+ *   All in f32, every operation rounded once (no contraction, IEEE division).
+ * Faces.  Cell (cx,cy,cz) owns the three lattice edges that leave its corner 0 along +x, +y, +z.  The owned edge along axis a
+ *   emits one quad iff its ends differ in inside-ness and the cell's two other coordinates are both >= 1 (the four cells around
+ *   the edge then exist, and all are active).  With (u, w) the axes after a in the cyclic order x, y, z, the quad's corners are
+ *   the vertices of the cells
+ *     v0 = c - e_u - e_w, v1 = c - e_w, v2 = c, v3 = c - e_u        (counter-clockwise seen from the axis' positive end)
+ *   in this order when corner 0 is the inside end and as (v0, v3, v2, v1) otherwise, so that the right-hand normal points from
+ *   the inside end to the outside end (along -grad of the volume, the convention of nsr_field_density_gradient's unit normal).
+ *   A quad is the triangles (q0,q1,q2), (q0,q2,q3).  Faces are ordered by (owning cell's linear index, axis).
+ *   The mesh is a closed oriented 2-manifold wherever the surface stays off the lattice's boundary; where it reaches it the
+ *   mesh is open (edges on the upper boundary planes are owned by no cell, those on the lower ones miss a neighbour).
+ *
+ * Two calls, because the output sizes are known only after a count:
+ *   nsr_surface_nets_count: fills `workspace` (nsr_surface_nets_workspace_bytes(R0,R1,R2) bytes, 16-byte aligned: a header
+ *     {V, Q, R0, R1, R2}, the scanned per-block offsets, cell_vertex int32 [cells]) and writes counts_out[0] = V (vertices),
+ *     counts_out[1] = Q (quads; 2 Q triangles) on the device.  No host read, capture-safe.
+ *   nsr_surface_nets_emit: from the same vol, iso and the workspace the count left: verts [V,3] f32 and faces [2 Q,3] int32.
+ *     It READS THE HEADER BACK ON THE HOST (20 bytes, one stream synchronisation -- the one entry point of the library that
+ *     does; it is not legal inside a stream capture) and refuses a V, Q or shape that is not the workspace's before anything
+ *     is launched: V and Q size the caller's outputs.  V == 0 (then Q == 0) is a no-op success; verts and faces may be NULL
+ *     where their size is 0.
+ * NSR_ERR_INVALID_ARG before any launch: an R_a outside [2, 1024] (checked first; the workspace size is 0 then), a NULL vol,
+ * workspace, counts_out, lo or step, a NULL verts with V > 0 or faces with Q > 0, a pointer not aligned to 4 bytes (workspace:
+ * 16), V > cells, Q > 3 cells, Q > 0 with V == 0, or the mismatch above.
+ * ------------------------------------------------------------------------------------------ */
+uint64_t nsr_surface_nets_workspace_bytes(uint32_t R0, uint32_t R1, uint32_t R2);
+int nsr_surface_nets_count(const float *vol, uint32_t R0, uint32_t R1, uint32_t R2, float iso, void *workspace,
+                           uint32_t *counts_out, nsr_stream_t stream);
+int nsr_surface_nets_emit(const float *vol, uint32_t R0, uint32_t R1, uint32_t R2, float iso, const float *lo, const float *step,
+                          void *workspace, uint32_t V, uint32_t Q, float *verts, int32_t *faces, nsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

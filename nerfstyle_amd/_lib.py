@@ -132,6 +132,9 @@ SIGNATURES = {
                           vp, u32, i32, f32, vp, vp, vp, vp]),
     'nsr_ssim_workspace_bytes': (u64, [u32, u32, u32]),
     'nsr_ssim': (i32, [vp, u32, u32, vp, u32, u32, u32, u32, u32, f32, vp, vp, vp, vp, vp, vp]),
+    'nsr_surface_nets_workspace_bytes': (u64, [u32, u32, u32]),
+    'nsr_surface_nets_count': (i32, [vp, u32, u32, u32, f32, vp, vp, vp]),
+    'nsr_surface_nets_emit': (i32, [vp, u32, u32, u32, f32, ctypes.POINTER(f32), ctypes.POINTER(f32), vp, u32, u32, vp, vp, vp]),
 }
 
 _lib = None

@@ -400,6 +400,23 @@ class Renderer(torch.nn.Module):
                                                                         mt['fars'], self.cfg.t_thresh)
         return {'normal_map': normal_map, 'weights_sum': weights_sum, 'depth': depth}
 
+    def extract_mesh(self, resolution=256, iso: float = 10.0, aabb=None, colors: bool = True, normals: bool = True,
+                     labels: bool = True):
+        """The scene's geometry as a triangle mesh (nerfstyle_amd.mesh.Mesh; `.save_ply(path)` writes it): the iso-surface
+        sigma = iso of the density on a lattice of `resolution` points an axis (an int or a triple, at most 1024) over `aabb`
+        ([x0,y0,z0,x1,y1,z1]; default: the model's box), by surface nets on the device.  sigma includes cfg.density_scale, as
+        every render sees it; iso = 10 is torch-ngp's default.  Per vertex, each from one fused launch over the vertices:
+          normals  the unit normal of model.density_gradient(verts, normalize=True), pointing out of the dense side like the
+                   faces' right-hand normals
+          colors   uint8, round to nearest of the sigmoid RGB of model.field(verts)
+          labels   int32, the argmax of the same call's class channels -- the region a stylisation would paint the vertex with
+                   (None for a model without class channels)
+        A switch that is off returns None there and launches nothing for it.  A view_dependent model has no colour without a
+        direction: its vertices are shaded with dirs = -normal, the surface seen head-on from outside.
+        No occupancy bookkeeping, no gradients.  Reads two counts on the host: not legal while a graph is captured."""
+        from .mesh import extract_mesh
+        return extract_mesh(self, resolution=resolution, iso=iso, aabb=aabb, colors=colors, normals=normals, labels=labels)
+
     def _use_spatial_order(self, n_rays: int, dense: bool) -> bool:
         if self.model._spatial_scatter_unsupported:
             return False                 # learnt from a backward that fell back (style_nerf._field.backward)
