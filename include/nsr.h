@@ -977,6 +977,53 @@ int nsr_surface_nets_count(const float *vol, uint32_t R0, uint32_t R1, uint32_t 
 int nsr_surface_nets_emit(const float *vol, uint32_t R0, uint32_t R1, uint32_t R2, float iso, const float *lo, const float *step,
                           void *workspace, uint32_t V, uint32_t Q, float *verts, int32_t *faces, nsr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh cleaning: connected components of an indexed triangle mesh, their statistics, and a filter that drops whole components
+ * (csrc/mesh_clean.hip; torch-ngp's clean_mesh does this on the host after its marching cubes).  Additive: the ABI version stays.
+ * Every output is a pure function of the input: two calls give the same bits.
+ *
+ * Mesh: verts f32 [V,3], faces int32 [F,3], 0 <= V, F < 2^31.
+ * Components.  Two vertices are joined when one face holds both; components are the transitive closure of that relation.
+ *   label[v] = the SMALLEST vertex id of v's component; a vertex in no face is a component of its own, label[v] = v.
+ *   Degenerate faces (repeated indices) and duplicate faces are ordinary input.
+ * Bad faces.  A face with any index outside [0, V) joins nothing, belongs to no component, is never emitted and is counted in
+ *   *bad_faces (a device integer).  No kernel dereferences such an index.
+ * Statistics, read at the roots (the r with label[r] == r); the arrays are indexed by vertex id and hold 0, 0 and the empty
+ *   box (+inf, -inf) at every vertex that is no root:
+ *     n_verts[r]; n_faces[r] (a face counts for the component of its vertices); lo[r], hi[r]: the exact f32 minimum and maximum
+ *     of the component's vertices, coordinate by coordinate (-0 orders below +0; vertices are assumed finite).
+ *   Integer adds, mins and maxes are order-free, so these kernels use atomics and are deterministic all the same.
+ * Filter.  keep [V] uint8, read at the roots: the caller's decision per component (the keep rule of nerfstyle_amd/mesh.py:
+ *   n_faces >= min_faces; dx^2 + dy^2 + dz^2 >= min_diagonal^2 with d = hi - lo, in f32 in this written order; optionally the
+ *   k components of the most faces among those, ties to the smaller label).  Vertices and faces of components that are not kept
+ *   go; the survivors keep their relative order; a surviving vertex's new id is its rank among the surviving vertices and the
+ *   faces are re-indexed; index_map[v] = the new id, or -1.  Ranks come from ballots and a scan of block totals, no atomics.
+ *
+ *   nsr_mesh_components: labels [V] int32 (also the union-find's parent array while the call runs) and *bad_faces.  A lock-free
+ *     union-find over the faces that hooks the larger root under the smaller id, then a flatten launch: the root of a component
+ *     is its minimum id whatever the interleaving.  No workspace, no host read.
+ *   nsr_mesh_component_stats: from labels as nsr_mesh_components left them.  A label outside [0, V) is skipped.
+ *   nsr_mesh_filter_count: fills `workspace` (nsr_mesh_filter_workspace_bytes(V, F) bytes, 16-byte aligned: a header
+ *     {Vk, Fk, V, F} and the scanned per-block offsets) and writes counts_out[0] = Vk (kept vertices), counts_out[1] = Fk (kept
+ *     faces) on the device.  No host read.
+ *   nsr_mesh_filter_emit: from the same faces, labels, keep and the workspace the count left: index_map [V], verts_out [Vk,3],
+ *     faces_out [Fk,3].  Like nsr_surface_nets_emit it READS THE HEADER BACK ON THE HOST (one stream synchronisation; not legal
+ *     inside a stream capture) and refuses a Vk, Fk, V or F that is not the workspace's before anything is launched.
+ * V == 0 or F == 0 are legal: no labels or labels[v] = v, Vk = Fk = 0 or the kept singletons; arrays of size 0 may be NULL.
+ * NSR_ERR_INVALID_ARG before any launch: V or F >= 2^31 (the workspace size is 0 then), a NULL array of non-zero size, a NULL
+ * bad_faces, workspace or counts_out, a pointer not aligned to 4 bytes (workspace: 16; keep: 1), Vk > V, Fk > F, Fk > 0 with
+ * Vk == 0, or the mismatch above.
+ * ------------------------------------------------------------------------------------------ */
+int nsr_mesh_components(const int32_t *faces, uint32_t V, uint32_t F, int32_t *labels, uint32_t *bad_faces, nsr_stream_t stream);
+int nsr_mesh_component_stats(const float *verts, const int32_t *faces, const int32_t *labels, uint32_t V, uint32_t F,
+                             uint32_t *n_verts, uint32_t *n_faces, float *lo, float *hi, nsr_stream_t stream);
+uint64_t nsr_mesh_filter_workspace_bytes(uint32_t V, uint32_t F);
+int nsr_mesh_filter_count(const int32_t *faces, const int32_t *labels, const uint8_t *keep, uint32_t V, uint32_t F, void *workspace,
+                          uint32_t *counts_out, nsr_stream_t stream);
+int nsr_mesh_filter_emit(const float *verts, const int32_t *faces, const int32_t *labels, const uint8_t *keep, uint32_t V,
+                         uint32_t F, void *workspace, uint32_t Vk, uint32_t Fk, int32_t *index_map, float *verts_out,
+                         int32_t *faces_out, nsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

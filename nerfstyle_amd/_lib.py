@@ -135,6 +135,11 @@ SIGNATURES = {
     'nsr_surface_nets_workspace_bytes': (u64, [u32, u32, u32]),
     'nsr_surface_nets_count': (i32, [vp, u32, u32, u32, f32, vp, vp, vp]),
     'nsr_surface_nets_emit': (i32, [vp, u32, u32, u32, f32, ctypes.POINTER(f32), ctypes.POINTER(f32), vp, u32, u32, vp, vp, vp]),
+    'nsr_mesh_components': (i32, [vp, u32, u32, vp, vp, vp]),
+    'nsr_mesh_component_stats': (i32, [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    'nsr_mesh_filter_workspace_bytes': (u64, [u32, u32]),
+    'nsr_mesh_filter_count': (i32, [vp, vp, vp, u32, u32, vp, vp, vp]),
+    'nsr_mesh_filter_emit': (i32, [vp, vp, vp, vp, u32, u32, vp, u32, u32, vp, vp, vp, vp]),
 }
 
 _lib = None

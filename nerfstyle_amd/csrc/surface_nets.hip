@@ -5,26 +5,22 @@
 // cell, so that the vertex ids -- the rank of a cell among the active ones in that order -- and the face order fall out of a
 // block-local rank plus the scanned block totals, with no atomics anywhere:
 //   k_sn_count     8 corner reads -> corner mask, active flag, owned quads (0..3); totals[block] = (vertices, quads)
-//   k_sn_scan      256 totals a block, exclusive in place, the block's sum to the next level (SN_SCAN entries a pass; the levels
-//                  are walked on the host: 1023^3 cells are 4.2 M blocks -> 16 K -> 64 -> 1)
-//   k_sn_scan_add  adds the scanned level above back into a level
+//   k_bs_scan, k_bs_scan_add (block_scan.h)  the totals scanned into exclusive offsets, level by level: 1023^3 cells are
+//                  4.2 M blocks -> 16 K -> 64 -> 1
 //   k_sn_vertices  recomputes the mask and the in-block rank; verts[id], cell_vertex[cell] = id
 //   k_sn_faces     a launch of its own (it reads its neighbours' ids): 4 corner reads, the owned edges' quads at their offsets
-// In-block ranks: wave64 ballots and a popcount below the lane (two ballots for the 2-bit quad count), then the four wave totals
-// through LDS.  Reads are coalesced along k; the four (x, y) rows a wave touches are re-read by its neighbours from L1/L2, they
+// In-block ranks (bs_block_rank): wave64 ballots and a popcount below the lane (two ballots for the 2-bit quad count), then the
+// four wave totals through LDS.  Reads are coalesced along k; the four (x, y) rows a wave touches are re-read by its neighbours from L1/L2, they
 // are not staged in LDS (a block's 256 cells wrap over rows of any length).  HBM traffic: the volume three times (count,
 // vertices, faces), cell_vertex and the outputs once.
 //
 // The whole file is compiled with contraction off: tests/mesh_ref.py reaches the vertices' bits with NumPy f32.
-#include "nsr_common.h"
+#include "block_scan.h"
 
 #pragma clang fp contract(off)
 
-#define SN_BLOCK 256
-#define SN_SCAN 256                      // totals per scan block (one a thread)
-#define SN_MAX_R 1024u
-#define SN_MAX_LEVELS 4                  // ceil(1023^3 / 256) = 4 181 880 -> 16 336 -> 64 -> 1
-#define SN_HEADER_WORDS 8                // V, Q, R0, R1, R2, 0, 0, 0
+#define SN_BLOCK BS_BLOCK
+#define SN_MAX_R 1024u                   // ceil(1023^3 / 256) = 4 181 880 block totals -> 16 336 -> 64 -> 1
 
 struct SnShape {
     uint32_t R0, R1, R2;                 // lattice points an axis
@@ -33,9 +29,7 @@ struct SnShape {
 };
 
 struct SnLayout {                        // byte offsets into the workspace, each a multiple of 16
-    uint32_t levels;
-    uint32_t n[SN_MAX_LEVELS];           // entries of level l (n[0]: the count kernel's blocks)
-    uint64_t off[SN_MAX_LEVELS];
+    BsLevels scan;                       // the header {V, Q, R0, R1, R2, 0, 0, 0} and the levels of block totals
     uint64_t cell_vertex;
     uint64_t bytes;
 };
@@ -50,19 +44,9 @@ static bool sn_shape(uint32_t R0, uint32_t R1, uint32_t R2, SnShape *s) {
 
 static SnLayout sn_layout(const SnShape &s) {
     SnLayout l;
-    uint64_t at = SN_HEADER_WORDS * 4;
-    uint32_t n = nsr_div_up(s.ncells, SN_BLOCK);
-    l.levels = 0;
-    for (;;) {
-        l.n[l.levels] = n;
-        l.off[l.levels] = at;
-        at += ((uint64_t)n * 8 + 15) & ~15ull;
-        l.levels++;
-        if (n <= SN_SCAN) break;
-        n = nsr_div_up(n, SN_SCAN);
-    }
-    l.cell_vertex = at;
-    l.bytes = at + (((uint64_t)s.ncells * 4 + 15) & ~15ull);
+    l.scan = bs_levels(nsr_div_up(s.ncells, SN_BLOCK));
+    l.cell_vertex = l.scan.end;
+    l.bytes = l.cell_vertex + (((uint64_t)s.ncells * 4 + 15) & ~15ull);
     return l;
 }
 
@@ -74,29 +58,6 @@ __device__ __forceinline__ void sn_cell(const SnShape &s, uint32_t c, uint32_t &
     cz = c - t * s.n2;
     cx = t / s.n1;
     cy = t - cx * s.n1;
-}
-
-// lanes below this one in the wave whose bit is set
-__device__ __forceinline__ uint32_t sn_below(unsigned long long ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// Exclusive rank of `count` (0..3) among the block's threads in thread order, and the block's total.  All threads call it.
-__device__ __forceinline__ uint32_t sn_block_rank(uint32_t count, uint32_t *s_wave, uint32_t &total) {
-    const unsigned long long b0 = __ballot(count & 1u), b1 = __ballot(count & 2u);
-    const uint32_t wave = threadIdx.x >> 6;
-    uint32_t rank = sn_below(b0) + 2u * sn_below(b1);
-    if ((threadIdx.x & 63) == 0) s_wave[wave] = (uint32_t)__popcll(b0) + 2u * (uint32_t)__popcll(b1);
-    __syncthreads();
-    total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < SN_BLOCK / 64; w++) {
-        const uint32_t t = s_wave[w];
-        if (w < wave) rank += t;
-        total += t;
-    }
-    __syncthreads();                                // s_wave is free for the next call
-    return rank;
 }
 
 // corner q = 4 dx + 2 dy + dz of cell (cx, cy, cz): the C order of vol[cx:cx+2, cy:cy+2, cz:cz+2]
@@ -141,52 +102,9 @@ __global__ void __launch_bounds__(SN_BLOCK) k_sn_count(const float *__restrict__
         nq = (uint32_t)__popc(sn_quads(m & 1u, m & 16u, m & 4u, m & 2u, cx, cy, cz));
     }
     uint32_t nv_total, nq_total;
-    sn_block_rank(active, s_wave, nv_total);
-    sn_block_rank(nq, s_wave, nq_total);
+    bs_block_rank(active, s_wave, nv_total);
+    bs_block_rank(nq, s_wave, nq_total);
     if (threadIdx.x == 0) totals[blockIdx.x] = make_uint2(nv_total, nq_total);
-}
-
-// t[0 .. n) in chunks of SN_SCAN: exclusive scan of each chunk in place, the chunk's sum to sums[block]; counts_out (the top
-// level only, one block, whose `sums` is the workspace header): the grand totals once more, and the shape into the header
-__global__ void __launch_bounds__(SN_SCAN) k_sn_scan(uint2 *__restrict__ t, uint32_t n, uint2 *__restrict__ sums,
-                                                     uint32_t *__restrict__ counts_out, SnShape s) {
-    __shared__ uint2 s_wave[SN_SCAN / 64];
-    const uint32_t i = blockIdx.x * SN_SCAN + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint2 mine = i < n ? t[i] : make_uint2(0u, 0u);
-    uint32_t x = mine.x, y = mine.y;                // inclusive over the wave
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t ux = __shfl_up(x, d), uy = __shfl_up(y, d);
-        if (lane >= d) x += ux, y += uy;
-    }
-    if (lane == 63) s_wave[wave] = make_uint2(x, y);
-    __syncthreads();
-    uint2 before = make_uint2(0u, 0u), total = make_uint2(0u, 0u);
-#pragma unroll
-    for (uint32_t w = 0; w < SN_SCAN / 64; w++) {
-        const uint2 sw = s_wave[w];
-        if (w < wave) before.x += sw.x, before.y += sw.y;
-        total.x += sw.x, total.y += sw.y;
-    }
-    if (i < n) t[i] = make_uint2(before.x + x - mine.x, before.y + y - mine.y);
-    if (threadIdx.x == 0) {
-        sums[blockIdx.x] = total;
-        if (counts_out) {                           // sums is the workspace header: the shape it was counted for beside the totals
-            counts_out[0] = total.x, counts_out[1] = total.y;
-            uint32_t *header = (uint32_t *)sums;
-            header[2] = s.R0, header[3] = s.R1, header[4] = s.R2;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(SN_SCAN) k_sn_scan_add(uint2 *__restrict__ t, uint32_t n, const uint2 *__restrict__ above) {
-    const uint32_t i = blockIdx.x * SN_SCAN + threadIdx.x;
-    if (i < n) {
-        const uint2 a = above[blockIdx.x];
-        uint2 v = t[i];
-        v.x += a.x, v.y += a.y;
-        t[i] = v;
-    }
 }
 
 struct SnBox {
@@ -210,7 +128,7 @@ __global__ void __launch_bounds__(SN_BLOCK) k_sn_vertices(const float *__restric
     }
     const uint32_t active = (m != 0u && m != 0xffu) ? 1u : 0u;
     uint32_t total;
-    const uint32_t id = offsets[blockIdx.x].x + sn_block_rank(active, s_wave, total);
+    const uint32_t id = offsets[blockIdx.x].x + bs_block_rank(active, s_wave, total);
     if (!active || id >= V) return;                 // id >= V: a V that is not this workspace's (refused on the host already)
 
     // the lattice coordinates of the cell's two planes an axis
@@ -263,7 +181,7 @@ __global__ void __launch_bounds__(SN_BLOCK) k_sn_faces(const float *__restrict__
                          sn_inside(vol[base + 1], iso), cx, cy, cz);
     }
     uint32_t total;
-    uint32_t q = offsets[blockIdx.x].y + sn_block_rank((uint32_t)__popc(quads), s_wave, total);
+    uint32_t q = offsets[blockIdx.x].y + bs_block_rank((uint32_t)__popc(quads), s_wave, total);
     if (!quads) return;
     // cells around the owned edge, counter-clockwise seen from the axis' positive end (normal +axis): the linear-index steps
     // back along the two other axes, in the cyclic order (y, z), (z, x), (x, y)
@@ -304,18 +222,8 @@ int nsr_surface_nets_count(const float *vol, uint32_t R0, uint32_t R1, uint32_t 
     const SnLayout l = sn_layout(s);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
-    uint32_t *header = (uint32_t *)ws;
-    uint2 *lv[SN_MAX_LEVELS];
-    for (uint32_t i = 0; i < l.levels; i++) lv[i] = (uint2 *)(ws + l.off[i]);
-
-    hipLaunchKernelGGL(k_sn_count, dim3(l.n[0]), dim3(SN_BLOCK), 0, st, vol, s, iso, lv[0]);
-    for (uint32_t i = 0; i < l.levels; i++) {
-        const bool top = i + 1 == l.levels;         // one block: its sum is the grand total -> header[0..1] and counts_out
-        hipLaunchKernelGGL(k_sn_scan, dim3(nsr_div_up(l.n[i], SN_SCAN)), dim3(SN_SCAN), 0, st, lv[i], l.n[i],
-                           top ? (uint2 *)header : lv[i + 1], top ? counts_out : (uint32_t *)nullptr, s);
-    }
-    for (uint32_t i = l.levels - 1; i-- > 0;)
-        hipLaunchKernelGGL(k_sn_scan_add, dim3(nsr_div_up(l.n[i], SN_SCAN)), dim3(SN_SCAN), 0, st, lv[i], l.n[i], lv[i + 1]);
+    hipLaunchKernelGGL(k_sn_count, dim3(l.scan.n[0]), dim3(SN_BLOCK), 0, st, vol, s, iso, (uint2 *)(ws + l.scan.off[0]));
+    bs_scan_levels(ws, l.scan, counts_out, make_uint3(R0, R1, R2), st);   // the shape it was counted for beside the totals
     return nsr_launch_status();
 }
 
@@ -343,13 +251,13 @@ int nsr_surface_nets_emit(const float *vol, uint32_t R0, uint32_t R1, uint32_t R
 
     const SnLayout l = sn_layout(s);
     char *ws = (char *)workspace;
-    const uint2 *offsets = (const uint2 *)(ws + l.off[0]);
+    const uint2 *offsets = (const uint2 *)(ws + l.scan.off[0]);
     int32_t *cell_vertex = (int32_t *)(ws + l.cell_vertex);
     SnBox box;
     for (int a = 0; a < 3; a++) box.lo[a] = lo[a], box.step[a] = step[a];
-    hipLaunchKernelGGL(k_sn_vertices, dim3(l.n[0]), dim3(SN_BLOCK), 0, st, vol, s, iso, box, offsets, V, verts, cell_vertex);
+    hipLaunchKernelGGL(k_sn_vertices, dim3(l.scan.n[0]), dim3(SN_BLOCK), 0, st, vol, s, iso, box, offsets, V, verts, cell_vertex);
     if (Q != 0)
-        hipLaunchKernelGGL(k_sn_faces, dim3(l.n[0]), dim3(SN_BLOCK), 0, st, vol, s, iso, offsets, Q,
+        hipLaunchKernelGGL(k_sn_faces, dim3(l.scan.n[0]), dim3(SN_BLOCK), 0, st, vol, s, iso, offsets, Q,
                            (const int32_t *)cell_vertex, faces);
     return nsr_launch_status();
 }

@@ -9,8 +9,16 @@ pure function of the volume, no atomics.
 or by hand: `density_volume` samples sigma on a lattice with the fused sigma-only forward, `surface_nets` turns any device volume
 into (verts, faces).  NOT capture-legal: the sizes of the outputs are known only after a count, so `surface_nets` reads two
 integers back on the host between its two launches (and nsr_surface_nets_emit checks them once more).  Opt-in: nothing else in
-the package calls it."""
+the package calls it.
+
+Mesh cleaning (csrc/mesh_clean.hip; include/nsr.h, "Mesh cleaning"): `connected_components` labels every vertex with the smallest
+vertex id of its component (a lock-free union-find on the device whose result does not depend on the interleaving),
+`component_stats` gives each component's vertex and face counts and its box, `filter_components` / `Mesh.clean` /
+`extract_mesh(min_faces=..., min_diagonal=..., keep_largest=...)` drop whole components -- the floaters of a NeRF density --
+and re-index what stays, order preserved, bit for bit a function of the input.  The same host reads, so not capture-legal
+either."""
 import ctypes
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Optional
 
@@ -66,6 +74,136 @@ def surface_nets(volume, iso, lo, hi):
         L.check(L.lib().nsr_surface_nets_emit(vol_p, R[0], R[1], R[2], float(iso), lo32.ctypes.data_as(fp), step.ctypes.data_as(fp),
                                               L.p(ws), V, Q, L.p(verts), L.p(faces) if Q else None, L.stream()), 'surface_nets_emit')
     return verts, faces
+
+
+# ---- mesh cleaning -----------------------------------------------------------------------------------------------------------
+ComponentStats = namedtuple('ComponentStats', 'roots n_verts n_faces lo hi')
+
+
+def _check_faces(faces, who):
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError('{}: faces must be an int32 [F,3] tensor; got {} {}'.format(
+            who, getattr(faces, 'dtype', type(faces)), tuple(getattr(faces, 'shape', ()))))
+    return faces.detach().contiguous()
+
+
+def _check_verts(verts, who):
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError('{}: verts must be a float32 [V,3] tensor; got {} {}'.format(
+            who, getattr(verts, 'dtype', type(verts)), tuple(getattr(verts, 'shape', ()))))
+    return verts.detach().contiguous()
+
+
+def _check_keep_rule(min_faces, min_diagonal, keep_largest, who):
+    if int(min_faces) != min_faces or not 0 <= min_faces < 2 ** 31:
+        raise ValueError('{}: min_faces must be an integer in 0 .. 2^31 - 1; got {}'.format(who, min_faces))
+    if not float(min_diagonal) >= 0.0:
+        raise ValueError('{}: min_diagonal must be >= 0; got {}'.format(who, min_diagonal))
+    if keep_largest is not None and (int(keep_largest) != keep_largest or keep_largest < 1):
+        raise ValueError('{}: keep_largest must be None or an integer >= 1; got {}'.format(who, keep_largest))
+
+
+def _no_capture(who):
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('{} reads its counts on the host: it cannot be captured into a graph'.format(who))
+
+
+def connected_components(faces, num_verts):
+    """labels int32 [V] of the mesh (faces int32 [F,3] on the device, V = num_verts): labels[v] is the smallest vertex id of v's
+    component; a vertex in no face is its own.  A face with an index outside [0, V) joins nothing and raises ValueError after the
+    host read of the device's bad-face count.  Not legal while a graph is captured.  CPU tensors are refused."""
+    faces = _check_faces(faces, 'connected_components')
+    V, F = int(num_verts), int(faces.shape[0])
+    if not 0 <= V < 2 ** 31 or F >= 2 ** 31:
+        raise ValueError('connected_components: V and F must be below 2^31; got {} and {}'.format(V, F))
+    faces_p = L.p(faces)
+    _no_capture('connected_components')
+    labels = torch.empty(V, dtype=torch.int32, device=faces.device)
+    bad = torch.empty(1, dtype=torch.int32, device=faces.device)
+    L.check(L.lib().nsr_mesh_components(faces_p, V, F, L.p(labels), L.p(bad), L.stream()), 'mesh_components')
+    n_bad = int(bad.item())                                               # the host read
+    if n_bad:
+        raise ValueError('connected_components: {} of {} faces hold a vertex index outside [0, {})'.format(n_bad, F, V))
+    return labels
+
+
+def _stats_arrays(verts, faces, labels):
+    """n_verts, n_faces [V] int32 and lo, hi [V,3] f32, indexed by vertex id and meaningful at the roots"""
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    dev = verts.device
+    n_verts = torch.empty(V, dtype=torch.int32, device=dev)
+    n_faces = torch.empty(V, dtype=torch.int32, device=dev)
+    lo = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    hi = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    L.check(L.lib().nsr_mesh_component_stats(L.p(verts), L.p(faces), L.p(labels), V, F, L.p(n_verts), L.p(n_faces), L.p(lo), L.p(hi),
+                                             L.stream()), 'mesh_component_stats')
+    return n_verts, n_faces, lo, hi
+
+
+def component_stats(verts, faces, labels):
+    """ComponentStats(roots, n_verts, n_faces, lo, hi) of the mesh's components, one row a component in ascending order of the
+    root (its label, the smallest vertex id): roots, n_verts, n_faces int32 [C]; lo, hi f32 [C,3], the exact box of the
+    component's vertices.  `labels` as connected_components returns them.  All on the device; one host read (C)."""
+    verts, faces = _check_verts(verts, 'component_stats'), _check_faces(faces, 'component_stats')
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or labels.shape != (verts.shape[0],):
+        raise ValueError('component_stats: labels must be an int32 [V] tensor; got {} {}'.format(
+            getattr(labels, 'dtype', type(labels)), tuple(getattr(labels, 'shape', ()))))
+    labels = labels.detach().contiguous()
+    for t in (verts, faces, labels):
+        L.p(t)
+    _no_capture('component_stats')
+    n_verts, n_faces, lo, hi = _stats_arrays(verts, faces, labels)
+    V = int(verts.shape[0])
+    roots = torch.nonzero(labels == torch.arange(V, dtype=torch.int32, device=labels.device)).reshape(-1)     # ascending
+    return ComponentStats(roots.to(torch.int32), n_verts[roots], n_faces[roots], lo[roots], hi[roots])
+
+
+def keep_components(stats, num_verts, min_faces=0, min_diagonal=0.0, keep_largest=None):
+    """The keep rule on ComponentStats -> keep uint8 [V], set at the roots of the kept components.  A component is kept iff
+    n_faces >= min_faces, dx^2 + dy^2 + dz^2 >= min_diagonal^2 (d = hi - lo; f32, in this written order) and, with keep_largest
+    = k, it is among the k of the most faces of those that passed (ties to the smaller label).  Elementwise work over the
+    roots: torch on the device."""
+    _check_keep_rule(min_faces, min_diagonal, keep_largest, 'keep_components')
+    d = stats.hi - stats.lo
+    diag2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+    threshold = float(np.float32(min_diagonal) * np.float32(min_diagonal))
+    ok = (stats.n_faces >= int(min_faces)) & (diag2 >= threshold)
+    roots = stats.roots.to(torch.int64)
+    if keep_largest is not None:
+        cand = torch.nonzero(ok).reshape(-1)
+        key = (0x7fffffff - stats.n_faces[cand].to(torch.int64)) * (1 << 32) + roots[cand]       # most faces first, then the label
+        first = cand[torch.argsort(key)[:int(keep_largest)]]
+        ok = torch.zeros_like(ok)
+        ok[first] = True
+    keep = torch.zeros(int(num_verts), dtype=torch.uint8, device=roots.device)
+    keep[roots] = ok.to(torch.uint8)
+    return keep
+
+
+def filter_components(verts, faces, min_faces=0, min_diagonal=0.0, keep_largest=None):
+    """Drops the components the keep rule (keep_components) refuses -> (verts [Vk,3], faces [Fk,3], index_map int32 [V]).  The
+    survivors keep their relative order; a surviving vertex's new id is its rank among them, index_map[v] is that id or -1, and
+    the faces are re-indexed.  Bit for bit a function of the input.  Raises ValueError on a face index outside [0, V).  Host
+    reads of the counts: not legal while a graph is captured.  CPU tensors are refused."""
+    verts, faces = _check_verts(verts, 'filter_components'), _check_faces(faces, 'filter_components')
+    _check_keep_rule(min_faces, min_diagonal, keep_largest, 'filter_components')
+    L.p(verts)
+    labels = connected_components(faces, verts.shape[0])
+    stats = component_stats(verts, faces, labels)
+    keep = keep_components(stats, verts.shape[0], min_faces, min_diagonal, keep_largest)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    dev = verts.device
+    nbytes = int(L.lib().nsr_mesh_filter_workspace_bytes(V, F))
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    L.check(L.lib().nsr_mesh_filter_count(L.p(faces), L.p(labels), L.p(keep), V, F, L.p(ws), L.p(counts), L.stream()), 'mesh_filter_count')
+    Vk, Fk = (int(c) for c in counts.cpu().tolist())                      # the host read
+    index_map = torch.empty(V, dtype=torch.int32, device=dev)
+    verts_out = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+    faces_out = torch.empty(Fk, 3, dtype=torch.int32, device=dev)
+    L.check(L.lib().nsr_mesh_filter_emit(L.p(verts), L.p(faces), L.p(labels), L.p(keep), V, F, L.p(ws), Vk, Fk, L.p(index_map),
+                                         L.p(verts_out), L.p(faces_out), L.stream()), 'mesh_filter_emit')
+    return verts_out, faces_out, index_map
 
 
 def lattice_points(lo32, step, shape, start, end, device):
@@ -147,6 +285,13 @@ class Mesh:
             f.write(vrec.tobytes())
             f.write(frec.tobytes())
 
+    def clean(self, min_faces=0, min_diagonal=0.0, keep_largest=None):
+        """-> a new Mesh without the components filter_components drops; colors, normals and labels follow the vertices."""
+        verts, faces, index_map = filter_components(self.verts, self.faces, min_faces, min_diagonal, keep_largest)
+        kept = index_map >= 0                                             # a boolean mask keeps the order
+        pick = lambda t: None if t is None else t[kept]
+        return Mesh(verts, faces, pick(self.colors), pick(self.normals), pick(self.labels))
+
 
 def colors_uint8(rgb):
     """sigmoid colours in [0,1] -> uint8, round to nearest"""
@@ -154,8 +299,10 @@ def colors_uint8(rgb):
 
 
 @torch.no_grad()
-def extract_mesh(renderer, resolution=256, iso=10.0, aabb=None, colors=True, normals=True, labels=True, chunk=1 << 24):
+def extract_mesh(renderer, resolution=256, iso=10.0, aabb=None, colors=True, normals=True, labels=True, chunk=1 << 24,
+                 min_faces=0, min_diagonal=0.0, keep_largest=None):
     """Renderer.extract_mesh (its docstring states the interface)."""
+    _check_keep_rule(min_faces, min_diagonal, keep_largest, 'extract_mesh')
     model = renderer.model
     if aabb is None:
         mn, sz = model._bbox()
@@ -166,6 +313,8 @@ def extract_mesh(renderer, resolution=256, iso=10.0, aabb=None, colors=True, nor
     vol = density_volume(model, lo, hi, resolution, density_scale=renderer.cfg.density_scale, chunk=chunk)
     verts, faces = surface_nets(vol, iso, lo, hi)
     del vol
+    if min_faces != 0 or min_diagonal != 0.0 or keep_largest is not None:
+        verts, faces, _ = filter_components(verts, faces, min_faces, min_diagonal, keep_largest)     # dropped vertices are never shaded
     mesh = Mesh(verts, faces)
     want_field = colors or (labels and model.class_dim > 0)
     nrm = None

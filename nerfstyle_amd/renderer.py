@@ -401,7 +401,7 @@ class Renderer(torch.nn.Module):
         return {'normal_map': normal_map, 'weights_sum': weights_sum, 'depth': depth}
 
     def extract_mesh(self, resolution=256, iso: float = 10.0, aabb=None, colors: bool = True, normals: bool = True,
-                     labels: bool = True):
+                     labels: bool = True, min_faces: int = 0, min_diagonal: float = 0.0, keep_largest=None):
         """The scene's geometry as a triangle mesh (nerfstyle_amd.mesh.Mesh; `.save_ply(path)` writes it): the iso-surface
         sigma = iso of the density on a lattice of `resolution` points an axis (an int or a triple, at most 1024) over `aabb`
         ([x0,y0,z0,x1,y1,z1]; default: the model's box), by surface nets on the device.  sigma includes cfg.density_scale, as
@@ -413,9 +413,15 @@ class Renderer(torch.nn.Module):
                    (None for a model without class channels)
         A switch that is off returns None there and launches nothing for it.  A view_dependent model has no colour without a
         direction: its vertices are shaded with dirs = -normal, the surface seen head-on from outside.
-        No occupancy bookkeeping, no gradients.  Reads two counts on the host: not legal while a graph is captured."""
+        min_faces, min_diagonal, keep_largest: mesh cleaning (mesh.filter_components).  A connected component of the mesh stays
+        iff it has at least min_faces triangles, its box's diagonal is at least min_diagonal (world units) and, with
+        keep_largest = k, it is among the k components of the most triangles that passed; the floaters of a density trained on
+        few views go this way.  The filter runs on the device between the extractor and the per-vertex launches, so dropped
+        vertices are never shaded.  With the defaults none of it is called.
+        No occupancy bookkeeping, no gradients.  Reads its counts on the host: not legal while a graph is captured."""
         from .mesh import extract_mesh
-        return extract_mesh(self, resolution=resolution, iso=iso, aabb=aabb, colors=colors, normals=normals, labels=labels)
+        return extract_mesh(self, resolution=resolution, iso=iso, aabb=aabb, colors=colors, normals=normals, labels=labels,
+                            min_faces=min_faces, min_diagonal=min_diagonal, keep_largest=keep_largest)
 
     def _use_spatial_order(self, n_rays: int, dense: bool) -> bool:
         if self.model._spatial_scatter_unsupported:
