@@ -21,7 +21,7 @@ EXTRA_FLAGS = {'field.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'field_normal.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'render_infer.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'field_bwd_gout.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form']}
-HEADERS = ['nsr_common.h', 'rm_util.h', 'rm_probe.h', 'philox.h', 'ray_pose.h', 'table_scatter.h', 'lattice.h', 'mfma_tiles.h', 'field_common.h', 'field_bwd.h', 'block_scan.h', 'uf_core.h',
+HEADERS = ['nsr_common.h', 'fixed_sum.h', 'seg_sum.h', 'rm_util.h', 'rm_probe.h', 'philox.h', 'ray_pose.h', 'table_scatter.h', 'lattice.h', 'mfma_tiles.h', 'field_common.h', 'field_bwd.h', 'block_scan.h', 'uf_core.h',
            os.path.join('..', '..', 'include', 'nsr.h')]
 FLAGS = ['-O3', '-fPIC', '-std=c++17', '--offload-arch=' + ARCH, '-Wall', '-Wno-unused-function']
 

@@ -7,7 +7,7 @@
 //                    workspace header, and the totals once more to counts_out
 //   k_bs_scan_add    adds the scanned level above back into a level
 #pragma once
-#include "nsr_common.h"
+#include "fixed_sum.h"
 
 #define BS_BLOCK 256
 #define BS_SCAN 256                      // totals per scan block (one a thread)
@@ -69,13 +69,8 @@ static __global__ void __launch_bounds__(BS_SCAN) k_bs_scan(uint2 *__restrict__ 
     __shared__ uint2 s_wave[BS_SCAN / 64];
     const uint32_t i = blockIdx.x * BS_SCAN + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint2 mine = i < n ? t[i] : make_uint2(0u, 0u);
-    uint32_t x = mine.x, y = mine.y;                // inclusive over the wave
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t ux = __shfl_up(x, d), uy = __shfl_up(y, d);
-        if (lane >= d) x += ux, y += uy;
-    }
-    if (lane == 63) s_wave[wave] = make_uint2(x, y);
+    const uint2 incl = nsr_wave_scan(mine);
+    if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     uint2 before = make_uint2(0u, 0u), total = make_uint2(0u, 0u);
 #pragma unroll
@@ -84,7 +79,7 @@ static __global__ void __launch_bounds__(BS_SCAN) k_bs_scan(uint2 *__restrict__ 
         if (w < wave) before.x += sw.x, before.y += sw.y;
         total.x += sw.x, total.y += sw.y;
     }
-    if (i < n) t[i] = make_uint2(before.x + x - mine.x, before.y + y - mine.y);
+    if (i < n) t[i] = make_uint2(before.x + incl.x - mine.x, before.y + incl.y - mine.y);
     if (threadIdx.x == 0) {
         sums[blockIdx.x] = total;
         if (counts_out) {                           // sums is the workspace header: what was counted beside the totals

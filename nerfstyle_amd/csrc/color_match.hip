@@ -8,7 +8,7 @@
 // are bound by memory traffic and move 16 B per lane per access where the layout allows: a stride-4 row is one float4;
 // four stride-3 rows are three float4 when their first byte is 16-byte aligned, scalar loads otherwise.  Which loads are
 // used never changes the arithmetic or its order.
-#include "nsr_common.h"
+#include "fixed_sum.h"
 
 #define CM_BLOCK 256
 #define CM_WAVES (CM_BLOCK / 64)
@@ -37,30 +37,10 @@ __device__ __forceinline__ void cm_add(CmAcc &a, float rf, float gf, float bf) {
     a.s[6] += g * g; a.s[7] += g * b; a.s[8] += b * b;
 }
 
-// sum over the block in a fixed order: butterfly over the 64 lanes, then the waves in ascending order (thread 0 holds it)
-__device__ __forceinline__ void cm_block_sum(CmAcc &a, double (*red)[9]) {
-#pragma unroll
-    for (int k = 0; k < 9; k++)
-        for (int off = 32; off >= 1; off >>= 1) a.s[k] += __shfl_xor(a.s[k], off, 64);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) red[threadIdx.x >> 6][k] = a.s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            double s = 0.0;
-            for (int w = 0; w < CM_WAVES; w++) s += red[w][k];
-            a.s[k] = s;
-        }
-    }
-}
-
 template <int STRIDE>
 __global__ void __launch_bounds__(CM_BLOCK)
 k_color_moments(const float *__restrict__ rows, uint64_t n, double *__restrict__ partials) {
-    __shared__ double red[CM_WAVES][9];
+    __shared__ double red[9][CM_WAVES];
     CmAcc a;
 #pragma unroll
     for (int k = 0; k < 9; k++) a.s[k] = 0.0;
@@ -94,17 +74,17 @@ k_color_moments(const float *__restrict__ rows, uint64_t n, double *__restrict__
             }
         }
     }
-    cm_block_sum(a, red);
+    nsr_block_sum_stage(a.s, red);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) partials[(uint64_t)blockIdx.x * 9 + k] = a.s[k];
+        for (int k = 0; k < 9; k++) partials[(uint64_t)blockIdx.x * 9 + k] = nsr_block_sum_col<CM_WAVES>(red[k]);
     }
 }
 
-// one block: thread t adds the partials of blocks t, t + 256, ... in that order, then the block sum above
+// one block: thread t adds the partials of blocks t, t + 256, ... in that order, then the block sum
 __global__ void __launch_bounds__(CM_BLOCK)
 k_color_moments_final(const double *__restrict__ partials, uint32_t nblocks, double *__restrict__ moments) {
-    __shared__ double red[CM_WAVES][9];
+    __shared__ double red[9][CM_WAVES];
     CmAcc a;
 #pragma unroll
     for (int k = 0; k < 9; k++) a.s[k] = 0.0;
@@ -112,10 +92,10 @@ k_color_moments_final(const double *__restrict__ partials, uint32_t nblocks, dou
 #pragma unroll
         for (int k = 0; k < 9; k++) a.s[k] += partials[(uint64_t)b * 9 + k];
     }
-    cm_block_sum(a, red);
+    nsr_block_sum_stage(a.s, red);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) moments[k] = a.s[k];
+        for (int k = 0; k < 9; k++) moments[k] = nsr_block_sum_col<CM_WAVES>(red[k]);
     }
 }
 

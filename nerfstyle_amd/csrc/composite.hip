@@ -18,11 +18,12 @@
 // (tests: <= 2e-5 absolute), and are bit-identical from run to run.
 //
 // The loss kernel is one thread per ray (value + gradient in one pass, targets gathered through the pixel indices), a
-// block tree for the value and a second one-block kernel that adds the block partials in a fixed order (cp_block_sum2 in both).
-#include "nsr_common.h"
+// block sum for the value and a second one-block kernel that adds the block partials in a fixed order (fixed_sum.h in both).
+#include "seg_sum.h"
 
 #define CP_MAXC 16
 #define CP_BLOCK 256
+static_assert(CP_BLOCK == SEG_BLOCK, "seg_blocks counts blocks of SEG_BLOCK threads");
 
 #define CP_DPP(old, v, ctrl, rm, bm)                                                                                  \
     __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, (float)(old)), __builtin_bit_cast(int, (float)(v)), \
@@ -453,20 +454,19 @@ struct LossArgs {
     uint32_t nblocks;
 };
 
-// fixed-order block tree over two values: true on thread 0, which leaves with the block's sums in (x, y)
-__device__ __forceinline__ bool cp_block_sum2(float &x, float &y) {
-    __shared__ float red[2][CP_BLOCK / 64];
-    for (int off = 32; off >= 1; off >>= 1) { x += __shfl_xor(x, off, 64); y += __shfl_xor(y, off, 64); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = x; red[1][threadIdx.x >> 6] = y; }
-    __syncthreads();
-    if (threadIdx.x != 0) return false;
-    x = y = 0.0f;
-    for (int w = 0; w < CP_BLOCK / 64; w++) { x += red[0][w]; y += red[1][w]; }
-    return true;
+// the block's (mse, ce) to partials[blockIdx.x]; every thread of the block calls it
+__device__ __forceinline__ void cp_loss_partials(const LossArgs &a, float mse, float ce, float (&red)[2][CP_BLOCK / 64]) {
+    const float v[2] = {mse, ce};
+    nsr_block_sum_stage(v, red);
+    if (threadIdx.x == 0) {
+        a.partials[blockIdx.x * 2] = nsr_block_sum_col<CP_BLOCK / 64>(red[0]);
+        a.partials[blockIdx.x * 2 + 1] = nsr_block_sum_col<CP_BLOCK / 64>(red[1]);
+    }
 }
 
 __global__ void __launch_bounds__(CP_BLOCK)
 k_recon_loss(LossArgs a) {
+    __shared__ float red[2][CP_BLOCK / 64];
     const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
     const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
     float mse = 0.0f, ce = 0.0f;
@@ -492,19 +492,18 @@ k_recon_loss(LossArgs a) {
             for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
         }
     }
-    if (cp_block_sum2(mse, ce)) {
-        a.partials[blockIdx.x * 2] = mse;
-        a.partials[blockIdx.x * 2 + 1] = ce;
-    }
+    cp_loss_partials(a, mse, ce, red);
 }
 
 __global__ void __launch_bounds__(CP_BLOCK)
 k_recon_loss_final(LossArgs a) {
-    float mse = 0.0f, ce = 0.0f;
-    for (uint32_t b = threadIdx.x; b < a.nblocks; b += CP_BLOCK) { mse += a.partials[b * 2]; ce += a.partials[b * 2 + 1]; }
-    if (cp_block_sum2(mse, ce)) {
-        const float m = mse / (3.0f * (float)a.N);
-        const float c = ce / (float)a.N * a.ce_lambda;
+    __shared__ float red[2][CP_BLOCK / 64];
+    float v[2] = {0.0f, 0.0f};              // mse, ce
+    for (uint32_t b = threadIdx.x; b < a.nblocks; b += CP_BLOCK) { v[0] += a.partials[b * 2]; v[1] += a.partials[b * 2 + 1]; }
+    nsr_block_sum_stage(v, red);
+    if (threadIdx.x == 0) {
+        const float m = nsr_block_sum_col<CP_BLOCK / 64>(red[0]) / (3.0f * (float)a.N);
+        const float c = nsr_block_sum_col<CP_BLOCK / 64>(red[1]) / (float)a.N * a.ce_lambda;
         const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
         a.out[0] = (m + c) * s;
         a.out[1] = m;
@@ -524,6 +523,7 @@ struct WLossArgs {
 
 __global__ void __launch_bounds__(CP_BLOCK)
 k_recon_loss_weighted(WLossArgs wa) {
+    __shared__ float red[2][CP_BLOCK / 64];
     const LossArgs &a = wa.l;
     const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
     const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
@@ -554,10 +554,7 @@ k_recon_loss_weighted(WLossArgs wa) {
             for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
         }
     }
-    if (cp_block_sum2(mse, ce)) {
-        a.partials[blockIdx.x * 2] = mse;
-        a.partials[blockIdx.x * 2 + 1] = ce;
-    }
+    cp_loss_partials(a, mse, ce, red);
 }
 
 // k_recon_loss_weighted with a gain per frame and colour channel (per-frame exposure and white balance): ray n of segment n / K,
@@ -576,6 +573,7 @@ struct ELossArgs {
 
 __global__ void __launch_bounds__(CP_BLOCK)
 k_recon_loss_exposure(ELossArgs ea) {
+    __shared__ float red[2][CP_BLOCK / 64];
     const LossArgs &a = ea.w.l;
     const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
     const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
@@ -612,31 +610,11 @@ k_recon_loss_exposure(ELossArgs ea) {
             for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
         }
     }
-    if (cp_block_sum2(mse, ce)) {
-        a.partials[blockIdx.x * 2] = mse;
-        a.partials[blockIdx.x * 2 + 1] = ce;
-    }
+    cp_loss_partials(a, mse, ce, red);
 }
 
-// grad_exposure[f] = ln2 * sum of term over the rays of the segments naming f, in fp64, in the order of the pose backward of
-// frame_batch.hip (k_frames_bwd_*) with three sums for its twelve.  seg_partials is [S][B][3] f64, B = cp_exp_seg_blocks(K):
-//   K <  CP_EXP_THREAD_K   k_exposure_seg_thread: a thread per segment adds its K rays in order (B = 1)
-//   K >= CP_EXP_THREAD_K   k_exposure_seg_block: block s * B + b takes rays b * 256 + t, strided by B * 256, of segment s; per
-//                          thread in that order, then the xor tree over the wave (offsets 32 .. 1), then the four waves in order;
-//                          B = ceil(K / 256) capped at CP_EXP_MAX_SEG_BLOCKS
-// k_exposure_final, a wave per frame: the segments in ascending s, 64 at a time (a ballot of seg_frame[s] == f, then the set
-// bits from the lowest); for a segment naming the frame, lanes 0..2 add its B partials in order and then that sum to the
-// frame's; the frame's sum times ln2 is rounded to fp32 once.  A frame no segment names meets no add and gets +0.0; a segment
-// naming no frame writes no partial and none of it is read.  No atomics, no counters; every term and partial read was written
-// earlier in this call.
-#define CP_EXP_THREAD_K 64u
-#define CP_EXP_MAX_SEG_BLOCKS 64u
-static inline uint32_t cp_exp_seg_blocks(uint32_t K) {
-    if (K < CP_EXP_THREAD_K) return 1u;
-    const uint32_t b = nsr_div_up(K, CP_BLOCK);
-    return b < CP_EXP_MAX_SEG_BLOCKS ? b : CP_EXP_MAX_SEG_BLOCKS;
-}
-
+// grad_exposure[f] = ln2 * sum of term over the rays of the segments naming f, in fp64: the three parts of seg_sum.h with three
+// sums per segment, seg_partials [S][B][3]; the frame's sum times ln2 is rounded to fp32 once.
 __global__ void __launch_bounds__(CP_BLOCK)
 k_exposure_seg_thread(const float *__restrict__ term, const int32_t *__restrict__ seg_frame, uint32_t F, uint32_t S, uint32_t K,
                       double *__restrict__ seg_partials) {
@@ -658,49 +636,23 @@ k_exposure_seg_block(const float *__restrict__ term, const int32_t *__restrict__
                      double *__restrict__ seg_partials) {
     __shared__ double red[3][CP_BLOCK / 64];
     const uint32_t s = blockIdx.x / B, b = blockIdx.x - s * B;
-    if ((uint32_t)seg_frame[s] >= F) return;                   // the whole block: nobody waits at the barrier
+    if ((uint32_t)seg_frame[s] >= F) return;                   // the whole block: nobody waits at the block sum's barrier
     double acc[3] = {0.0, 0.0, 0.0};
     const float *t = term + (size_t)s * K * 3;
     for (uint32_t k = b * CP_BLOCK + threadIdx.x; k < K; k += B * CP_BLOCK) {
 #pragma unroll
         for (int c = 0; c < 3; c++) acc[c] += (double)t[(size_t)k * 3 + c];
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) acc[c] += __shfl_xor(acc[c], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) red[c][threadIdx.x >> 6] = acc[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double sum = 0.0;
-        for (int w = 0; w < CP_BLOCK / 64; w++) sum += red[threadIdx.x][w];
-        seg_partials[(size_t)blockIdx.x * 3 + threadIdx.x] = sum;
-    }
+    nsr_block_sum_stage(acc, red);
+    if (threadIdx.x < 3) seg_partials[(size_t)blockIdx.x * 3 + threadIdx.x] = nsr_block_sum_col<CP_BLOCK / 64>(red[threadIdx.x]);
 }
 
 __global__ void __launch_bounds__(64)
 k_exposure_final(const double *__restrict__ seg_partials, const int32_t *__restrict__ seg_frame, uint32_t S, uint32_t B,
                  float *__restrict__ grad_exposure) {
     const int32_t f = (int32_t)blockIdx.x;
-    const uint32_t lane = threadIdx.x;
-    double acc = 0.0;
-    for (uint32_t base = 0; base < S; base += 64u) {
-        const uint32_t mine = base + lane;
-        uint64_t named = __ballot(mine < S && seg_frame[mine] == f);
-        while (named) {
-            const uint32_t s = base + (uint32_t)__ffsll((long long)named) - 1u;
-            named &= named - 1u;
-            if (lane < 3u) {
-                double t = 0.0;
-                for (uint32_t b = 0; b < B; b++) t += seg_partials[((size_t)s * B + b) * 3 + lane];
-                acc += t;
-            }
-        }
-    }
-    if (lane < 3u) grad_exposure[(size_t)f * 3 + lane] = (float)(0.6931471805599453 * acc);
+    const double acc = seg_frame_sum(seg_frame, S, B, seg_partials, 3u, 0u, 3u, [f](int32_t named) { return named == f; });
+    if (threadIdx.x < 3u) grad_exposure[(size_t)f * 3 + threadIdx.x] = (float)(0.6931471805599453 * acc);
 }
 
 // 256 CUs x 8 blocks of 4 waves: the persistent grid of the ray kernels, the cap of the loss grid and with it the loss workspace
@@ -886,7 +838,7 @@ int nsr_recon_loss_weighted(const float *rgb_map, const float *classes, uint32_t
 static constexpr uint64_t CP_EXP_WS_SEG = (uint64_t)CP_MAX_BLOCKS * 2 * sizeof(float);
 static_assert(CP_EXP_WS_SEG % 8 == 0, "seg_partials are doubles");
 static uint64_t cp_exp_ws_term(uint32_t S, uint32_t K) {
-    return CP_EXP_WS_SEG + (uint64_t)S * cp_exp_seg_blocks(K) * 3 * sizeof(double);
+    return CP_EXP_WS_SEG + (uint64_t)S * seg_blocks(K) * 3 * sizeof(double);
 }
 
 uint64_t nsr_recon_loss_exposure_workspace_bytes(uint32_t N, uint32_t F, uint32_t S, uint32_t K) {
@@ -904,7 +856,7 @@ int nsr_recon_loss_exposure(const float *rgb_map, const float *classes, uint32_t
     if (const int e = cp_loss_args(ea.w.l, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
                                    grad_classes, loss_out, workspace)) return e;
     NSR_CHECK_PTR(exposure); NSR_CHECK_PTR(seg_frame); NSR_CHECK_PTR(grad_exposure);
-    const uint32_t B = cp_exp_seg_blocks(K);
+    const uint32_t B = seg_blocks(K);
     if (((uintptr_t)workspace & 7u) != 0 || F > 0x7fffffffu || (uint64_t)S * B > 0x7fffffffull) return NSR_ERR_INVALID_ARG;
     double *seg_partials = (double *)((char *)workspace + CP_EXP_WS_SEG);
     ea.w.ray_weight = ray_weight; ea.w.ray_err = ray_err;
@@ -912,7 +864,7 @@ int nsr_recon_loss_exposure(const float *rgb_map, const float *classes, uint32_t
     ea.term = (float *)((char *)workspace + cp_exp_ws_term(S, K));
     hipLaunchKernelGGL(k_recon_loss_exposure, dim3(ea.w.l.nblocks), dim3(CP_BLOCK), 0, (hipStream_t)stream, ea);
     hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, ea.w.l);
-    if (K < CP_EXP_THREAD_K)
+    if (K < SEG_THREAD_K)
         hipLaunchKernelGGL(k_exposure_seg_thread, dim3(nsr_div_up(S, CP_BLOCK)), dim3(CP_BLOCK), 0, (hipStream_t)stream,
                            (const float *)ea.term, seg_frame, F, S, K, seg_partials);
     else

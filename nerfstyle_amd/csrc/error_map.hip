@@ -8,6 +8,7 @@
 // Everything that decides a draw is integer arithmetic: sums of integers do not depend on the order the atomics arrive in, so
 // two runs, two ranks and a NumPy restatement (tests/error_map_ref.py) reach the same bits.  Floats appear in the running
 // error, its quantisation and the returned weight, each with contraction off and the operation order of include/nsr.h.
+#include "fixed_sum.h"
 #include "philox.h"
 
 #define EM_BLOCK 256
@@ -80,8 +81,7 @@ k_errmap_accumulate(EmGrid g, const int32_t *__restrict__ seg_frame, const int32
             waiting &= ~group;
             const uint32_t count = (uint32_t)__popcll(group);
             uint32_t sum = key == k ? a : 0u;
-            if (count > 1u)                                             // wave-uniform
-                for (int off = 32; off >= 1; off >>= 1) sum += (uint32_t)__shfl_xor((int)sum, off, 64);
+            if (count > 1u) sum = nsr_wave_sum(sum);                    // wave-uniform
             if (lane == first) {
                 atomicAdd(acc_sum + k, (unsigned long long)sum);
                 atomicAdd(acc_cnt + k, count);
@@ -103,10 +103,7 @@ k_errmap_accumulate(EmGrid g, const int32_t *__restrict__ seg_frame, const int32
 __device__ __forceinline__ uint64_t em_block_scan(uint64_t v, uint64_t &carry) {
     __shared__ uint64_t wave_total[EM_WAVES];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)v, off, 64);
-        if (lane >= (uint32_t)off) v += up;
-    }
+    v = nsr_wave_scan(v);
     __syncthreads();                                   // the previous chunk's totals have been read
     if (lane == 63u) wave_total[wave] = v;
     __syncthreads();

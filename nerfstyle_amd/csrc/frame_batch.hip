@@ -6,8 +6,9 @@
 //     k_frames_bwd_*                its backward: one [3,4] sum per frame, deterministic
 #include "philox.h"
 #include "ray_pose.h"
+#include "seg_sum.h"
 
-// FB_BLOCK, FB_THREAD_K, FB_MAX_SEG_BLOCKS and fb_seg_blocks, the segments-to-blocks mapping of the backward, are ray_pose.h's
+static_assert(FB_BLOCK == SEG_BLOCK, "seg_blocks counts blocks of SEG_BLOCK threads");
 
 // ---------------------------------------------------------------------------------------------
 // the draw: uniform with replacement
@@ -59,15 +60,8 @@ k_generate_rays_frames(const float *__restrict__ poses, uint32_t F, uint32_t w, 
 // ---------------------------------------------------------------------------------------------
 // backward: grad_poses[f] = sum over the rays of the segments naming f of the terms of k_generate_rays_bwd (ru_pose_term, fp64)
 // ---------------------------------------------------------------------------------------------
-// Segments to blocks.  The workspace is partials [S][B][12] f64, B = fb_seg_blocks(K) blocks per segment:
-//   K <  FB_THREAD_K   k_frames_bwd_thread: a thread per segment walks its K rays in order and writes the segment's twelve sums
-//                      (B = 1).  K = 1, per-ray frames, is S threads with one ray each.
-//   K >= FB_THREAD_K   k_frames_bwd_block: block s * B + b takes rays b * 256 + t, strided by B * 256, of segment s through the
-//                      block tree (ru_block_sum12); B = ceil(K / 256) capped at FB_MAX_SEG_BLOCKS.
-// k_frames_bwd_final, a wave per frame: the segments in ascending s, 64 at a time (a ballot of seg_frame[s] == f, then the set
-// bits from the lowest); for a segment naming the frame, lanes 0..11 add its B partials in order and then that sum to the
-// frame's.  A frame no segment names, and a segment naming no frame, meet no add: exact zeros, and nothing of such a segment is
-// read.  No atomics, no counters; every partial read was written by the launch before, in this call.
+// The three parts of seg_sum.h with twelve sums per segment: k_frames_bwd_thread, k_frames_bwd_block, and k_frames_bwd_final, a
+// wave per frame over the segments naming it.
 struct FbCam { uint32_t F, w; float fx, fy, cx, cy; int camera_flip; };
 
 __global__ void __launch_bounds__(FB_BLOCK)
@@ -94,9 +88,10 @@ k_frames_bwd_thread(const float *__restrict__ poses, FbCam c, const int32_t *__r
 __global__ void __launch_bounds__(FB_BLOCK)
 k_frames_bwd_block(const float *__restrict__ poses, FbCam c, const int32_t *__restrict__ seg_frame, const int32_t *__restrict__ pix,
                    uint32_t K, uint32_t B, const float *__restrict__ g_o, const float *__restrict__ g_d, double *__restrict__ partials) {
+    __shared__ double red[12][FB_BLOCK / 64];
     const uint32_t s = blockIdx.x / B, b = blockIdx.x - s * B;
     const uint32_t f = (uint32_t)seg_frame[s];
-    if (f >= c.F) return;                                     // the whole block: nobody waits at the tree's barrier
+    if (f >= c.F) return;                                     // the whole block: nobody waits at the block sum's barrier
     double R[3][3];
     ru_load_rotation(poses + (size_t)f * 12, R);
     const double f0 = (c.camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (c.camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (c.camera_flip >> 0) & 1 ? -1.0 : 1.0;
@@ -107,30 +102,16 @@ k_frames_bwd_block(const float *__restrict__ poses, FbCam c, const int32_t *__re
         const size_t n = (size_t)s * K + k;
         ru_pose_term(R, f0, f1, f2, (uint32_t)pix[n], c.w, c.fx, c.fy, c.cx, c.cy, g_o, g_d, n, acc);
     }
-    ru_block_sum12(acc);
-    if (threadIdx.x < 12) partials[(size_t)blockIdx.x * 12 + threadIdx.x] = acc[0];
+    nsr_block_sum_stage(acc, red);
+    if (threadIdx.x < 12) partials[(size_t)blockIdx.x * 12 + threadIdx.x] = nsr_block_sum_col<FB_BLOCK / 64>(red[threadIdx.x]);
 }
 
 __global__ void __launch_bounds__(64)
 k_frames_bwd_final(const double *__restrict__ partials, const int32_t *__restrict__ seg_frame, uint32_t S, uint32_t B,
                    float *__restrict__ grad_poses) {
     const int32_t f = (int32_t)blockIdx.x;
-    const uint32_t lane = threadIdx.x;
-    double acc = 0.0;
-    for (uint32_t base = 0; base < S; base += 64u) {
-        const uint32_t mine = base + lane;
-        uint64_t named = __ballot(mine < S && seg_frame[mine] == f);
-        while (named) {
-            const uint32_t s = base + (uint32_t)__ffsll((long long)named) - 1u;
-            named &= named - 1u;
-            if (lane < 12u) {
-                double t = 0.0;
-                for (uint32_t b = 0; b < B; b++) t += partials[((size_t)s * B + b) * 12 + lane];
-                acc += t;
-            }
-        }
-    }
-    if (lane < 12u) grad_poses[(size_t)f * 12 + lane] = (float)acc;
+    const double acc = seg_frame_sum(seg_frame, S, B, partials, 12u, 0u, 12u, [f](int32_t named) { return named == f; });
+    if (threadIdx.x < 12u) grad_poses[(size_t)f * 12 + threadIdx.x] = (float)acc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -170,7 +151,7 @@ int nsr_generate_rays_frames(const float *poses, uint32_t F, uint32_t w, uint32_
 
 uint64_t nsr_generate_rays_frames_backward_workspace_bytes(uint32_t F, uint32_t S, uint32_t K) {
     (void)F;
-    const uint64_t bytes = (uint64_t)S * fb_seg_blocks(K) * 12 * sizeof(double);
+    const uint64_t bytes = (uint64_t)S * seg_blocks(K) * 12 * sizeof(double);
     return bytes ? bytes : 12 * sizeof(double);
 }
 
@@ -181,14 +162,14 @@ int nsr_generate_rays_frames_backward(const float *poses, uint32_t F, uint32_t w
     if (F == 0) return NSR_OK;
     NSR_CHECK_PTR(grad_poses);
     uint64_t N = (uint64_t)S * K;
-    const uint32_t B = fb_seg_blocks(K);
+    const uint32_t B = seg_blocks(K);
     if (N != 0) {
         NSR_CHECK_PTR(poses); NSR_CHECK_PTR(seg_frame); NSR_CHECK_PTR(pix); NSR_CHECK_PTR(grad_rays_o); NSR_CHECK_PTR(grad_rays_d);
         NSR_CHECK_PTR(workspace);
         if (w == 0 || h == 0 || ((uintptr_t)workspace & 7u) != 0 || N > 0xffffffffull || (uint64_t)S * B > 0x7fffffffull)
             return NSR_ERR_INVALID_ARG;
         const FbCam c{F, w, fx, fy, cx, cy, camera_flip};
-        if (K < FB_THREAD_K)
+        if (K < SEG_THREAD_K)
             hipLaunchKernelGGL(k_frames_bwd_thread, dim3(nsr_div_up(S, FB_BLOCK)), dim3(FB_BLOCK), 0, (hipStream_t)stream, poses, c, seg_frame,
                                pix, S, K, grad_rays_o, grad_rays_d, (double *)workspace);
         else

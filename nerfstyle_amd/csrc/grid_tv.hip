@@ -11,7 +11,7 @@
 //
 // Rounding of one draw's add (what the tests' bound counts): the differences (one rounding each), their sum as
 // ((x- + x+) + (y- + y+)) + (z- + z+) (each difference passes through at most three adds), c * scale, and the product.
-#include "nsr_common.h"
+#include "fixed_sum.h"
 #include "philox.h"
 
 #define TV_BLOCK 256
@@ -47,33 +47,12 @@ __device__ __forceinline__ TvRow<RF> tv_load(const float *__restrict__ tab, uint
     return r;
 }
 
-// sum over the block in a fixed order: butterfly over the 64 lanes, then the waves in ascending order (thread 0 holds it)
-template <int RF>
-__device__ __forceinline__ void tv_block_sum(double (&a)[RF], double (*red)[TV_MAX_LANES]) {
-#pragma unroll
-    for (int k = 0; k < RF; k++)
-        for (int off = 32; off >= 1; off >>= 1) a[k] += __shfl_xor(a[k], off, 64);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < RF; k++) red[threadIdx.x >> 6][k] = a[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < RF; k++) {
-            double s = 0.0;
-            for (int w = 0; w < TV_WAVES; w++) s += red[w][k];
-            a[k] = s;
-        }
-    }
-}
-
 // partials: [level][blockIdx.x][RF] f64 when VALUE; grad may be NULL when VALUE (value only)
 template <int RF, bool VALUE>
 __global__ void __launch_bounds__(TV_BLOCK)
 k_grid_tv(const float *__restrict__ tables, float *__restrict__ grad, NsrLevels levels, TvArgs a,
           const uint32_t *__restrict__ sequence_dev, const float *__restrict__ scale_dev, double *__restrict__ partials) {
-    __shared__ double red[TV_WAVES][TV_MAX_LANES];
+    __shared__ double red[RF][TV_WAVES];
     const uint32_t level = blockIdx.y;
     const uint32_t n = a.n[level];
     if (n == 0u) return;                                               // the whole block: nobody waits at the barrier below
@@ -132,20 +111,20 @@ k_grid_tv(const float *__restrict__ tables, float *__restrict__ grad, NsrLevels 
         }
     }
     if (VALUE) {
-        tv_block_sum<RF>(acc, red);
+        nsr_block_sum_stage(acc, red);
         if (threadIdx.x == 0) {
             double *out = partials + ((size_t)level * gridDim.x + blockIdx.x) * RF;
 #pragma unroll
-            for (int k = 0; k < RF; k++) out[k] = acc[k];
+            for (int k = 0; k < RF; k++) out[k] = nsr_block_sum_col<TV_WAVES>(red[k]);
         }
     }
 }
 
-// one block per level: thread t adds the partials of blocks t, t + 256, ... in that order, then the block sum above
+// one block per level: thread t adds the partials of blocks t, t + 256, ... in that order, then the block sum
 template <int RF>
 __global__ void __launch_bounds__(TV_BLOCK)
 k_grid_tv_final(const double *__restrict__ partials, uint32_t nblocks, TvArgs a, double *__restrict__ value) {
-    __shared__ double red[TV_WAVES][TV_MAX_LANES];
+    __shared__ double red[RF][TV_WAVES];
     const uint32_t level = blockIdx.x;
     const uint32_t n = a.n[level];
     double acc[RF];
@@ -157,10 +136,10 @@ k_grid_tv_final(const double *__restrict__ partials, uint32_t nblocks, TvArgs a,
             for (int k = 0; k < RF; k++) acc[k] += partials[((size_t)level * nblocks + b) * RF + k];
         }
     }
-    tv_block_sum<RF>(acc, red);
+    nsr_block_sum_stage(acc, red);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int k = 0; k < RF; k++) value[(size_t)level * RF + k] = n != 0u ? acc[k] / (double)n : 0.0;
+        for (int k = 0; k < RF; k++) value[(size_t)level * RF + k] = n != 0u ? nsr_block_sum_col<TV_WAVES>(red[k]) / (double)n : 0.0;
     }
 }
 

@@ -5,6 +5,9 @@
 //     k_lens_bwd_final              a wave per frame for the pose rows, one more wave for the lens row
 // The single-pose case is F = S = 1, K = N.
 #include "ray_pose.h"
+#include "seg_sum.h"
+
+static_assert(FB_BLOCK == SEG_BLOCK, "seg_blocks counts blocks of SEG_BLOCK threads");
 
 __global__ void __launch_bounds__(FB_BLOCK)
 k_generate_rays_lens(const float *__restrict__ poses, uint32_t F, uint32_t w, const float *__restrict__ lens, int camera_flip,
@@ -27,8 +30,7 @@ k_generate_rays_lens(const float *__restrict__ poses, uint32_t F, uint32_t w, co
 }
 
 // ---------------------------------------------------------------------------------------------
-// backward: the workspace is partials [S][B][18] f64, B = fb_seg_blocks(K); segments to blocks and the order of every sum are
-// k_frames_bwd_*'s (frame_batch.hip).  A segment naming no frame writes no partial and none is read for it.
+// backward: the three parts of seg_sum.h with eighteen sums per segment, columns 0..11 the pose's and 12..17 the lens's
 // ---------------------------------------------------------------------------------------------
 struct LensCam { uint32_t F, w; int camera_flip; };
 
@@ -64,9 +66,10 @@ __global__ void __launch_bounds__(FB_BLOCK)
 k_lens_bwd_block(const float *__restrict__ poses, LensCam c, const float *__restrict__ lens, const int32_t *__restrict__ seg_frame,
                  const int32_t *__restrict__ pix, uint32_t K, uint32_t B, const float *__restrict__ g_o, const float *__restrict__ g_d,
                  double *__restrict__ partials) {
+    __shared__ double red[18][FB_BLOCK / 64];
     const uint32_t s = blockIdx.x / B, b = blockIdx.x - s * B;
     const uint32_t f = (uint32_t)seg_frame[s];
-    if (f >= c.F) return;                                     // the whole block: nobody waits at the tree's barrier
+    if (f >= c.F) return;                                     // the whole block: nobody waits at the block sum's barrier
     double R[3][3], L[6];
     ru_load_rotation(poses + (size_t)f * 12, R);
     lens_load(lens, L);
@@ -78,39 +81,22 @@ k_lens_bwd_block(const float *__restrict__ poses, LensCam c, const float *__rest
         const size_t n = (size_t)s * K + k;
         ru_lens_term(R, f0, f1, f2, (uint32_t)pix[n], c.w, L, g_o, g_d, n, acc);
     }
-    ru_block_sum<18>(acc);
-    if (threadIdx.x < 18) partials[(size_t)blockIdx.x * 18 + threadIdx.x] = acc[0];
+    nsr_block_sum_stage(acc, red);
+    if (threadIdx.x < 18) partials[(size_t)blockIdx.x * 18 + threadIdx.x] = nsr_block_sum_col<FB_BLOCK / 64>(red[threadIdx.x]);
 }
 
-// Blocks 0 .. pose_rows-1 (pose_rows = F, or 0 without grad_poses): k_frames_bwd_final on columns 0..11 of the partials.  Block
-// pose_rows: the lens row, columns 12..17 summed the same way over every segment that names a frame in [0, F), ascending s.
+// Blocks 0 .. pose_rows-1 (pose_rows = F, or 0 without grad_poses): a frame's pose row, columns 0..11 of the segments naming it.
+// Block pose_rows: the lens row, columns 12..17 of every segment that names a frame in [0, F).
 __global__ void __launch_bounds__(64)
 k_lens_bwd_final(const double *__restrict__ partials, const int32_t *__restrict__ seg_frame, uint32_t S, uint32_t B, uint32_t F,
                  uint32_t pose_rows, float *__restrict__ grad_poses, float *__restrict__ grad_lens) {
-    const bool lens_row = blockIdx.x == pose_rows;
-    const uint32_t lane = threadIdx.x, col = lens_row ? 12u : 0u, ncol = lens_row ? 6u : 12u;
-    double acc = 0.0;
-    for (uint32_t base = 0; base < S; base += 64u) {
-        const uint32_t mine = base + lane;
-        bool hit = false;
-        if (mine < S) {
-            const uint32_t f = (uint32_t)seg_frame[mine];
-            hit = lens_row ? f < F : f == blockIdx.x;
-        }
-        uint64_t named = __ballot(hit);
-        while (named) {
-            const uint32_t s = base + (uint32_t)__ffsll((long long)named) - 1u;
-            named &= named - 1u;
-            if (lane < ncol) {
-                double t = 0.0;
-                for (uint32_t b = 0; b < B; b++) t += partials[((size_t)s * B + b) * 18 + col + lane];
-                acc += t;
-            }
-        }
-    }
-    if (lane < ncol) {
-        if (lens_row) grad_lens[lane] = (float)acc;
-        else grad_poses[(size_t)blockIdx.x * 12 + lane] = (float)acc;
+    const uint32_t row = blockIdx.x, lane = threadIdx.x;
+    if (row == pose_rows) {
+        const double acc = seg_frame_sum(seg_frame, S, B, partials, 18u, 12u, 6u, [F](int32_t named) { return (uint32_t)named < F; });
+        if (lane < 6u) grad_lens[lane] = (float)acc;
+    } else {
+        const double acc = seg_frame_sum(seg_frame, S, B, partials, 18u, 0u, 12u, [row](int32_t named) { return (uint32_t)named == row; });
+        if (lane < 12u) grad_poses[(size_t)row * 12 + lane] = (float)acc;
     }
 }
 
@@ -133,7 +119,7 @@ int nsr_generate_rays_lens(const float *poses, uint32_t F, uint32_t w, uint32_t 
 
 uint64_t nsr_generate_rays_lens_backward_workspace_bytes(uint32_t F, uint32_t S, uint32_t K) {
     (void)F;
-    const uint64_t bytes = (uint64_t)S * fb_seg_blocks(K) * 18 * sizeof(double);
+    const uint64_t bytes = (uint64_t)S * seg_blocks(K) * 18 * sizeof(double);
     return bytes ? bytes : 18 * sizeof(double);
 }
 
@@ -144,14 +130,14 @@ int nsr_generate_rays_lens_backward(const float *poses, uint32_t F, uint32_t w, 
     NSR_CHECK_PTR(grad_lens);
     if (F > 0x7ffffffeu) return NSR_ERR_INVALID_ARG;
     const uint64_t N = F != 0 ? (uint64_t)S * K : 0;          // without frames no segment names one
-    const uint32_t B = fb_seg_blocks(K);
+    const uint32_t B = seg_blocks(K);
     if (N != 0) {
         NSR_CHECK_PTR(poses); NSR_CHECK_PTR(lens); NSR_CHECK_PTR(seg_frame); NSR_CHECK_PTR(pix); NSR_CHECK_PTR(grad_rays_o);
         NSR_CHECK_PTR(grad_rays_d); NSR_CHECK_PTR(workspace);
         if (w == 0 || h == 0 || ((uintptr_t)workspace & 7u) != 0 || N > 0xffffffffull || (uint64_t)S * B > 0x7fffffffull)
             return NSR_ERR_INVALID_ARG;
         const LensCam c{F, w, camera_flip};
-        if (K < FB_THREAD_K)
+        if (K < SEG_THREAD_K)
             hipLaunchKernelGGL(k_lens_bwd_thread, dim3(nsr_div_up(S, FB_BLOCK)), dim3(FB_BLOCK), 0, (hipStream_t)stream, poses, c, lens,
                                seg_frame, pix, S, K, grad_rays_o, grad_rays_d, (double *)workspace);
         else

@@ -15,7 +15,7 @@
 // in LDS; windows outside the image store zeros) and gathers them per pixel.  The value of a window is added by the one
 // tile that holds its centre; the block partials are summed in a fixed order by k_matting_final: no atomics, the result
 // is the same bit for bit from run to run.
-#include "nsr_common.h"
+#include "fixed_sum.h"
 
 #define MT_TX 32
 #define MT_TY 8
@@ -119,15 +119,8 @@ k_matting(MattingArgs a) {
         }
     }
 
-    // block partial, fixed order
-    for (int off = 32; off >= 1; off >>= 1) val += __shfl_xor(val, off, 64);
-    if ((tid & 63) == 0) s_red[tid >> 6] = val;
-    __syncthreads();                                          // also publishes s_cf
-    if (tid == 0) {
-        double s = 0.0;
-        for (int w = 0; w < MT_BLOCK / 64; w++) s += s_red[w];
-        a.partials[blockIdx.y * gridDim.x + blockIdx.x] = s;
-    }
+    nsr_block_sum_stage(val, s_red);                          // its barrier also publishes s_cf
+    if (tid == 0) a.partials[blockIdx.y * gridDim.x + blockIdx.x] = nsr_block_sum_col<MT_BLOCK / 64>(s_red);
     if (!a.grad) return;
 
     const int tx = tid % MT_TX, ty = tid / MT_TX;
@@ -164,14 +157,8 @@ k_matting_final(MattingArgs a) {
     __shared__ double red[MT_BLOCK / 64];
     double s = 0.0;
     for (uint32_t b = threadIdx.x; b < a.nblocks; b += MT_BLOCK) s += a.partials[b];
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < MT_BLOCK / 64; w++) t += red[w];
-        a.loss[0] = t;
-    }
+    nsr_block_sum_stage(s, red);
+    if (threadIdx.x == 0) a.loss[0] = nsr_block_sum_col<MT_BLOCK / 64>(red);
 }
 
 static dim3 mt_grid(uint32_t H, uint32_t W) { return dim3(nsr_div_up(W, MT_TX), nsr_div_up(H, MT_TY)); }

@@ -112,9 +112,7 @@ k_ou_mark(OuArgs a) {
             }
         }
         if (a.n_untrained) {
-            uint32_t s = __popc(clear);
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+            const uint32_t s = nsr_wave_sum((uint32_t)__popc(clear));
             if ((threadIdx.x & 63) == 0 && s) atomicAdd(&marked[cas], s);
         }
     }

@@ -166,15 +166,8 @@ k_occ_decay_max(float *__restrict__ grid, const float *__restrict__ tmp, uint32_
         }
         acc += fmaxf(g, 0.0f);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.0f;
-        for (int w = 0; w < OCC_BLOCK / 64; w++) s += wsum[w];
-        partial[blockIdx.x] = s;
-    }
+    nsr_block_sum_stage(acc, wsum);
+    if (threadIdx.x == 0) partial[blockIdx.x] = nsr_block_sum_col<OCC_BLOCK / 64>(wsum);
 }
 // one block: fixed-order tree over the per-block sums -> mean (renderer.py:186), threshold (:188), sequence++
 __global__ void __launch_bounds__(1024)

@@ -1,9 +1,8 @@
 // Per-ray arithmetic of device ray generation and of its backward towards the camera, shared by the single-pose kernels
 // (ray_util.hip), the mixed-frame ones (frame_batch.hip) and the lens ones (lens.hip): one ray from a pose and a pixel id, one
-// ray's fp64 terms of the pose gradient (and of the lens gradient), the fixed-order block tree over those sums, and the mapping
-// of a batch's segments to blocks.
+// ray's fp64 terms of the pose gradient (and of the lens gradient).  The sums over those terms are fixed_sum.h's and seg_sum.h's.
 #pragma once
-#include "nsr_common.h"
+#include "fixed_sum.h"
 
 #define RU_BLOCK 256
 
@@ -124,36 +123,5 @@ __device__ __forceinline__ void ru_lens_term(const double (&R)[3][3], double f0,
     acc[17] += m * r2 * r2;
 }
 
-// fixed-order block tree over NV values: threads 0..NV-1 leave with the block's sum k in v[0]
-template <int NV>
-__device__ __forceinline__ void ru_block_sum(double (&v)[NV]) {
-    __shared__ double red[NV][RU_BLOCK / 64];
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < NV; k++) v[k] += __shfl_xor(v[k], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; k++) red[k][threadIdx.x >> 6] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        double s = 0.0;
-        for (int w = 0; w < RU_BLOCK / 64; w++) s += red[threadIdx.x][w];
-        v[0] = s;
-    }
-}
-__device__ __forceinline__ void ru_block_sum12(double (&v)[12]) { ru_block_sum<12>(v); }
-
-// Segments of a mixed-frame batch to blocks, in every backward that sums per segment (frame_batch.hip, lens.hip): below
-// FB_THREAD_K rays a thread owns a whole segment, from it on a segment owns B = fb_seg_blocks(K) blocks of FB_BLOCK threads,
-// each striding over the segment's rays.
+// the block of the mixed-frame and lens kernels (frame_batch.hip, lens.hip)
 #define FB_BLOCK 256
-#define FB_MAX_SEG_BLOCKS 64u
-#define FB_THREAD_K 64u
-static inline uint32_t fb_seg_blocks(uint32_t K) {
-    if (K < FB_THREAD_K) return 1u;
-    const uint32_t b = nsr_div_up(K, FB_BLOCK);
-    return b < FB_MAX_SEG_BLOCKS ? b : FB_MAX_SEG_BLOCKS;
-}
-static_assert(FB_BLOCK == RU_BLOCK, "ru_block_sum is a tree over RU_BLOCK threads");

@@ -87,13 +87,14 @@ __global__ void k_generate_rays(const float *__restrict__ pose, uint32_t w, uint
 // Twelve sums over the rays: every ray's term and the sums are formed in fp64 (a few dozen operations per ray against two
 // 12-byte loads; the per-entry error is then the final rounding to fp32), block tree + a fixed-order one-block final pass over
 // the block partials, as k_recon_loss: no atomics, no counter, every partial the final pass reads was written by this call.
-// The per-ray term (ru_pose_term) and the block tree (ru_block_sum12) are ray_pose.h's.
+// The per-ray term (ru_pose_term) is ray_pose.h's, the block sum fixed_sum.h's: sum k on thread k.
 #define RU_MAX_BLOCKS 2048u
 
 __global__ void __launch_bounds__(RU_BLOCK)
 k_generate_rays_bwd(const float *__restrict__ pose, uint32_t w, float fx, float fy, float cx, float cy, int camera_flip,
                     const int32_t *__restrict__ pix, uint32_t N, const float *__restrict__ g_o, const float *__restrict__ g_d,
                     double *__restrict__ partials) {
+    __shared__ double red[12][RU_BLOCK / 64];
     double R[3][3];
     ru_load_rotation(pose, R);
     const double f0 = (camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (camera_flip >> 0) & 1 ? -1.0 : 1.0;
@@ -102,12 +103,13 @@ k_generate_rays_bwd(const float *__restrict__ pose, uint32_t w, float fx, float 
     for (int k = 0; k < 12; k++) acc[k] = 0.0;
     for (uint32_t n = blockIdx.x * RU_BLOCK + threadIdx.x; n < N; n += gridDim.x * RU_BLOCK)
         ru_pose_term(R, f0, f1, f2, pix ? (uint32_t)pix[n] : n, w, fx, fy, cx, cy, g_o, g_d, n, acc);
-    ru_block_sum12(acc);
-    if (threadIdx.x < 12) partials[(size_t)blockIdx.x * 12 + threadIdx.x] = acc[0];
+    nsr_block_sum_stage(acc, red);
+    if (threadIdx.x < 12) partials[(size_t)blockIdx.x * 12 + threadIdx.x] = nsr_block_sum_col<RU_BLOCK / 64>(red[threadIdx.x]);
 }
 
 __global__ void __launch_bounds__(RU_BLOCK)
 k_generate_rays_bwd_final(const double *__restrict__ partials, uint32_t nblocks, float *__restrict__ grad_pose) {
+    __shared__ double red[12][RU_BLOCK / 64];
     double acc[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) acc[k] = 0.0;
@@ -115,8 +117,8 @@ k_generate_rays_bwd_final(const double *__restrict__ partials, uint32_t nblocks,
 #pragma unroll
         for (int k = 0; k < 12; k++) acc[k] += partials[(size_t)b * 12 + k];
     }
-    ru_block_sum12(acc);
-    if (threadIdx.x < 12) grad_pose[threadIdx.x] = (float)acc[0];
+    nsr_block_sum_stage(acc, red);
+    if (threadIdx.x < 12) grad_pose[threadIdx.x] = (float)nsr_block_sum_col<RU_BLOCK / 64>(red[threadIdx.x]);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -51,9 +51,7 @@ __device__ __forceinline__ bool rm_wave_ray_begin(uint32_t n, uint32_t lane, uin
     const uint32_t blk0 = (n / RM_BLOCK) * RM_BLOCK;
     uint32_t part = 0;
     for (uint32_t i = blk0 + lane; i < n; i += 64) part += counts[i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
-    point_index = block_bases[n / RM_BLOCK] + part;
+    point_index = block_bases[n / RM_BLOCK] + nsr_wave_sum(part);
     num_steps = counts[n];
     if (lane == 0) {
         rays[n * 3 + 0] = (int32_t)n;

@@ -1,7 +1,7 @@
 // Morton code and block-scan helpers shared by the ray-march (rm_probe.h, raymarch.hip, raymarch_infer.hip, ray_util.hip)
 // and occupancy-update (occupancy.hip) kernels.
 #pragma once
-#include "nsr_common.h"
+#include "fixed_sum.h"
 
 // raymarching.cu:56-81
 __device__ __forceinline__ uint32_t rm_expand_bits(uint32_t v) {
@@ -31,16 +31,11 @@ __device__ __forceinline__ uint32_t rm_morton3d_invert(uint32_t x) {
 // power of two (at H = 24, morton(23, 23, 23) = 29183 >= 13824: a read past the bitfield).
 static inline bool rm_grid_size_ok(uint32_t H) { return H >= 8 && H <= 512 && (H & (H - 1u)) == 0u; }
 
-// wave64 inclusive scan by shuffles, then a block scan over the (<= 16) wave totals in LDS.
+// wave64 inclusive scan (fixed_sum.h), then a block scan over the (<= 16) wave totals in LDS.
 // Returns the exclusive prefix of v inside the block and the block total in `total`.
 __device__ __forceinline__ uint32_t rm_block_exclusive_scan(uint32_t v, uint32_t *lds_wave_sums, uint32_t &total) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += up;
-    }
+    const uint32_t incl = nsr_wave_scan(v);
     if (lane == 63) lds_wave_sums[wave] = incl;
     __syncthreads();
     const uint32_t nw = blockDim.x >> 6;

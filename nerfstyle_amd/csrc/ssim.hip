@@ -21,7 +21,7 @@
 // (+ 4 B map); backward 12 + 8 B read, 4 B written.
 #include <math.h>
 
-#include "nsr_common.h"
+#include "fixed_sum.h"
 
 #define SS_T 32                          // tile edge (nerfstyle_amd/ssim.py: TILE)
 #define SS_R 5                           // window radius
@@ -172,15 +172,8 @@ k_ssim_fwd(SsimArgs a) {
         }
         if (a.ssim_map) a.ssim_map[pix * 3 + c] = m;
     }
-    // block partial, fixed order
-    for (int off = 32; off >= 1; off >>= 1) val += __shfl_xor(val, off, 64);
-    if ((tid & 63) == 0) s_red[tid >> 6] = val;
-    __syncthreads();
-    if (tid == 0) {
-        double s = 0.0;
-        for (int w = 0; w < SS_BLOCK / 64; w++) s += s_red[w];
-        a.partials[(size_t)c * a.nblocks + blockIdx.y * gridDim.x + blockIdx.x] = s;
-    }
+    nsr_block_sum_stage(val, s_red);
+    if (tid == 0) a.partials[(size_t)c * a.nblocks + blockIdx.y * gridDim.x + blockIdx.x] = nsr_block_sum_col<SS_BLOCK / 64>(s_red);
 }
 
 __global__ void __launch_bounds__(SS_BLOCK)
@@ -232,24 +225,18 @@ k_ssim_bwd(SsimArgs a) {
     }
 }
 
-// one block: thread t adds partial[c][t], partial[c][t + 256], ... in that order; butterfly over the 64 lanes; the four
-// waves in ascending order; out = {(s0 + s1 + s2) / 3, s0, s1, s2} / counted pixels
+// one block: thread t adds partial[c][t], partial[c][t + 256], ... in that order, then the block sum;
+// out = {(s0 + s1 + s2) / 3, s0, s1, s2} / counted pixels
 __global__ void __launch_bounds__(SS_BLOCK)
 k_ssim_final(SsimArgs a) {
     __shared__ double red[3][SS_BLOCK / 64];
-    for (int c = 0; c < 3; c++) {
-        double s = 0.0;
-        for (uint32_t b = threadIdx.x; b < a.nblocks; b += SS_BLOCK) s += a.partials[(size_t)c * a.nblocks + b];
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-        if ((threadIdx.x & 63) == 0) red[c][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int c = 0; c < 3; c++)
+        for (uint32_t b = threadIdx.x; b < a.nblocks; b += SS_BLOCK) s[c] += a.partials[(size_t)c * a.nblocks + b];
+    nsr_block_sum_stage(s, red);
     if (threadIdx.x == 0) {
         double t[3];
-        for (int c = 0; c < 3; c++) {
-            t[c] = 0.0;
-            for (int w = 0; w < SS_BLOCK / 64; w++) t[c] += red[c][w];
-        }
+        for (int c = 0; c < 3; c++) t[c] = nsr_block_sum_col<SS_BLOCK / 64>(red[c]);
         a.out[0] = ((t[0] + t[1]) + t[2]) * a.inv_plane / 3.0;
         for (int c = 0; c < 3; c++) a.out[1 + c] = t[c] * a.inv_plane;
     }
