@@ -19,6 +19,7 @@
 //
 // The loss kernel is one thread per ray (value + gradient in one pass, targets gathered through the pixel indices), a
 // block sum for the value and a second one-block kernel that adds the block partials in a fixed order (fixed_sum.h in both).
+#include <type_traits>
 #include "seg_sum.h"
 
 #define CP_MAXC 16
@@ -453,6 +454,16 @@ struct LossArgs {
     float *out;                           // [3]: scaled total, mse, ce (both unscaled)
     uint32_t nblocks;
 };
+struct WLossArgs : LossArgs {             // ... with a weight per ray (importance sampling: error_map.hip)
+    const float *ray_weight;              // [N] or NULL: 1
+    float *ray_err;                       // [N] or NULL
+};
+struct ELossArgs : WLossArgs {            // ... and a gain per frame and colour channel (per-frame exposure and white balance)
+    const float *exposure;                // [F,3] log2 gains
+    const int32_t *seg_frame;             // [N / K]
+    uint32_t F, K;
+    float *term;                          // [N,3]
+};
 
 // the block's (mse, ce) to partials[blockIdx.x]; every thread of the block calls it
 __device__ __forceinline__ void cp_loss_partials(const LossArgs &a, float mse, float ce, float (&red)[2][CP_BLOCK / 64]) {
@@ -464,20 +475,53 @@ __device__ __forceinline__ void cp_loss_partials(const LossArgs &a, float mse, f
     }
 }
 
+// The per-ray pass of the three losses, one body; Args says which one.
+//   LossArgs    the plain loss.
+//   WLossArgs   every per-ray term of value and gradient times ray_weight[n], the means still over N; ray_err (optional) gets
+//               the ray's unweighted sum of squared colour differences, the fp32 differences' squares summed exactly in fp64
+//               and rounded once.
+//   ELossArgs   ray n of segment n / K, frame f = seg_frame[n / K], is modelled to have been observed as p = rgb_map *
+//               exp2(exposure[f]) (a frame outside [0, F) reads no exposure row: gain 1); the difference, the value and the
+//               per-ray error are those of p, the gradient towards rgb_map is the gradient towards p times the gain, and term =
+//               (d loss / d p) * p, staged per ray and channel, is what the exposure segment sums below add up per frame (d p /
+//               d exposure = ln2 * p).  p is a product rounded on its own (__fmul_rn: a contraction into the difference would
+//               leave term without its operand).
+// The operand-shape rule: a factor that a loss does not have is the constant 1 in the one expression all three share, so a weight
+// of exactly 1 and an exposure of 0 (gain exactly 1) give every operation the operands it has in the loss without them -- (1 *
+// df) * df + mse contracts like df * df + mse, 1 * (lse - logit) + ce like (lse - logit) + ce -- and the compiler folds the
+// constant away: the plain kernel has no weight multiply, no fp64 error and no ray_err store, the weighted one no gain and no
+// term store.  All three write partials for the same final pass.
+template <typename Args>
 __global__ void __launch_bounds__(CP_BLOCK)
-k_recon_loss(LossArgs a) {
+k_recon_loss(Args a) {
+    constexpr bool WEIGHTED = std::is_base_of_v<WLossArgs, Args>, EXPOSURE = std::is_base_of_v<ELossArgs, Args>;
     __shared__ float red[2][CP_BLOCK / 64];
     const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
     const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
     float mse = 0.0f, ce = 0.0f;
     for (uint32_t n = blockIdx.x * CP_BLOCK + threadIdx.x; n < a.N; n += gridDim.x * CP_BLOCK) {
         const size_t row = a.pix ? (size_t)a.pix[n] : (size_t)n;
+        const float w = [&] { if constexpr (WEIGHTED) return a.ray_weight ? a.ray_weight[n] : 1.0f; else return 1.0f; }();
+        uint32_t f = 0u;
+        bool named = false;
+        if constexpr (EXPOSURE) { f = (uint32_t)a.seg_frame[n / a.K]; named = f < a.F; }
+        double e = 0.0;
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const float df = a.rgb_map[(size_t)n * 3 + k] - a.target_rgb[row * 3 + k];
-            mse += df * df;
-            a.g_rgb[(size_t)n * 3 + k] = 2.0f * df * inv3n * s;
+            float gain = 1.0f, p = a.rgb_map[(size_t)n * 3 + k];
+            if constexpr (EXPOSURE) {
+                gain = named ? exp2f(a.exposure[(size_t)f * 3 + k]) : 1.0f;
+                p = __fmul_rn(p, gain);
+            }
+            const float df = p - a.target_rgb[row * 3 + k];
+            const float wdf = w * df;
+            mse += wdf * df;
+            if constexpr (WEIGHTED) e += (double)df * (double)df;
+            const float gp = 2.0f * df * inv3n * s * w;
+            a.g_rgb[(size_t)n * 3 + k] = gp * gain;
+            if constexpr (EXPOSURE) a.term[(size_t)n * 3 + k] = gp * p;
         }
+        if constexpr (WEIGHTED) { if (a.ray_err) a.ray_err[n] = (float)e; }
         if (a.classes && a.nc) {
             // nn.CrossEntropyLoss (trainers/base.py:281): logsumexp(logits) - logits[label], mean over the rays
             const float *lg = a.classes + (size_t)n * a.nc;
@@ -487,8 +531,8 @@ k_recon_loss(LossArgs a) {
             float se = 0.0f;
             for (uint32_t k = 0; k < a.nc; k++) se += expf(lg[k] - mx);
             const float lse = mx + logf(se);
-            ce += lse - lg[min(label, a.nc - 1u)];
-            const float gk = a.ce_lambda * invn * s;
+            ce += w * (lse - lg[min(label, a.nc - 1u)]);
+            const float gk = a.ce_lambda * invn * s * w;
             for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
         }
     }
@@ -511,140 +555,41 @@ k_recon_loss_final(LossArgs a) {
     }
 }
 
-// k_recon_loss with a weight per ray (importance sampling: error_map.hip): every per-ray term of value and gradient times
-// ray_weight[n], the means still over N; ray_err (optional) gets the ray's unweighted sum of squared colour differences.  Written
-// so that a weight of exactly 1 leaves every operation of k_recon_loss with the same operands -- (1 * df) * df + mse contracts
-// like df * df + mse, 1 * (lse - logit) + ce like (lse - logit) + ce -- and the partials go through the same final pass.
-struct WLossArgs {
-    LossArgs l;
-    const float *ray_weight;              // [N] or NULL: 1
-    float *ray_err;                       // [N] or NULL
-};
-
-__global__ void __launch_bounds__(CP_BLOCK)
-k_recon_loss_weighted(WLossArgs wa) {
-    __shared__ float red[2][CP_BLOCK / 64];
-    const LossArgs &a = wa.l;
-    const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
-    const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
-    float mse = 0.0f, ce = 0.0f;
-    for (uint32_t n = blockIdx.x * CP_BLOCK + threadIdx.x; n < a.N; n += gridDim.x * CP_BLOCK) {
-        const size_t row = a.pix ? (size_t)a.pix[n] : (size_t)n;
-        const float w = wa.ray_weight ? wa.ray_weight[n] : 1.0f;
-        double e = 0.0;                     // the fp32 differences' squares summed exactly, rounded once
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float df = a.rgb_map[(size_t)n * 3 + k] - a.target_rgb[row * 3 + k];
-            const float wdf = w * df;
-            mse += wdf * df;
-            e += (double)df * (double)df;
-            a.g_rgb[(size_t)n * 3 + k] = 2.0f * df * inv3n * s * w;
-        }
-        if (wa.ray_err) wa.ray_err[n] = (float)e;
-        if (a.classes && a.nc) {
-            const float *lg = a.classes + (size_t)n * a.nc;
-            const uint32_t label = (uint32_t)a.target_cls[row];
-            float mx = lg[0];
-            for (uint32_t k = 1; k < a.nc; k++) mx = fmaxf(mx, lg[k]);
-            float se = 0.0f;
-            for (uint32_t k = 0; k < a.nc; k++) se += expf(lg[k] - mx);
-            const float lse = mx + logf(se);
-            ce += w * (lse - lg[min(label, a.nc - 1u)]);
-            const float gk = a.ce_lambda * invn * s * w;
-            for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
-        }
-    }
-    cp_loss_partials(a, mse, ce, red);
-}
-
-// k_recon_loss_weighted with a gain per frame and colour channel (per-frame exposure and white balance): ray n of segment n / K,
-// frame f = seg_frame[n / K], is modelled to have been observed as p = rgb_map * exp2(exposure[f]); the difference, the value and
-// the per-ray error are those of p, the gradient towards rgb_map is the gradient towards p times the gain, and term = (d loss /
-// d p) * p, staged per ray and channel, is what the kernels below add up per frame (d p / d exposure = ln2 * p).  p is a product
-// rounded on its own (__fmul_rn: a contraction into the difference would leave term without its operand); every other
-// expression has the shape it has in k_recon_loss_weighted, so that exposure 0 (gain exactly 1) leaves that kernel's operands.
-struct ELossArgs {
-    WLossArgs w;
-    const float *exposure;                // [F,3] log2 gains
-    const int32_t *seg_frame;             // [N / K]
-    uint32_t F, K;
-    float *term;                          // [N,3]
-};
-
-__global__ void __launch_bounds__(CP_BLOCK)
-k_recon_loss_exposure(ELossArgs ea) {
-    __shared__ float red[2][CP_BLOCK / 64];
-    const LossArgs &a = ea.w.l;
-    const float s = (a.scale ? a.scale[0] : 1.0f) * a.factor;
-    const float inv3n = 1.0f / (3.0f * (float)a.N), invn = 1.0f / (float)a.N;
-    float mse = 0.0f, ce = 0.0f;
-    for (uint32_t n = blockIdx.x * CP_BLOCK + threadIdx.x; n < a.N; n += gridDim.x * CP_BLOCK) {
-        const size_t row = a.pix ? (size_t)a.pix[n] : (size_t)n;
-        const float w = ea.w.ray_weight ? ea.w.ray_weight[n] : 1.0f;
-        const uint32_t f = (uint32_t)ea.seg_frame[n / ea.K];
-        const bool named = f < ea.F;       // a frame outside [0, F) reads no exposure row: gain 1
-        double e = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float gain = named ? exp2f(ea.exposure[(size_t)f * 3 + k]) : 1.0f;
-            const float p = __fmul_rn(a.rgb_map[(size_t)n * 3 + k], gain);
-            const float df = p - a.target_rgb[row * 3 + k];
-            const float wdf = w * df;
-            mse += wdf * df;
-            e += (double)df * (double)df;
-            const float gp = 2.0f * df * inv3n * s * w;
-            a.g_rgb[(size_t)n * 3 + k] = gp * gain;
-            ea.term[(size_t)n * 3 + k] = gp * p;
-        }
-        if (ea.w.ray_err) ea.w.ray_err[n] = (float)e;
-        if (a.classes && a.nc) {
-            const float *lg = a.classes + (size_t)n * a.nc;
-            const uint32_t label = (uint32_t)a.target_cls[row];
-            float mx = lg[0];
-            for (uint32_t k = 1; k < a.nc; k++) mx = fmaxf(mx, lg[k]);
-            float se = 0.0f;
-            for (uint32_t k = 0; k < a.nc; k++) se += expf(lg[k] - mx);
-            const float lse = mx + logf(se);
-            ce += w * (lse - lg[min(label, a.nc - 1u)]);
-            const float gk = a.ce_lambda * invn * s * w;
-            for (uint32_t k = 0; k < a.nc; k++) a.g_classes[(size_t)n * a.nc + k] = (expf(lg[k] - lse) - (k == label ? 1.0f : 0.0f)) * gk;
-        }
-    }
-    cp_loss_partials(a, mse, ce, red);
+// the per-ray pass of the loss that Args names, then the final pass they share
+template <typename Args>
+static void cp_loss_launch(const Args &a, hipStream_t s) {
+    hipLaunchKernelGGL(k_recon_loss<Args>, dim3(a.nblocks), dim3(CP_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, s, static_cast<const LossArgs &>(a));
 }
 
 // grad_exposure[f] = ln2 * sum of term over the rays of the segments naming f, in fp64: the three parts of seg_sum.h with three
 // sums per segment, seg_partials [S][B][3]; the frame's sum times ln2 is rounded to fp32 once.
-__global__ void __launch_bounds__(CP_BLOCK)
-k_exposure_seg_thread(const float *__restrict__ term, const int32_t *__restrict__ seg_frame, uint32_t F, uint32_t S, uint32_t K,
-                      double *__restrict__ seg_partials) {
-    const uint32_t s = blockIdx.x * CP_BLOCK + threadIdx.x;
-    if (s >= S) return;
-    if ((uint32_t)seg_frame[s] >= F) return;
-    double acc[3] = {0.0, 0.0, 0.0};
-    const float *t = term + (size_t)s * K * 3;
-    for (uint32_t k = 0; k < K; k++) {
+struct ExpSegArgs {
+    const float *term;                    // [S * K, 3]
+    const int32_t *seg_frame;
+    uint32_t F, S, K, B;
+    double *seg_partials;
+};
+
+__device__ __forceinline__ auto cp_exposure_terms(const float *__restrict__ term) {
+    return [=](uint32_t, size_t n0) {
+        const float *t = term + n0 * 3;
+        return [=](uint32_t k, double (&acc)[3]) {
 #pragma unroll
-        for (int c = 0; c < 3; c++) acc[c] += (double)t[(size_t)k * 3 + c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) seg_partials[(size_t)s * 3 + c] = acc[c];
+            for (int c = 0; c < 3; c++) acc[c] += (double)t[(size_t)k * 3 + c];
+        };
+    };
 }
 
-__global__ void __launch_bounds__(CP_BLOCK)
-k_exposure_seg_block(const float *__restrict__ term, const int32_t *__restrict__ seg_frame, uint32_t F, uint32_t K, uint32_t B,
-                     double *__restrict__ seg_partials) {
-    __shared__ double red[3][CP_BLOCK / 64];
-    const uint32_t s = blockIdx.x / B, b = blockIdx.x - s * B;
-    if ((uint32_t)seg_frame[s] >= F) return;                   // the whole block: nobody waits at the block sum's barrier
-    double acc[3] = {0.0, 0.0, 0.0};
-    const float *t = term + (size_t)s * K * 3;
-    for (uint32_t k = b * CP_BLOCK + threadIdx.x; k < K; k += B * CP_BLOCK) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) acc[c] += (double)t[(size_t)k * 3 + c];
-    }
-    nsr_block_sum_stage(acc, red);
-    if (threadIdx.x < 3) seg_partials[(size_t)blockIdx.x * 3 + threadIdx.x] = nsr_block_sum_col<CP_BLOCK / 64>(red[threadIdx.x]);
+__global__ void __launch_bounds__(SEG_BLOCK)
+k_exposure_seg_thread(ExpSegArgs a) {
+    seg_sum_thread<3>(a.seg_frame, a.F, a.S, a.K, a.seg_partials, cp_exposure_terms(a.term));
+}
+
+__global__ void __launch_bounds__(SEG_BLOCK)
+k_exposure_seg_block(ExpSegArgs a) {
+    __shared__ double red[3][SEG_BLOCK / 64];
+    seg_sum_block<3>(a.seg_frame, a.F, a.K, a.B, a.seg_partials, red, cp_exposure_terms(a.term));
 }
 
 __global__ void __launch_bounds__(64)
@@ -816,8 +761,7 @@ int nsr_recon_loss(const float *rgb_map, const float *classes, uint32_t N, uint3
     LossArgs a;
     if (const int e = cp_loss_args(a, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
                                    grad_classes, loss_out, workspace)) return e;
-    hipLaunchKernelGGL(k_recon_loss, dim3(a.nblocks), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, a);
+    cp_loss_launch(a, (hipStream_t)stream);
     return nsr_launch_status();
 }
 
@@ -825,12 +769,11 @@ int nsr_recon_loss_weighted(const float *rgb_map, const float *classes, uint32_t
                             const int64_t *target_cls, const int64_t *pix, const float *ray_weight, float ce_lambda, float factor,
                             const float *scale, float *grad_rgb_map, float *grad_classes, float *ray_err, float *loss_out,
                             void *workspace, nsr_stream_t stream) {
-    WLossArgs wa;
-    if (const int e = cp_loss_args(wa.l, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
+    WLossArgs a;
+    if (const int e = cp_loss_args(a, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
                                    grad_classes, loss_out, workspace)) return e;
-    wa.ray_weight = ray_weight; wa.ray_err = ray_err;
-    hipLaunchKernelGGL(k_recon_loss_weighted, dim3(wa.l.nblocks), dim3(CP_BLOCK), 0, (hipStream_t)stream, wa);
-    hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, wa.l);
+    a.ray_weight = ray_weight; a.ray_err = ray_err;
+    cp_loss_launch(a, (hipStream_t)stream);
     return nsr_launch_status();
 }
 
@@ -852,24 +795,19 @@ int nsr_recon_loss_exposure(const float *rgb_map, const float *classes, uint32_t
                             float *grad_rgb_map, float *grad_classes, float *grad_exposure, float *ray_err, float *loss_out,
                             void *workspace, nsr_stream_t stream) {
     if (N == 0 || F == 0 || S == 0 || K == 0 || (uint64_t)S * K != (uint64_t)N) return NSR_ERR_INVALID_ARG;
-    ELossArgs ea;
-    if (const int e = cp_loss_args(ea.w.l, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
+    ELossArgs a;
+    if (const int e = cp_loss_args(a, rgb_map, classes, N, nc, target_rgb, target_cls, pix, ce_lambda, factor, scale, grad_rgb_map,
                                    grad_classes, loss_out, workspace)) return e;
     NSR_CHECK_PTR(exposure); NSR_CHECK_PTR(seg_frame); NSR_CHECK_PTR(grad_exposure);
+    if (F > 0x7fffffffu || !seg_sum_ok(N, S, K, workspace)) return NSR_ERR_INVALID_ARG;
     const uint32_t B = seg_blocks(K);
-    if (((uintptr_t)workspace & 7u) != 0 || F > 0x7fffffffu || (uint64_t)S * B > 0x7fffffffull) return NSR_ERR_INVALID_ARG;
     double *seg_partials = (double *)((char *)workspace + CP_EXP_WS_SEG);
-    ea.w.ray_weight = ray_weight; ea.w.ray_err = ray_err;
-    ea.exposure = exposure; ea.seg_frame = seg_frame; ea.F = F; ea.K = K;
-    ea.term = (float *)((char *)workspace + cp_exp_ws_term(S, K));
-    hipLaunchKernelGGL(k_recon_loss_exposure, dim3(ea.w.l.nblocks), dim3(CP_BLOCK), 0, (hipStream_t)stream, ea);
-    hipLaunchKernelGGL(k_recon_loss_final, dim3(1), dim3(CP_BLOCK), 0, (hipStream_t)stream, ea.w.l);
-    if (K < SEG_THREAD_K)
-        hipLaunchKernelGGL(k_exposure_seg_thread, dim3(nsr_div_up(S, CP_BLOCK)), dim3(CP_BLOCK), 0, (hipStream_t)stream,
-                           (const float *)ea.term, seg_frame, F, S, K, seg_partials);
-    else
-        hipLaunchKernelGGL(k_exposure_seg_block, dim3(S * B), dim3(CP_BLOCK), 0, (hipStream_t)stream, (const float *)ea.term, seg_frame, F,
-                           K, B, seg_partials);
+    a.ray_weight = ray_weight; a.ray_err = ray_err;
+    a.exposure = exposure; a.seg_frame = seg_frame; a.F = F; a.K = K;
+    a.term = (float *)((char *)workspace + cp_exp_ws_term(S, K));
+    cp_loss_launch(a, (hipStream_t)stream);
+    seg_sum_launch(k_exposure_seg_thread, k_exposure_seg_block, S, K, (hipStream_t)stream,
+                   ExpSegArgs{a.term, seg_frame, F, S, K, B, seg_partials});
     hipLaunchKernelGGL(k_exposure_final, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double *)seg_partials, seg_frame, S, B,
                        grad_exposure);
     return nsr_launch_status();

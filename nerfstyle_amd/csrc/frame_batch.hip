@@ -36,74 +36,54 @@ k_draw_frame_batch(uint32_t F, uint32_t P, uint32_t K, uint32_t N, uint32_t seed
 __global__ void k_advance_sequence(uint32_t *__restrict__ sequence_dev) { sequence_dev[0] += 1u; }
 
 // ---------------------------------------------------------------------------------------------
-// forward: ru_write_ray (the arithmetic of k_generate_rays, contraction off) with the pose of the ray's segment
+// forward: the body of k_generate_rays (ru_generate_rays, ray_pose.h) with the pose of the ray's segment
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(FB_BLOCK)
 k_generate_rays_frames(const float *__restrict__ poses, uint32_t F, uint32_t w, float fx, float fy, float cx, float cy, int camera_flip,
                        const int32_t *__restrict__ seg_frame, const int32_t *__restrict__ pix, uint32_t K, uint32_t N,
                        float *__restrict__ rays_o, float *__restrict__ rays_d) {
-    const float f0 = (camera_flip >> 2) & 1 ? -1.0f : 1.0f;   // nerf_lib.py:121, bit order [2,1,0]
-    const float f1 = (camera_flip >> 1) & 1 ? -1.0f : 1.0f;
-    const float f2 = (camera_flip >> 0) & 1 ? -1.0f : 1.0f;
-    for (uint32_t n = blockIdx.x * FB_BLOCK + threadIdx.x; n < N; n += gridDim.x * FB_BLOCK) {
-        const uint32_t f = (uint32_t)seg_frame[n / K];
-        if (f >= F) {      // no such frame: rays the march treats as out of range
-            const float nan = __int_as_float(0x7fc00000);
-#pragma unroll
-            for (int k = 0; k < 3; k++) { rays_o[(size_t)n * 3 + k] = nan; rays_d[(size_t)n * 3 + k] = nan; }
-            continue;
-        }
-        ru_write_ray(ru_load_pose(poses + (size_t)f * 12), f0, f1, f2, (uint32_t)pix[n], w, fx, fy, cx, cy, (size_t)n, rays_o, rays_d);
-    }
+    ru_generate_rays<size_t>(RuSegPoses{poses, seg_frame, pix, F, K}, RuPinhole{fx, fy, cx, cy}, camera_flip, w, FB_BLOCK, N, rays_o,
+                             rays_d);
 }
 
 // ---------------------------------------------------------------------------------------------
 // backward: grad_poses[f] = sum over the rays of the segments naming f of the terms of k_generate_rays_bwd (ru_pose_term, fp64)
 // ---------------------------------------------------------------------------------------------
-// The three parts of seg_sum.h with twelve sums per segment: k_frames_bwd_thread, k_frames_bwd_block, and k_frames_bwd_final, a
-// wave per frame over the segments naming it.
-struct FbCam { uint32_t F, w; float fx, fy, cx, cy; int camera_flip; };
+// The three parts of seg_sum.h with twelve sums per segment: k_frames_bwd_thread and k_frames_bwd_block are seg_sum_thread and
+// seg_sum_block over ru_pose_term, k_frames_bwd_final is a wave per frame over the segments naming it.
+struct FbBwdArgs {
+    const float *poses;
+    uint32_t F, w;
+    RuPinhole cam;
+    int camera_flip;
+    const int32_t *seg_frame, *pix;
+    uint32_t S, K, B;
+    const float *g_o, *g_d;
+    double *partials;                     // [S][B][12]
+};
 
-__global__ void __launch_bounds__(FB_BLOCK)
-k_frames_bwd_thread(const float *__restrict__ poses, FbCam c, const int32_t *__restrict__ seg_frame, const int32_t *__restrict__ pix,
-                    uint32_t S, uint32_t K, const float *__restrict__ g_o, const float *__restrict__ g_d, double *__restrict__ partials) {
-    const uint32_t s = blockIdx.x * FB_BLOCK + threadIdx.x;
-    if (s >= S) return;
-    const uint32_t f = (uint32_t)seg_frame[s];
-    if (f >= c.F) return;
-    double R[3][3];
-    ru_load_rotation(poses + (size_t)f * 12, R);
-    const double f0 = (c.camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (c.camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (c.camera_flip >> 0) & 1 ? -1.0 : 1.0;
-    double acc[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) acc[k] = 0.0;
-    for (uint32_t k = 0; k < K; k++) {
-        const size_t n = (size_t)s * K + k;
-        ru_pose_term(R, f0, f1, f2, (uint32_t)pix[n], c.w, c.fx, c.fy, c.cx, c.cy, g_o, g_d, n, acc);
-    }
-#pragma unroll
-    for (int k = 0; k < 12; k++) partials[(size_t)s * 12 + k] = acc[k];
+// make_term of seg_sum.h: ru_pose_term with the rotation of the segment's frame
+__device__ __forceinline__ auto fb_pose_terms(const FbBwdArgs &a) {
+    return [=](uint32_t f, size_t n0) {
+        double R[3][3];
+        ru_load_rotation(a.poses + (size_t)f * 12, R);
+        const RuFlip<double> flip = ru_flip<double>(a.camera_flip);
+        return [=](uint32_t k, double (&acc)[12]) {
+            const size_t n = n0 + k;
+            ru_pose_term(R, flip, (uint32_t)a.pix[n], a.w, a.cam, a.g_o, a.g_d, n, acc);
+        };
+    };
 }
 
-__global__ void __launch_bounds__(FB_BLOCK)
-k_frames_bwd_block(const float *__restrict__ poses, FbCam c, const int32_t *__restrict__ seg_frame, const int32_t *__restrict__ pix,
-                   uint32_t K, uint32_t B, const float *__restrict__ g_o, const float *__restrict__ g_d, double *__restrict__ partials) {
-    __shared__ double red[12][FB_BLOCK / 64];
-    const uint32_t s = blockIdx.x / B, b = blockIdx.x - s * B;
-    const uint32_t f = (uint32_t)seg_frame[s];
-    if (f >= c.F) return;                                     // the whole block: nobody waits at the block sum's barrier
-    double R[3][3];
-    ru_load_rotation(poses + (size_t)f * 12, R);
-    const double f0 = (c.camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (c.camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (c.camera_flip >> 0) & 1 ? -1.0 : 1.0;
-    double acc[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) acc[k] = 0.0;
-    for (uint32_t k = b * FB_BLOCK + threadIdx.x; k < K; k += B * FB_BLOCK) {
-        const size_t n = (size_t)s * K + k;
-        ru_pose_term(R, f0, f1, f2, (uint32_t)pix[n], c.w, c.fx, c.fy, c.cx, c.cy, g_o, g_d, n, acc);
-    }
-    nsr_block_sum_stage(acc, red);
-    if (threadIdx.x < 12) partials[(size_t)blockIdx.x * 12 + threadIdx.x] = nsr_block_sum_col<FB_BLOCK / 64>(red[threadIdx.x]);
+__global__ void __launch_bounds__(SEG_BLOCK)
+k_frames_bwd_thread(FbBwdArgs a) {
+    seg_sum_thread<12>(a.seg_frame, a.F, a.S, a.K, a.partials, fb_pose_terms(a));
+}
+
+__global__ void __launch_bounds__(SEG_BLOCK)
+k_frames_bwd_block(FbBwdArgs a) {
+    __shared__ double red[12][SEG_BLOCK / 64];
+    seg_sum_block<12>(a.seg_frame, a.F, a.K, a.B, a.partials, red, fb_pose_terms(a));
 }
 
 __global__ void __launch_bounds__(64)
@@ -166,15 +146,10 @@ int nsr_generate_rays_frames_backward(const float *poses, uint32_t F, uint32_t w
     if (N != 0) {
         NSR_CHECK_PTR(poses); NSR_CHECK_PTR(seg_frame); NSR_CHECK_PTR(pix); NSR_CHECK_PTR(grad_rays_o); NSR_CHECK_PTR(grad_rays_d);
         NSR_CHECK_PTR(workspace);
-        if (w == 0 || h == 0 || ((uintptr_t)workspace & 7u) != 0 || N > 0xffffffffull || (uint64_t)S * B > 0x7fffffffull)
-            return NSR_ERR_INVALID_ARG;
-        const FbCam c{F, w, fx, fy, cx, cy, camera_flip};
-        if (K < SEG_THREAD_K)
-            hipLaunchKernelGGL(k_frames_bwd_thread, dim3(nsr_div_up(S, FB_BLOCK)), dim3(FB_BLOCK), 0, (hipStream_t)stream, poses, c, seg_frame,
-                               pix, S, K, grad_rays_o, grad_rays_d, (double *)workspace);
-        else
-            hipLaunchKernelGGL(k_frames_bwd_block, dim3(S * B), dim3(FB_BLOCK), 0, (hipStream_t)stream, poses, c, seg_frame, pix, K, B,
-                               grad_rays_o, grad_rays_d, (double *)workspace);
+        if (w == 0 || h == 0 || !seg_sum_ok(N, S, K, workspace)) return NSR_ERR_INVALID_ARG;
+        const FbBwdArgs a{poses, F, w, RuPinhole{fx, fy, cx, cy}, camera_flip, seg_frame, pix, S, K, B, grad_rays_o, grad_rays_d,
+                          (double *)workspace};
+        seg_sum_launch(k_frames_bwd_thread, k_frames_bwd_block, S, K, (hipStream_t)stream, a);
     }
     // no rays: every frame's gradient is still written (zeros)
     hipLaunchKernelGGL(k_frames_bwd_final, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double *)workspace, seg_frame,

@@ -13,76 +13,47 @@ __global__ void __launch_bounds__(FB_BLOCK)
 k_generate_rays_lens(const float *__restrict__ poses, uint32_t F, uint32_t w, const float *__restrict__ lens, int camera_flip,
                      const int32_t *__restrict__ seg_frame, const int32_t *__restrict__ pix, uint32_t K, uint32_t N,
                      float *__restrict__ rays_o, float *__restrict__ rays_d) {
-    const float f0 = (camera_flip >> 2) & 1 ? -1.0f : 1.0f;   // nerf_lib.py:121, bit order [2,1,0]
-    const float f1 = (camera_flip >> 1) & 1 ? -1.0f : 1.0f;
-    const float f2 = (camera_flip >> 0) & 1 ? -1.0f : 1.0f;
-    const RuLens Ln = ru_load_lens(lens);
-    for (uint32_t n = blockIdx.x * FB_BLOCK + threadIdx.x; n < N; n += gridDim.x * FB_BLOCK) {
-        const uint32_t f = (uint32_t)seg_frame[n / K];
-        if (f >= F) {      // no such frame: rays the march treats as out of range
-            const float nan = __int_as_float(0x7fc00000);
-#pragma unroll
-            for (int k = 0; k < 3; k++) { rays_o[(size_t)n * 3 + k] = nan; rays_d[(size_t)n * 3 + k] = nan; }
-            continue;
-        }
-        ru_write_ray_lens(ru_load_pose(poses + (size_t)f * 12), f0, f1, f2, (uint32_t)pix[n], w, Ln, (size_t)n, rays_o, rays_d);
-    }
+    ru_generate_rays<size_t>(RuSegPoses{poses, seg_frame, pix, F, K}, ru_load_lens(lens), camera_flip, w, FB_BLOCK, N, rays_o, rays_d);
 }
 
 // ---------------------------------------------------------------------------------------------
 // backward: the three parts of seg_sum.h with eighteen sums per segment, columns 0..11 the pose's and 12..17 the lens's
 // ---------------------------------------------------------------------------------------------
-struct LensCam { uint32_t F, w; int camera_flip; };
+struct LensBwdArgs {
+    const float *poses;
+    uint32_t F, w;
+    int camera_flip;
+    const float *lens;
+    const int32_t *seg_frame, *pix;
+    uint32_t S, K, B;
+    const float *g_o, *g_d;
+    double *partials;                     // [S][B][18]
+};
 
-__device__ __forceinline__ void lens_load(const float *__restrict__ lens, double (&L)[6]) {
+// make_term of seg_sum.h: ru_lens_term with the rotation of the segment's frame and the lens in fp64
+__device__ __forceinline__ auto lens_terms(const LensBwdArgs &a) {
+    return [=](uint32_t f, size_t n0) {
+        double R[3][3], L[6];
+        ru_load_rotation(a.poses + (size_t)f * 12, R);
 #pragma unroll
-    for (int k = 0; k < 6; k++) L[k] = (double)lens[k];
+        for (int k = 0; k < 6; k++) L[k] = (double)a.lens[k];
+        const RuFlip<double> flip = ru_flip<double>(a.camera_flip);
+        return [=](uint32_t k, double (&acc)[18]) {
+            const size_t n = n0 + k;
+            ru_lens_term(R, flip, (uint32_t)a.pix[n], a.w, L, a.g_o, a.g_d, n, acc);
+        };
+    };
 }
 
-__global__ void __launch_bounds__(FB_BLOCK)
-k_lens_bwd_thread(const float *__restrict__ poses, LensCam c, const float *__restrict__ lens, const int32_t *__restrict__ seg_frame,
-                  const int32_t *__restrict__ pix, uint32_t S, uint32_t K, const float *__restrict__ g_o, const float *__restrict__ g_d,
-                  double *__restrict__ partials) {
-    const uint32_t s = blockIdx.x * FB_BLOCK + threadIdx.x;
-    if (s >= S) return;
-    const uint32_t f = (uint32_t)seg_frame[s];
-    if (f >= c.F) return;
-    double R[3][3], L[6];
-    ru_load_rotation(poses + (size_t)f * 12, R);
-    lens_load(lens, L);
-    const double f0 = (c.camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (c.camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (c.camera_flip >> 0) & 1 ? -1.0 : 1.0;
-    double acc[18];
-#pragma unroll
-    for (int k = 0; k < 18; k++) acc[k] = 0.0;
-    for (uint32_t k = 0; k < K; k++) {
-        const size_t n = (size_t)s * K + k;
-        ru_lens_term(R, f0, f1, f2, (uint32_t)pix[n], c.w, L, g_o, g_d, n, acc);
-    }
-#pragma unroll
-    for (int k = 0; k < 18; k++) partials[(size_t)s * 18 + k] = acc[k];
+__global__ void __launch_bounds__(SEG_BLOCK)
+k_lens_bwd_thread(LensBwdArgs a) {
+    seg_sum_thread<18>(a.seg_frame, a.F, a.S, a.K, a.partials, lens_terms(a));
 }
 
-__global__ void __launch_bounds__(FB_BLOCK)
-k_lens_bwd_block(const float *__restrict__ poses, LensCam c, const float *__restrict__ lens, const int32_t *__restrict__ seg_frame,
-                 const int32_t *__restrict__ pix, uint32_t K, uint32_t B, const float *__restrict__ g_o, const float *__restrict__ g_d,
-                 double *__restrict__ partials) {
-    __shared__ double red[18][FB_BLOCK / 64];
-    const uint32_t s = blockIdx.x / B, b = blockIdx.x - s * B;
-    const uint32_t f = (uint32_t)seg_frame[s];
-    if (f >= c.F) return;                                     // the whole block: nobody waits at the block sum's barrier
-    double R[3][3], L[6];
-    ru_load_rotation(poses + (size_t)f * 12, R);
-    lens_load(lens, L);
-    const double f0 = (c.camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (c.camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (c.camera_flip >> 0) & 1 ? -1.0 : 1.0;
-    double acc[18];
-#pragma unroll
-    for (int k = 0; k < 18; k++) acc[k] = 0.0;
-    for (uint32_t k = b * FB_BLOCK + threadIdx.x; k < K; k += B * FB_BLOCK) {
-        const size_t n = (size_t)s * K + k;
-        ru_lens_term(R, f0, f1, f2, (uint32_t)pix[n], c.w, L, g_o, g_d, n, acc);
-    }
-    nsr_block_sum_stage(acc, red);
-    if (threadIdx.x < 18) partials[(size_t)blockIdx.x * 18 + threadIdx.x] = nsr_block_sum_col<FB_BLOCK / 64>(red[threadIdx.x]);
+__global__ void __launch_bounds__(SEG_BLOCK)
+k_lens_bwd_block(LensBwdArgs a) {
+    __shared__ double red[18][SEG_BLOCK / 64];
+    seg_sum_block<18>(a.seg_frame, a.F, a.K, a.B, a.partials, red, lens_terms(a));
 }
 
 // Blocks 0 .. pose_rows-1 (pose_rows = F, or 0 without grad_poses): a frame's pose row, columns 0..11 of the segments naming it.
@@ -134,15 +105,9 @@ int nsr_generate_rays_lens_backward(const float *poses, uint32_t F, uint32_t w, 
     if (N != 0) {
         NSR_CHECK_PTR(poses); NSR_CHECK_PTR(lens); NSR_CHECK_PTR(seg_frame); NSR_CHECK_PTR(pix); NSR_CHECK_PTR(grad_rays_o);
         NSR_CHECK_PTR(grad_rays_d); NSR_CHECK_PTR(workspace);
-        if (w == 0 || h == 0 || ((uintptr_t)workspace & 7u) != 0 || N > 0xffffffffull || (uint64_t)S * B > 0x7fffffffull)
-            return NSR_ERR_INVALID_ARG;
-        const LensCam c{F, w, camera_flip};
-        if (K < SEG_THREAD_K)
-            hipLaunchKernelGGL(k_lens_bwd_thread, dim3(nsr_div_up(S, FB_BLOCK)), dim3(FB_BLOCK), 0, (hipStream_t)stream, poses, c, lens,
-                               seg_frame, pix, S, K, grad_rays_o, grad_rays_d, (double *)workspace);
-        else
-            hipLaunchKernelGGL(k_lens_bwd_block, dim3(S * B), dim3(FB_BLOCK), 0, (hipStream_t)stream, poses, c, lens, seg_frame, pix, K, B,
-                               grad_rays_o, grad_rays_d, (double *)workspace);
+        if (w == 0 || h == 0 || !seg_sum_ok(N, S, K, workspace)) return NSR_ERR_INVALID_ARG;
+        const LensBwdArgs a{poses, F, w, camera_flip, lens, seg_frame, pix, S, K, B, grad_rays_o, grad_rays_d, (double *)workspace};
+        seg_sum_launch(k_lens_bwd_thread, k_lens_bwd_block, S, K, (hipStream_t)stream, a);
     }
     // no rays: the lens row and every frame's row are still written (zeros)
     const uint32_t pose_rows = grad_poses != nullptr ? F : 0u;

@@ -11,6 +11,7 @@
 // pose word (a broadcast, no bank conflict).
 #include "nsr_common.h"
 #include "rm_util.h"
+#include "ray_pose.h"
 
 #pragma clang fp contract(off)
 
@@ -146,9 +147,8 @@ int nsr_occ_mark_untrained(float *density_grid, uint8_t *bitfield, uint32_t C, u
     a.x_lo = x_lo; a.x_hi = x_hi; a.y_lo = y_lo; a.y_hi = y_hi;
     a.kx_lo = sqrt(1.0 + x_lo * x_lo); a.kx_hi = sqrt(1.0 + x_hi * x_hi);
     a.ky_lo = sqrt(1.0 + y_lo * y_lo); a.ky_hi = sqrt(1.0 + y_hi * y_hi);
-    a.f0 = (camera_flip >> 2) & 1 ? -1.0 : 1.0;            // nerf_lib.py:121, bit order [2,1,0], as k_generate_rays
-    a.f1 = (camera_flip >> 1) & 1 ? -1.0 : 1.0;
-    a.f2 = (camera_flip >> 0) & 1 ? -1.0 : 1.0;
+    const RuFlip<double> flip = ru_flip<double>(camera_flip);          // as k_generate_rays
+    a.f0 = flip.f0; a.f1 = flip.f1; a.f2 = flip.f2;
     if (n_untrained) hipLaunchKernelGGL(k_ou_zero, dim3(1), dim3(64), 0, s, n_untrained, C);
     hipLaunchKernelGGL(k_ou_mark, dim3(nsr_grid_1d(a.N, OU_BLOCK)), dim3(OU_BLOCK), 0, s, a);
     return nsr_launch_status();

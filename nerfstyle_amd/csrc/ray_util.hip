@@ -74,12 +74,7 @@ __global__ void k_packbits(const float *__restrict__ grid, uint32_t N, float thr
 __global__ void k_generate_rays(const float *__restrict__ pose, uint32_t w, uint32_t h, float fx, float fy, float cx,
                                 float cy, int camera_flip, const int32_t *__restrict__ pix, uint32_t N,
                                 float *__restrict__ rays_o, float *__restrict__ rays_d) {
-    const RuPose P = ru_load_pose(pose);
-    const float f0 = (camera_flip >> 2) & 1 ? -1.0f : 1.0f;   // nerf_lib.py:121, bit order [2,1,0]
-    const float f1 = (camera_flip >> 1) & 1 ? -1.0f : 1.0f;
-    const float f2 = (camera_flip >> 0) & 1 ? -1.0f : 1.0f;
-    for (uint32_t n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x)
-        ru_write_ray(P, f0, f1, f2, pix ? (uint32_t)pix[n] : n, w, fx, fy, cx, cy, n, rays_o, rays_d);
+    ru_generate_rays<uint32_t>(RuOnePose{pose, pix}, RuPinhole{fx, fy, cx, cy}, camera_flip, w, blockDim.x, N, rays_o, rays_d);
 }
 
 // Backward of k_generate_rays with respect to the pose: grad_pose[:, 3] = sum_n grad_o[n]; with c_n the pixel's camera-frame
@@ -97,12 +92,13 @@ k_generate_rays_bwd(const float *__restrict__ pose, uint32_t w, float fx, float 
     __shared__ double red[12][RU_BLOCK / 64];
     double R[3][3];
     ru_load_rotation(pose, R);
-    const double f0 = (camera_flip >> 2) & 1 ? -1.0 : 1.0, f1 = (camera_flip >> 1) & 1 ? -1.0 : 1.0, f2 = (camera_flip >> 0) & 1 ? -1.0 : 1.0;
+    const RuFlip<double> flip = ru_flip<double>(camera_flip);
+    const RuPinhole cam{fx, fy, cx, cy};
     double acc[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) acc[k] = 0.0;
     for (uint32_t n = blockIdx.x * RU_BLOCK + threadIdx.x; n < N; n += gridDim.x * RU_BLOCK)
-        ru_pose_term(R, f0, f1, f2, pix ? (uint32_t)pix[n] : n, w, fx, fy, cx, cy, g_o, g_d, n, acc);
+        ru_pose_term(R, flip, pix ? (uint32_t)pix[n] : n, w, cam, g_o, g_d, n, acc);
     nsr_block_sum_stage(acc, red);
     if (threadIdx.x < 12) partials[(size_t)blockIdx.x * 12 + threadIdx.x] = nsr_block_sum_col<RU_BLOCK / 64>(red[threadIdx.x]);
 }

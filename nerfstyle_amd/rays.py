@@ -36,10 +36,27 @@ def pixel_ids(intr: Intrinsics, patch: Optional[Box2D] = None, precrop: float = 
     return ids, w, h, dx, dy
 
 
+def _empty_rays(N, device):
+    """(rays_o, rays_d) for a forward kernel to fill"""
+    return torch.empty(N, 3, dtype=torch.float32, device=device), torch.empty(N, 3, dtype=torch.float32, device=device)
+
+
+def _backward_inputs(g_o, g_d, workspace_bytes, device):
+    """what every ray backward takes: the two incoming gradients as contiguous float32 and its fp64 workspace"""
+    return (g_o.to(torch.float32).contiguous(), g_d.to(torch.float32).contiguous(),
+            torch.empty(int(workspace_bytes) // 8, dtype=torch.float64, device=device))
+
+
+def _pad_pose_rows(grad, rows):
+    """grad [F,3,4] (or None) as the gradient of poses with `rows` rows: the last rows of [F,4,4] poses never reach the rays"""
+    if grad is None or rows == 3:
+        return grad
+    return torch.cat((grad, torch.zeros(grad.shape[0], 1, 4, dtype=torch.float32, device=grad.device)), dim=1)
+
+
 def _launch_generate_rays(pose, W, H, fx, fy, cx, cy, camera_flip, ids):
     N = ids.shape[0]
-    rays_o = torch.empty(N, 3, dtype=torch.float32, device=pose.device)
-    rays_d = torch.empty(N, 3, dtype=torch.float32, device=pose.device)
+    rays_o, rays_d = _empty_rays(N, pose.device)
     L.check(L.lib().nsr_generate_rays(L.p(pose), W, H, fx, fy, cx, cy, camera_flip, L.p(ids), N, L.p(rays_o), L.p(rays_d), L.stream()),
             'generate_rays')
     return rays_o, rays_d
@@ -58,9 +75,8 @@ class _generate_rays_fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_o, g_d):
         pose, ids = ctx.saved_tensors
-        N, dev = ids.shape[0], pose.device
-        g_o, g_d = g_o.to(torch.float32).contiguous(), g_d.to(torch.float32).contiguous()
-        ws = torch.empty(int(L.lib().nsr_generate_rays_backward_workspace_bytes(N)) // 8, dtype=torch.float64, device=dev)
+        N = ids.shape[0]
+        g_o, g_d, ws = _backward_inputs(g_o, g_d, L.lib().nsr_generate_rays_backward_workspace_bytes(N), pose.device)
         grad = torch.zeros_like(pose)            # a [4,4] pose: its last row never reaches the rays
         L.check(L.lib().nsr_generate_rays_backward(L.p(pose), *ctx.args, L.p(ids), N, L.p(g_o), L.p(g_d), L.p(ws), L.p(grad),
                                                    L.stream()), 'generate_rays_backward')
@@ -116,9 +132,7 @@ def generate_rays(pose, intr: Intrinsics, img=None, patch: Optional[Box2D] = Non
 # ---- mixed-frame batches: S segments of K rays, segment s of frame seg_frame[s] (nsr_generate_rays_frames) ----------------------
 def _launch_generate_rays_frames(poses, W, H, fx, fy, cx, cy, camera_flip, seg_frame, pix, K):
     F, S = poses.shape[0], seg_frame.shape[0]
-    N = S * K
-    rays_o = torch.empty(N, 3, dtype=torch.float32, device=poses.device)
-    rays_d = torch.empty(N, 3, dtype=torch.float32, device=poses.device)
+    rays_o, rays_d = _empty_rays(S * K, poses.device)
     with profiling.timed('generate_rays_frames'):
         L.check(L.lib().nsr_generate_rays_frames(L.p(poses), F, W, H, fx, fy, cx, cy, camera_flip, L.p(seg_frame), L.p(pix), S, K,
                                                  L.p(rays_o), L.p(rays_d), L.stream()), 'generate_rays_frames')
@@ -140,15 +154,12 @@ class _generate_rays_frames_fn(torch.autograd.Function):
     def backward(ctx, g_o, g_d):
         poses, seg_frame, pix = ctx.saved_tensors
         F, S, K, dev = poses.shape[0], seg_frame.shape[0], ctx.K, poses.device
-        g_o, g_d = g_o.to(torch.float32).contiguous(), g_d.to(torch.float32).contiguous()
-        ws = torch.empty(int(L.lib().nsr_generate_rays_frames_backward_workspace_bytes(F, S, K)) // 8, dtype=torch.float64, device=dev)
+        g_o, g_d, ws = _backward_inputs(g_o, g_d, L.lib().nsr_generate_rays_frames_backward_workspace_bytes(F, S, K), dev)
         grad = torch.empty(F, 3, 4, dtype=torch.float32, device=dev)
         with profiling.timed('generate_rays_frames_bwd'):
             L.check(L.lib().nsr_generate_rays_frames_backward(L.p(poses), F, *ctx.args, L.p(seg_frame), L.p(pix), S, K, L.p(g_o),
                                                               L.p(g_d), L.p(ws), L.p(grad), L.stream()), 'generate_rays_frames_backward')
-        if ctx.rows == 4:                        # [F,4,4] poses: their last rows never reach the rays
-            grad = torch.cat((grad, torch.zeros(F, 1, 4, dtype=torch.float32, device=dev)), dim=1)
-        return (grad,) + (None,) * 10
+        return (_pad_pose_rows(grad, ctx.rows),) + (None,) * 10
 
 
 def generate_rays_frames(poses, seg_frame, pix, K: int, intr: Intrinsics, camera_flip: int = 0, pose_grad: bool = False,
@@ -185,9 +196,7 @@ def _check_lens(lens):
 
 def _launch_generate_rays_lens(poses, lens, W, H, camera_flip, seg_frame, pix, K):
     F, S = poses.shape[0], seg_frame.shape[0]
-    N = S * K
-    rays_o = torch.empty(N, 3, dtype=torch.float32, device=poses.device)
-    rays_d = torch.empty(N, 3, dtype=torch.float32, device=poses.device)
+    rays_o, rays_d = _empty_rays(S * K, poses.device)
     with profiling.timed('generate_rays_lens'):
         L.check(L.lib().nsr_generate_rays_lens(L.p(poses), F, W, H, L.p(lens), camera_flip, L.p(seg_frame), L.p(pix), S, K, L.p(rays_o),
                                                L.p(rays_d), L.stream()), 'generate_rays_lens')
@@ -209,17 +218,14 @@ class _generate_rays_lens_fn(torch.autograd.Function):
     def backward(ctx, g_o, g_d):
         poses, lens, seg_frame, pix = ctx.saved_tensors
         F, S, K, dev = poses.shape[0], seg_frame.shape[0], ctx.K, poses.device
-        g_o, g_d = g_o.to(torch.float32).contiguous(), g_d.to(torch.float32).contiguous()
-        ws = torch.empty(int(L.lib().nsr_generate_rays_lens_backward_workspace_bytes(F, S, K)) // 8, dtype=torch.float64, device=dev)
+        g_o, g_d, ws = _backward_inputs(g_o, g_d, L.lib().nsr_generate_rays_lens_backward_workspace_bytes(F, S, K), dev)
         grad = torch.empty(F, 3, 4, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         grad_lens = torch.empty(6, dtype=torch.float32, device=dev)
         with profiling.timed('generate_rays_lens_bwd'):
             L.check(L.lib().nsr_generate_rays_lens_backward(L.p(poses), F, *ctx.size, L.p(lens), ctx.flip, L.p(seg_frame), L.p(pix), S, K,
                                                             L.p(g_o), L.p(g_d), L.p(ws), L.p(grad), L.p(grad_lens), L.stream()),
                     'generate_rays_lens_backward')
-        if grad is not None and ctx.rows == 4:   # [F,4,4] poses: their last rows never reach the rays
-            grad = torch.cat((grad, torch.zeros(F, 1, 4, dtype=torch.float32, device=dev)), dim=1)
-        return (grad, grad_lens if ctx.needs_input_grad[1] else None) + (None,) * 6
+        return (_pad_pose_rows(grad, ctx.rows), grad_lens if ctx.needs_input_grad[1] else None) + (None,) * 6
 
 
 def _rays_lens(poses, lens, W, H, camera_flip, seg_frame, pix, K, pose_grad):

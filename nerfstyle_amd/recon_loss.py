@@ -12,37 +12,42 @@ import torch
 from . import _lib as L
 
 
+def _prepare(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, ray_weight, ray_err_out):
+    """what the forward of both Functions does before its launch -> (N, rgb_map, cls, nc, target_cls or None, g_rgb, g_cls, out):
+    the inputs detached as contiguous float32, the gradient and loss-term buffers, the checks of targets, pix and weights"""
+    N = rgb_map.shape[0]
+    rgb_map = rgb_map.detach().to(torch.float32).contiguous()
+    with_ce = classes is not None and classes.shape[1] > 0 and ce_lambda != 0.0
+    cls = classes.detach().to(torch.float32).contiguous() if with_ce else None
+    g_rgb = torch.empty_like(rgb_map)
+    g_cls = torch.empty_like(cls) if with_ce else None
+    out = torch.empty(3, dtype=torch.float32, device=rgb_map.device)
+    assert target_rgb.dtype == torch.float32 and target_rgb.is_contiguous()
+    if with_ce:
+        assert target_cls.dtype == torch.int64 and target_cls.is_contiguous()
+    if pix is not None:
+        assert pix.dtype == torch.int64 and pix.is_contiguous() and pix.numel() == N
+    else:
+        assert target_rgb.shape[0] == N
+    for t in (ray_weight, ray_err_out):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == N and not t.requires_grad), 'ray_weight / ray_err_out: [N] float32'
+    return N, rgb_map, cls, cls.shape[1] if with_ce else 0, target_cls if with_ce else None, g_rgb, g_cls, out
+
+
 class _recon_loss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale, ray_weight=None, ray_err_out=None):
         ctx.set_materialize_grads(False)
-        N = rgb_map.shape[0]
-        dev = rgb_map.device
-        rgb_map = rgb_map.detach().to(torch.float32).contiguous()
-        with_ce = classes is not None and classes.shape[1] > 0 and ce_lambda != 0.0
-        cls = classes.detach().to(torch.float32).contiguous() if with_ce else None
-        nc = cls.shape[1] if with_ce else 0
-        g_rgb = torch.empty_like(rgb_map)
-        g_cls = torch.empty_like(cls) if with_ce else None
-        out = torch.empty(3, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.lib().nsr_recon_loss_workspace_bytes(N)) // 4, dtype=torch.float32, device=dev)
-        assert target_rgb.dtype == torch.float32 and target_rgb.is_contiguous()
-        if with_ce:
-            assert target_cls.dtype == torch.int64 and target_cls.is_contiguous()
-        if pix is not None:
-            assert pix.dtype == torch.int64 and pix.is_contiguous() and pix.numel() == N
-        else:
-            assert target_rgb.shape[0] == N
+        N, rgb_map, cls, nc, target_cls, g_rgb, g_cls, out = _prepare(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, ray_weight,
+                                                                      ray_err_out)
+        ws = torch.empty(int(L.lib().nsr_recon_loss_workspace_bytes(N)) // 4, dtype=torch.float32, device=rgb_map.device)
         if ray_weight is None and ray_err_out is None:
-            L.check(L.lib().nsr_recon_loss(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls) if with_ce else None, L.p(pix),
-                                           float(ce_lambda), float(factor), L.p(scale), L.p(g_rgb), L.p(g_cls), L.p(out), L.p(ws),
-                                           L.stream()), 'recon_loss')
+            L.check(L.lib().nsr_recon_loss(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls), L.p(pix), float(ce_lambda),
+                                           float(factor), L.p(scale), L.p(g_rgb), L.p(g_cls), L.p(out), L.p(ws), L.stream()), 'recon_loss')
         else:
-            for t in (ray_weight, ray_err_out):
-                assert t is None or (t.dtype == torch.float32 and t.numel() == N and not t.requires_grad), 'ray_weight / ray_err_out: [N] float32'
-            L.check(L.lib().nsr_recon_loss_weighted(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls) if with_ce else None,
-                                                    L.p(pix), L.p(ray_weight), float(ce_lambda), float(factor), L.p(scale), L.p(g_rgb),
-                                                    L.p(g_cls), L.p(ray_err_out), L.p(out), L.p(ws), L.stream()), 'recon_loss_weighted')
+            L.check(L.lib().nsr_recon_loss_weighted(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls), L.p(pix),
+                                                    L.p(ray_weight), float(ce_lambda), float(factor), L.p(scale), L.p(g_rgb), L.p(g_cls),
+                                                    L.p(ray_err_out), L.p(out), L.p(ws), L.stream()), 'recon_loss_weighted')
         ctx.save_for_backward(g_rgb, g_cls)
         ctx.terms = out
         return out[0]
@@ -53,7 +58,7 @@ class _recon_loss(torch.autograd.Function):
         if go is None:
             return (None,) * 10
         # the stored gradients already carry scale * factor; `go` is 1 for loss.backward()
-        return g_rgb * go, (g_cls * go if g_cls is not None else None), None, None, None, None, None, None, None, None
+        return (g_rgb * go, (g_cls * go if g_cls is not None else None)) + (None,) * 8
 
 
 class _recon_loss_exposure(torch.autograd.Function):
@@ -62,32 +67,16 @@ class _recon_loss_exposure(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb_map, classes, exposure, target_rgb, target_cls, pix, ce_lambda, factor, scale, ray_weight, ray_err_out, seg_frame, K):
         ctx.set_materialize_grads(False)
-        N, F = rgb_map.shape[0], exposure.shape[0]
-        S = seg_frame.numel()
-        dev = rgb_map.device
-        rgb_map = rgb_map.detach().to(torch.float32).contiguous()
+        N, rgb_map, cls, nc, target_cls, g_rgb, g_cls, out = _prepare(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, ray_weight,
+                                                                      ray_err_out)
+        F, S = exposure.shape[0], seg_frame.numel()
         exposure = exposure.detach().contiguous()
-        with_ce = classes is not None and classes.shape[1] > 0 and ce_lambda != 0.0
-        cls = classes.detach().to(torch.float32).contiguous() if with_ce else None
-        nc = cls.shape[1] if with_ce else 0
-        g_rgb = torch.empty_like(rgb_map)
-        g_cls = torch.empty_like(cls) if with_ce else None
         g_exp = torch.empty_like(exposure)
-        out = torch.empty(3, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.lib().nsr_recon_loss_exposure_workspace_bytes(N, F, S, K)) // 8, dtype=torch.float64, device=dev)
-        assert target_rgb.dtype == torch.float32 and target_rgb.is_contiguous()
-        if with_ce:
-            assert target_cls.dtype == torch.int64 and target_cls.is_contiguous()
-        if pix is not None:
-            assert pix.dtype == torch.int64 and pix.is_contiguous() and pix.numel() == N
-        else:
-            assert target_rgb.shape[0] == N
-        for t in (ray_weight, ray_err_out):
-            assert t is None or (t.dtype == torch.float32 and t.numel() == N and not t.requires_grad), 'ray_weight / ray_err_out: [N] float32'
-        L.check(L.lib().nsr_recon_loss_exposure(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls) if with_ce else None,
-                                                L.p(pix), L.p(ray_weight), L.p(exposure), F, L.p(seg_frame), S, K, float(ce_lambda),
-                                                float(factor), L.p(scale), L.p(g_rgb), L.p(g_cls), L.p(g_exp), L.p(ray_err_out), L.p(out),
-                                                L.p(ws), L.stream()), 'recon_loss_exposure')
+        ws = torch.empty(int(L.lib().nsr_recon_loss_exposure_workspace_bytes(N, F, S, K)) // 8, dtype=torch.float64, device=rgb_map.device)
+        L.check(L.lib().nsr_recon_loss_exposure(L.p(rgb_map), L.p(cls), N, nc, L.p(target_rgb), L.p(target_cls), L.p(pix), L.p(ray_weight),
+                                                L.p(exposure), F, L.p(seg_frame), S, K, float(ce_lambda), float(factor), L.p(scale),
+                                                L.p(g_rgb), L.p(g_cls), L.p(g_exp), L.p(ray_err_out), L.p(out), L.p(ws), L.stream()),
+                'recon_loss_exposure')
         ctx.save_for_backward(g_rgb, g_cls, g_exp)
         ctx.terms = out
         return out[0]
@@ -142,38 +131,18 @@ def recon_loss(rgb_map, classes, target_rgb, target_cls=None, pix=None, ce_lambd
     d loss / d exposure, one deterministic fp64 sum per frame carrying scale * factor, reaches exposure.grad through autograd; with
     backward=True it is pushed together with the renderer's outputs.  ray_weight and ray_err_out stay optional.  With
     exposure None nothing of this runs."""
-    if exposure is not None:
-        return _recon_loss_with_exposure(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale, backward, ray_weight,
-                                         ray_err_out, exposure, seg_frame, rays_per_segment)
-    loss = _recon_loss.apply(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale, ray_weight, ray_err_out)
+    if exposure is None:
+        loss = _recon_loss.apply(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale, ray_weight, ray_err_out)
+        inputs = (rgb_map, classes)
+    else:
+        K = _exposure_arguments(rgb_map, exposure, seg_frame, rays_per_segment)
+        loss = _recon_loss_exposure.apply(rgb_map, classes, exposure, target_rgb, target_cls, pix, ce_lambda, factor, scale, ray_weight,
+                                          ray_err_out, seg_frame, K)
+        inputs = (rgb_map, classes, exposure)
     if not backward or loss.grad_fn is None:
         return loss
-    g_rgb, g_cls = loss.grad_fn.saved_tensors
-    outs, grads = [rgb_map], [g_rgb]
-    if g_cls is not None and classes is not None and classes.requires_grad:
-        outs.append(classes)
-        grads.append(g_cls)
-    if not rgb_map.requires_grad:
-        outs, grads = outs[1:], grads[1:]
-    if outs:
-        torch.autograd.backward(outs, grads)
-    det = loss.detach()
-    det._nsr_terms = loss.grad_fn.terms
-    return det
-
-
-def _recon_loss_with_exposure(rgb_map, classes, target_rgb, target_cls, pix, ce_lambda, factor, scale, backward, ray_weight, ray_err_out,
-                              exposure, seg_frame, rays_per_segment):
-    K = _exposure_arguments(rgb_map, exposure, seg_frame, rays_per_segment)
-    loss = _recon_loss_exposure.apply(rgb_map, classes, exposure, target_rgb, target_cls, pix, ce_lambda, factor, scale, ray_weight,
-                                      ray_err_out, seg_frame, K)
-    if not backward or loss.grad_fn is None:
-        return loss
-    g_rgb, g_cls, g_exp = loss.grad_fn.saved_tensors
-    pairs = [(rgb_map, g_rgb), (exposure, g_exp)]
-    if g_cls is not None and classes is not None:
-        pairs.append((classes, g_cls))
-    pairs = [(t, g) for t, g in pairs if t.requires_grad]
+    # the inputs that want a gradient with the one the kernel stored for them (none for classes without the cross-entropy term)
+    pairs = [(t, g) for t, g in zip(inputs, loss.grad_fn.saved_tensors) if g is not None and t is not None and t.requires_grad]
     if pairs:
         torch.autograd.backward([t for t, _ in pairs], [g for _, g in pairs])
     det = loss.detach()
