@@ -318,6 +318,7 @@ int nsr_grid_resolutions(uint32_t L, float S, uint32_t H, uint32_t *res_out);
  * offsets HOST [L+1] i32 (the reference passes a device tensor; it is 17 ints);
  * outputs of emb_dtype: layout [L,B,C] when out_blc == 0 (the reference kernel's) or
  * [B,L*C] when out_blc != 0 (what grid.py:58 returns after its permute+reshape copy).
+ * Rows whose input is outside [0,1] (gridencoder.cu:107-132) or NaN are written as zeros.
  * calc_grad_inputs != 0 -> NSR_ERR_UNSUPPORTED: no dy_dx buffer is written here; the input gradient comes from
  * nsr_grid_encode_input_backward, which recomputes the partials.
  * C in {1,2,4,8} like the reference; L <= 32. */
@@ -329,7 +330,7 @@ int nsr_grid_encode_forward(const float *inputs, const void *embeddings, int emb
 /* replaces grid_encode_backward (gridencoder.h:13, gridencoder.cu:238-328,464-494).
  * grad of grad_dtype in the layout selected by grad_blc; grad_embeddings [rows,C] f32 ALWAYS
  * (fp32 atomics; the reference accumulates in half under AMP) and arrives zeroed or holding a
- * running sum (the kernel accumulates). */
+ * running sum (the kernel accumulates).  Rows whose input is outside [0,1] or NaN add nothing. */
 int nsr_grid_encode_backward(const void *grad, int grad_dtype, const float *inputs,
                              const int32_t *offsets, float *grad_embeddings, uint32_t B, uint32_t D,
                              uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
@@ -352,16 +353,19 @@ int nsr_grid_encode_input_backward(const void *grad, int grad_dtype, const float
  * params: fp32 master weights, flat, row-major [out,in] per layer, layers concatenated, the
  * last layer's rows padded to a multiple of 16 (nsr_mlp_param_count).  Hidden width 64, ReLU.
  * Compute contract: inputs, weights and hidden activations rounded to compute_dtype
- * (NSR_F16 | NSR_BF16), products accumulated in fp32 by v_mfma_f32_16x16x32_{f16,bf16}.
- * x [M,n_in] f32; y [M,n_out] f32 (after out_act).  n_in in {16,32,64}; n_out <= 16;
- * n_hidden_layers in {1,2}; n_neurons == 64. */
+ * (NSR_F16 | NSR_BF16), products accumulated in fp32 by v_mfma_f32_16x16x32_{f16,bf16} (K = 32 layers) and the
+ * 16x16x16 forms (a 16-wide first layer, the output layer's transpose in the backward, every weight gradient).
+ * x [M,n_in] f32, 16-byte aligned; y [M,n_out] f32 (after out_act).  n_in in {16,32}; 1 <= n_out <= 16;
+ * n_hidden_layers in {1,2}; n_neurons == 64; anything else -> NSR_ERR_UNSUPPORTED.  An out_act other than
+ * NSR_ACT_NONE | NSR_ACT_SIGMOID, or x off 16-byte alignment -> NSR_ERR_INVALID_ARG.  M == 0 -> NSR_OK.  Nothing is
+ * written on an error. */
 uint32_t nsr_mlp_param_count(uint32_t n_in, uint32_t n_out, uint32_t n_neurons, uint32_t n_hidden_layers);
 int nsr_mlp_forward(const float *x, const float *params, uint32_t M, uint32_t n_in, uint32_t n_out,
                     uint32_t n_neurons, uint32_t n_hidden_layers, int out_act, int compute_dtype,
                     float *y, nsr_stream_t stream);
 /* dy [M,n_out] f32 = dL/dy (post-activation); y [M,n_out] the forward output (for sigmoid').
- * dx [M,n_in] f32 or NULL; dparams [count] f32 is ACCUMULATED into (fp32 atomics, one add per
- * workgroup per weight).  Activations are recomputed, nothing is saved by the forward. */
+ * dx [M,n_in] f32 (16-byte aligned) or NULL; dparams [count] f32 or NULL is ACCUMULATED into (fp32 atomics, one add per
+ * workgroup per non-zero weight gradient).  Activations are recomputed, nothing is saved by the forward: y may be NULL. */
 int nsr_mlp_backward(const float *x, const float *params, const float *y, const float *dy, uint32_t M,
                      uint32_t n_in, uint32_t n_out, uint32_t n_neurons, uint32_t n_hidden_layers,
                      int out_act, int compute_dtype, float *dx, float *dparams, nsr_stream_t stream);

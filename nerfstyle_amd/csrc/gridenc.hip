@@ -46,8 +46,8 @@ k_grid_fwd(const float *__restrict__ inputs, const T *__restrict__ grid, T *__re
     const NsrLevel lv = levels.lv[level];
     T *out = out_blc ? outputs + ((size_t)b * L + level) * C : outputs + ((size_t)level * B + b) * C;
     const float x0 = inputs[(size_t)b * 3 + 0], x1 = inputs[(size_t)b * 3 + 1], x2 = inputs[(size_t)b * 3 + 2];
-    // :107-132 out-of-range inputs produce zeros
-    if (x0 < 0 || x0 > 1 || x1 < 0 || x1 > 1 || x2 < 0 || x2 > 1) {
+    // :107-132 out-of-range inputs produce zeros; so does NaN (the test is written so that NaN fails it), as in the fused field
+    if (!(x0 >= 0 && x0 <= 1 && x1 >= 0 && x1 <= 1 && x2 >= 0 && x2 <= 1)) {
 #pragma unroll
         for (int ch = 0; ch < C; ch++) GeIO<T>::st(out + ch, 0.0f);
         return;
@@ -82,7 +82,7 @@ k_grid_bwd(const T *__restrict__ grad, const float *__restrict__ inputs, float *
     const uint32_t level = blockIdx.y;
     const NsrLevel lv = levels.lv[level];
     const float x0 = inputs[(size_t)b * 3 + 0], x1 = inputs[(size_t)b * 3 + 1], x2 = inputs[(size_t)b * 3 + 2];
-    if (x0 < 0 || x0 > 1 || x1 < 0 || x1 > 1 || x2 < 0 || x2 > 1) return;   // :268-273
+    if (!(x0 >= 0 && x0 <= 1 && x1 >= 0 && x1 <= 1 && x2 >= 0 && x2 <= 1)) return;   // :268-273, and NaN
     const T *gp = grad_blc ? grad + ((size_t)b * L + level) * C : grad + ((size_t)level * B + b) * C;
     float gcur[C];
 #pragma unroll
