@@ -1028,6 +1028,53 @@ int nsr_mesh_filter_emit(const float *verts, const int32_t *faces, const int32_t
                          uint32_t F, void *workspace, uint32_t Vk, uint32_t Fk, int32_t *index_map, float *verts_out,
                          int32_t *faces_out, nsr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Occupancy components: connected components of the occupied cells of the occupancy grid, their statistics, and a cull that
+ * closes whole components (csrc/occ_components.hip, csrc/occ_cc_core.h; Renderer.cull_floaters).  The volume-level counterpart
+ * of the mesh cleaning above: detached specks of density sit in the grid as small islands of occupied cells, and every march
+ * walks through them.  Additive: the ABI version stays.  Every output is a pure function of the input: two calls give the same
+ * bits.
+ *
+ * Grid: C cascades of H^3 cells, the shape rule of every nsr_occ_* call (C in 1..8, H a power of two in 8..512, C*H^3 < 2^31).
+ * Cell id u = c * H^3 + morton(ix, iy, iz).  Cell u is OCCUPIED iff bit (u & 7) of bitfield byte (u >> 3) is set: the layout
+ *   nsr_packbits and nsr_occ_update write and nsr_occ_mark_untrained clears.  Connectivity reads the bitfield only, never
+ *   density_grid.
+ * Neighbours: two occupied cells of the SAME cascade whose coordinates differ by exactly 1 along exactly one axis
+ *   (6-connectivity).  No wrap-around between 0 and H - 1.  No link between cascades: each cascade is labelled, judged and culled
+ *   on its own (a link through the coarser cascade, which holds its own full copy of the inner region, would glue any floater
+ *   within one coarse cell of the scene back onto it).  Components are the transitive closure.
+ * labels [C*H^3] int32: labels[u] = the SMALLEST cell id of u's component if u is occupied, -1 if not.  A root is a u with
+ *   labels[u] == u.
+ * Statistics, indexed by cell id and meaningful at the roots: n_cells [C*H^3] uint32; lo, hi [C*H^3,3] int32, the inclusive box
+ *   of the component in cell coordinates (ix, iy, iz).  A cell that is no root holds 0, lo = H, hi = -1.  Integer adds, mins and
+ *   maxes are order-free, so the kernels use atomics and are deterministic all the same.
+ * Keep rule (the caller's; nerfstyle_amd/raymarching.py, keep_occupancy_components, elementwise torch on the device with no host
+ *   read): a component of cascade c is kept iff n_cells >= min_cells; (2 b_c / H)^2 * (ex^2 + ey^2 + ez^2) >= min_diagonal^2
+ *   with e = hi - lo + 1 and b_c = min(2^c, bound), in fp64 in this written order; and, with keep_largest = k, it is among the k
+ *   components of the most cells OF ITS OWN CASCADE among those that passed, ties to the smaller label.
+ * Cull.  keep [C*H^3] uint8, read at the roots.  For every occupied cell whose component is not kept the bit is cleared and, if
+ *   density_grid is given, the cell's word becomes -1.0f (0xBF800000): the untrained state, which nsr_occ_update never leaves and
+ *   the occupied-cell list never names (a later nsr_occ_mark_untrained re-opens such a cell if enough cameras see it).  Every
+ *   other grid word keeps its bits exactly, NaN and -0.0f included; every other bit stays.  With density_grid NULL only bits are
+ *   cleared: the next nsr_occ_update rebuilds them.  n_culled [C] uint32 (optional) is WRITTEN with the cells cleared per cascade
+ *   (zeroed by a kernel of the call, then integer atomics of block sums).  A label outside [0, C*H^3) at an occupied cell decides
+ *   nothing and is never dereferenced.
+ *
+ *   nsr_occ_components: an init launch (labels[u] = u or -1), a union launch (a lock-free union-find that hooks the larger root
+ *     under the smaller id; a thread owns one bitfield byte, one 2x2x2 Morton block, and unites each of its occupied cells with
+ *     its occupied +x, +y, +z neighbours) and a flatten launch.  labels doubles as the parent array while the call runs.
+ *   nsr_occ_component_stats: from labels as nsr_occ_components left them.
+ *   nsr_occ_cull: bitfield (and density_grid) in place.
+ * None of them uses a workspace or reads anything on the host: all three are legal inside a stream capture.
+ * NSR_ERR_INVALID_ARG before any launch: the shape rule; a NULL bitfield, labels, keep, n_cells, lo or hi; labels or density_grid
+ * not aligned to 16 bytes; n_cells, lo, hi or n_culled not aligned to 4.
+ * ------------------------------------------------------------------------------------------ */
+int nsr_occ_components(const uint8_t *bitfield, uint32_t C, uint32_t H, int32_t *labels, nsr_stream_t stream);
+int nsr_occ_component_stats(const int32_t *labels, uint32_t C, uint32_t H, uint32_t *n_cells, int32_t *lo, int32_t *hi,
+                            nsr_stream_t stream);
+int nsr_occ_cull(float *density_grid, uint8_t *bitfield, const int32_t *labels, const uint8_t *keep, uint32_t C, uint32_t H,
+                 uint32_t *n_culled, nsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

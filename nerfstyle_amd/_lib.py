@@ -140,6 +140,9 @@ SIGNATURES = {
     'nsr_mesh_filter_workspace_bytes': (u64, [u32, u32]),
     'nsr_mesh_filter_count': (i32, [vp, vp, vp, u32, u32, vp, vp, vp]),
     'nsr_mesh_filter_emit': (i32, [vp, vp, vp, vp, u32, u32, vp, u32, u32, vp, vp, vp, vp]),
+    'nsr_occ_components': (i32, [vp, u32, u32, vp, vp]),
+    'nsr_occ_component_stats': (i32, [vp, u32, u32, vp, vp, vp, vp]),
+    'nsr_occ_cull': (i32, [vp, vp, vp, vp, u32, u32, vp, vp]),
 }
 
 _lib = None

@@ -111,6 +111,112 @@ def mark_untrained_grid(density_grid, bitfield, poses, frustum, camera_flip, bou
     return n_untrained
 
 
+# ---- occupancy components and the floater cull (csrc/occ_components.hip; include/nsr.h, "Occupancy components") ----------------
+def _occ_cells(who, cascade, grid_size):
+    C, H = int(cascade), int(grid_size)
+    if not (1 <= C <= 8 and 8 <= H <= 512 and H & (H - 1) == 0 and C * H ** 3 < 2 ** 31):
+        raise ValueError('{}: cascade in 1..8 and grid_size a power of two in 8..512 with cascade * grid_size^3 < 2^31; got {} and '
+                         '{}'.format(who, cascade, grid_size))
+    return C, H, C * H ** 3
+
+
+def _occ_tensor(who, name, t, dtype, shape):
+    """a tensor of that dtype and number of elements"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != int(torch.Size(shape).numel()):
+        raise ValueError('{}: {} must be a {} tensor of shape {}; got {} {}'.format(
+            who, name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+    return t
+
+
+def _occ_on_device(*tensors):
+    """a CPU (or non-contiguous) tensor raises before anything is allocated ("no CPU fallback")"""
+    for t in tensors:
+        L.p(t)
+
+
+def check_cull_rule(min_cells, min_diagonal, keep_largest, who):
+    """the keep rule's arguments, in the words of mesh._check_keep_rule"""
+    if int(min_cells) != min_cells or not 0 <= min_cells < 2 ** 31:
+        raise ValueError('{}: min_cells must be an integer in 0 .. 2^31 - 1; got {}'.format(who, min_cells))
+    if not float(min_diagonal) >= 0.0:
+        raise ValueError('{}: min_diagonal must be >= 0; got {}'.format(who, min_diagonal))
+    if keep_largest is not None and (int(keep_largest) != keep_largest or keep_largest < 1):
+        raise ValueError('{}: keep_largest must be None or an integer >= 1; got {}'.format(who, keep_largest))
+
+
+def occupancy_components(bitfield, cascade, grid_size):
+    """nsr_occ_components: labels int32 [C*H^3] of the occupancy bitfield (uint8 [C*H^3/8] on the device).  labels[u] is the
+    smallest cell id of the component of cell u = c * H^3 + morton(ix, iy, iz), or -1 where the cell is not occupied; occupied
+    cells of one cascade that share a face are joined, nothing wraps and nothing joins two cascades.  No host read."""
+    C, H, cells = _occ_cells('occupancy_components', cascade, grid_size)
+    _occ_on_device(_occ_tensor('occupancy_components', 'bitfield', bitfield, torch.uint8, (cells // 8,)))
+    labels = torch.empty(cells, dtype=torch.int32, device=bitfield.device)
+    with profiling.timed('occ_components'):
+        L.check(L.lib().nsr_occ_components(L.p(bitfield), C, H, L.p(labels), L.stream()), 'occ_components')
+    return labels
+
+
+def occupancy_component_stats(labels, cascade, grid_size):
+    """nsr_occ_component_stats -> (n_cells int32 [C*H^3], lo, hi int32 [C*H^3,3]), indexed by cell id and meaningful at the roots
+    (labels[u] == u): the component's number of cells and its inclusive box in cell coordinates.  Every other cell holds 0,
+    lo = H, hi = -1.  `labels` as occupancy_components returns them.  No host read."""
+    C, H, cells = _occ_cells('occupancy_component_stats', cascade, grid_size)
+    _occ_on_device(_occ_tensor('occupancy_component_stats', 'labels', labels, torch.int32, (cells,)))
+    dev = labels.device
+    n_cells = torch.empty(cells, dtype=torch.int32, device=dev)
+    lo = torch.empty(cells, 3, dtype=torch.int32, device=dev)
+    hi = torch.empty(cells, 3, dtype=torch.int32, device=dev)
+    L.check(L.lib().nsr_occ_component_stats(L.p(labels), C, H, L.p(n_cells), L.p(lo), L.p(hi), L.stream()), 'occ_component_stats')
+    return n_cells, lo, hi
+
+
+def keep_occupancy_components(n_cells, lo, hi, cascade, grid_size, bound, min_cells=0, min_diagonal=0.0, keep_largest=None):
+    """The keep rule on occupancy_component_stats' arrays -> keep uint8 [C*H^3], set at the roots of the kept components.  A
+    component of cascade c is kept iff n_cells >= min_cells, (2 b_c / H)^2 * (ex^2 + ey^2 + ez^2) >= min_diagonal^2 (e = hi - lo
+    + 1 in cells, b_c = min(2^c, bound): the box's diagonal in the grid's units; fp64, in this written order) and, with
+    keep_largest = k, it is among the k components of the most cells of its own cascade among those that passed (ties to the
+    smaller label).  The defaults keep everything.  Elementwise torch over all cells and a fixed-k topk a cascade: no host read."""
+    check_cull_rule(min_cells, min_diagonal, keep_largest, 'keep_occupancy_components')
+    C, H, cells = _occ_cells('keep_occupancy_components', cascade, grid_size)
+    _occ_tensor('keep_occupancy_components', 'n_cells', n_cells, torch.int32, (cells,))
+    _occ_tensor('keep_occupancy_components', 'lo', lo, torch.int32, (cells, 3))
+    _occ_tensor('keep_occupancy_components', 'hi', hi, torch.int32, (cells, 3))
+    _occ_on_device(n_cells, lo, hi)
+    dev = n_cells.device
+    n = n_cells.view(C, H ** 3).to(torch.int64)
+    e = (hi.view(C, H ** 3, 3) - lo.view(C, H ** 3, 3) + 1).to(torch.float64)
+    b = torch.tensor([min(float(2 ** c), float(bound)) for c in range(C)], dtype=torch.float64, device=dev)
+    unit = 2.0 * b / float(H)
+    diag2 = (unit * unit).view(C, 1) * ((e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2])
+    ok = (n > 0) & (n >= int(min_cells)) & (diag2 >= float(min_diagonal) * float(min_diagonal))      # n > 0: a root
+    if keep_largest is not None:
+        k = min(int(keep_largest), H ** 3)
+        never = torch.iinfo(torch.int64).max
+        ids = torch.arange(cells, dtype=torch.int64, device=dev).view(C, H ** 3)
+        key = torch.where(ok, (0x7fffffff - n) * (1 << 32) + ids, never)                   # most cells first, then the label
+        best, at = torch.topk(key, k, dim=1, largest=False)
+        return torch.zeros(C, H ** 3, dtype=torch.uint8, device=dev).scatter_(1, at, (best != never).to(torch.uint8)).view(cells)
+    return ok.to(torch.uint8).view(cells)
+
+
+def cull_occupancy(density_grid, bitfield, labels, keep, cascade, grid_size):
+    """nsr_occ_cull, in place: every occupied cell whose component's root has keep == 0 loses its bit in `bitfield` and, with a
+    density_grid (float32 [C, H^3]; None: bits only), gets density_grid = -1, the untrained state that update_state never
+    changes.  Every other bit and grid word stays as it is.  -> n_culled int32 [C] on the device.  No host read."""
+    C, H, cells = _occ_cells('cull_occupancy', cascade, grid_size)
+    if density_grid is not None:
+        _occ_tensor('cull_occupancy', 'density_grid', density_grid, torch.float32, (C, H ** 3))
+    _occ_tensor('cull_occupancy', 'bitfield', bitfield, torch.uint8, (cells // 8,))
+    _occ_tensor('cull_occupancy', 'labels', labels, torch.int32, (cells,))
+    _occ_tensor('cull_occupancy', 'keep', keep, torch.uint8, (cells,))
+    _occ_on_device(density_grid, bitfield, labels, keep)
+    n_culled = torch.empty(C, dtype=torch.int32, device=bitfield.device)
+    with profiling.timed('occ_cull'):
+        L.check(L.lib().nsr_occ_cull(L.p(density_grid), L.p(bitfield), L.p(labels), L.p(keep), C, H, L.p(n_culled), L.stream()),
+                'occ_cull')
+    return n_culled
+
+
 def _march_workspace(N, device, bound, max_steps):
     nbytes = int(L.lib().nsr_march_rays_train_workspace_bytes(N, float(bound), int(max_steps)))
     return torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=device)

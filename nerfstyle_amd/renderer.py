@@ -238,6 +238,34 @@ class Renderer(torch.nn.Module):
                                                       self.cfg.flip_camera, self.bound, C, H, margin_cells, min_views, counts=counts)
         return (n_untrained, counts) if return_counts else n_untrained
 
+    @torch.no_grad()
+    def cull_floaters(self, min_cells: int = 0, min_diagonal: float = 0.0, keep_largest: Optional[int] = None, permanent: bool = True,
+                      return_labels: bool = False):
+        """Closes the small islands of occupied cells in the occupancy grid -- the floaters every march walks through: the
+        volume-level counterpart of Mesh.clean.  The occupied cells of density_bitfield are split into connected components
+        (cells of one cascade that share a face; raymarching.occupancy_components), each cascade on its own, and a component is
+        kept iff it has at least `min_cells` cells, the diagonal of its box of cells is at least `min_diagonal` (in the grid's
+        units, the world's -- with use_ndc the warped space the grid lives in) and, with keep_largest = k, it is among the k
+        components of the most cells of its cascade among those (ties to the smaller label).  The defaults keep everything.
+        Every cell of a component that is not kept loses its bit.
+        permanent=True also writes density_grid = -1 there, the untrained state: update_state never changes such a cell and never
+        lists it as occupied, and the marks are part of state_dict(), like those of mark_untrained_grid.  A later
+        mark_untrained_grid re-opens (sets to 0) the marked cells that enough cameras see, so call it before, not after.
+        permanent=False clears bits only, for inference until the next update_state rebuilds them.
+        It works on density_grid / density_bitfield, never on a pinned bitfield, reads nothing on the host and is deterministic:
+        data-parallel ranks that call it with the same arguments hold the same grid.  Opt-in; nothing calls it otherwise.
+        Returns n_culled (int32 [cascade] on the device: the cells closed per cascade), with return_labels also the labels the
+        cull was decided on (int32 [cascade * H^3]: the smallest cell id of the cell's component, -1 where it was not occupied)."""
+        raymarching.check_cull_rule(min_cells, min_diagonal, keep_largest, 'cull_floaters')
+        C, H = self.cascade, self.cfg.grid_size
+        if not self.density_grid.is_contiguous():
+            self.density_grid = self.density_grid.contiguous()
+        labels = raymarching.occupancy_components(self.density_bitfield, C, H)
+        n_cells, lo, hi = raymarching.occupancy_component_stats(labels, C, H)
+        keep = raymarching.keep_occupancy_components(n_cells, lo, hi, C, H, self.bound, min_cells, min_diagonal, keep_largest)
+        n_culled = raymarching.cull_occupancy(self.density_grid if permanent else None, self.density_bitfield, labels, keep, C, H)
+        return (n_culled, labels) if return_labels else n_culled
+
     def pin_march_bitfield(self, bitfield: Optional[torch.Tensor]):
         """Benchmark / debugging hook: march through THIS bitfield while update_state keeps maintaining density_grid,
         mean_density and density_bitfield from the model as usual (None: back to density_bitfield).  Synthetic
