@@ -413,7 +413,8 @@ int nsr_field_forward(const nsr_field_desc *desc, const void *tables, const floa
  * density encoder's features and their three spatial tangents go through the density net together; nothing is saved, no
  * atomics.  Reads the density half of `tables` only.  sigmas [M] f32 or NULL: bit-identical to nsr_field_forward with
  * rgbs == NULL.  grads [M,3] f32 = density_scale * exp(clamp(logit,-15,15)) * d logit / d x (the trunc_exp rule of the
- * backward); with normalize != 0 the unit normal -grad / max(|grad|, 1e-20) instead (a zero gradient stays a zero vector).
+ * backward); with normalize != 0 the unit normal -grad / |grad| instead, for every gradient with finite components (a zero
+ * gradient stays a zero vector).
  * Samples whose position is NaN or encodes outside [0,1] get the forward's sigma and a zero gradient; slots at or past
  * *m_dev keep their sigma and get a zero gradient.  Capture-safe, no host read.  L != 16 -> NSR_ERR_UNSUPPORTED. */
 int nsr_field_density_gradient(const nsr_field_desc *desc, const void *tables, const float *mlp_params,

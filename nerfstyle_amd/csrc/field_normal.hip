@@ -26,8 +26,8 @@
 //
 // Output: grad_x sigma_k = density_scale * exp(clamp(logit, -15, 15)) * dlogit_k * du_k/dx_k with du_k/dx_k =
 // 1 / (2 * bbox_size[k]) (field_unit) -- the trunc_exp rule of the backward (tcnn_nerf.py:62-66).  normalize: the unit normal
-// -grad / max(|grad|, 1e-20); a zero gradient gives a zero vector.  Samples whose encoder input is outside [0,1] or NaN get
-// sigma as the forward gives it and a zero gradient; slots at or past *m_dev keep their sigma and get a zero gradient.
+// -grad / |grad| for every gradient with finite components; a zero gradient gives a zero vector.  Samples whose encoder input
+// is outside [0,1] or NaN get sigma as the forward gives it and a zero gradient; slots at or past *m_dev keep their sigma and get a zero gradient.
 #include "field_common.h"
 
 constexpr int DG_W1C = FW_SIGMA_TOTAL;              // W1 with res_l / res_15 in its columns: four frag32 (shorts)
@@ -194,8 +194,17 @@ k_field_density_grad(DensityGradArgs da) {
                     const float big = fmaxf(fmaxf(fabsf(gx), fabsf(gy)), fabsf(gz));
                     if (big > 0.f) {
                         const float rx = gx / big, ry = gy / big, rz = gz / big;
-                        const float inv = -1.0f / fmaxf(big * sqrtf(rx * rx + ry * ry + rz * rz), 1e-20f);
-                        gx *= inv; gy *= inv; gz *= inv;
+                        const float len = sqrtf(rx * rx + ry * ry + rz * rz);   // of the rescaled vector: in [1, sqrt 3]
+                        const float norm = big * len;                           // |grad|: inf above FLT_MAX
+                        if (norm >= 1e-20f && norm <= 3.402823466e+38f) {
+                            const float inv = -1.0f / norm;
+                            gx *= inv; gy *= inv; gz *= inv;
+                        } else {
+                            // a gradient below 1e-20 (a tiny density_scale) is still a direction, and so is one whose
+                            // components are finite while its length is not: 1 / |grad| would overflow or vanish
+                            const float inv = -1.0f / len;
+                            gx = rx * inv; gy = ry * inv; gz = rz * inv;
+                        }
                     } else {
                         gx = gy = gz = 0.f;                             // also turns -0 into +0
                     }
