@@ -19,12 +19,16 @@ share one block and the oracle's fp32 sums are longest), and the kernel's fp32 s
 random walk of at most 1 500 roundings of 6e-8 each: ~2e-6), so the bar is the 2e-5 of the comparison above.
 
 A launch gives every wave ONE 16-sample tile until the batch exceeds 262 144 samples, so a wave meets a block change
-only where blocks hold fewer than 16 samples: the synthetic blocks hold 1 .. 5."""
+only where blocks hold fewer than 16 samples: the synthetic blocks hold 1 .. 5.  Of this file only test_marched_patch goes
+past that size (its waves walk more than one tile), with one aggregate per level.  The walk of two and three tiles a wave --
+the key, the lattices and the prefetches carried across a tile boundary -- is test_gpu_table_scatter_walk.py's; the
+position builders and the fp64 scatter are shared with it (table_scatter_cases.py)."""
 import numpy as np
 import pytest
 import torch
 
 from helpers import rel_l2, room_cameras, small_scene
+from table_scatter_cases import SYNTHETIC, np_trilinear_scatter, unit_of
 
 pytestmark = pytest.mark.gpu
 
@@ -55,99 +59,6 @@ def _model(dev, dt='f16', table_dtype=None):
 @pytest.fixture(scope='module')
 def model(dev):
     return _model(dev)
-
-
-# ---------------------------------------------------------------------------------------------
-# positions: blocks are the sample order's keys, 1/1024 of the encoder input u per axis; x = 8 u - 6 for the +-2 box
-# ---------------------------------------------------------------------------------------------
-def _block_points(rng, blocks):
-    """1 .. 5 points inside each block (bx, by, bz), block after block, as float32 positions"""
-    out = []
-    for b in blocks:
-        n = int(rng.integers(1, 6))
-        u = (np.asarray(b, np.float64)[None, :] + 0.02 + 0.96 * rng.random((n, 3))) / 1024.0
-        out.append(u * 8.0 - 6.0)
-    return np.concatenate(out).astype(np.float32)
-
-
-def unit_of(pts):
-    """field_unit (field_common.h) in the same fp32 operations"""
-    xn = (pts.astype(np.float32) - np.float32(-2.0)) / np.float32(4.0)
-    return (xn + np.float32(1.0)) / np.float32(2.0)
-
-
-def _sites(rng, n):
-    """(y, z) block coordinates of n runs inside the box, all different"""
-    s = set()
-    while len(s) < n:
-        s.add((int(rng.integers(520, 1016)), int(rng.integers(520, 1016))))
-    return sorted(s)
-
-
-def _x_places(k_parity):
-    """first x block of a run of four: interior, touching u = 0 (outside the box, still encoded; the order's key clamps
-    there, so the walk follows the buffer), touching u = 1 (block 1023: the cell of a sample at u = 1 clamps to res - 1)"""
-    return [700 + k_parity, k_parity, 1020 + k_parity]
-
-
-def case_x_runs(rng):
-    chunks = []
-    for parity in (0, 1):
-        for k in _x_places(parity):
-            for (y, z) in _sites(rng, 40):
-                chunks.append(_block_points(rng, [(k + i, y, z) for i in range(4) if k + i < 1024]))
-    pts = np.concatenate(chunks)
-    pts[-1] = [2.0, 0.37, -0.81]                                # u0 == 1 exactly: the clamped cell
-    return pts
-
-
-def case_gaps(rng):
-    chunks = []
-    for gap in (2, 5):
-        for k in (640, 641, 2, 3, 1016, 1017):
-            for (y, z) in _sites(rng, 40):
-                chunks.append(_block_points(rng, [(k, y, z), (k + gap, y, z)]))
-    return np.concatenate(chunks)
-
-
-def case_morton_quad(rng):
-    chunks = []
-    for k in (600, 602, 0, 1022):                               # even: the four blocks are consecutive Morton keys
-        for (j, z) in _sites(rng, 40):
-            j &= ~1
-            chunks.append(_block_points(rng, [(k, j, z), (k + 1, j, z), (k, j + 1, z), (k + 1, j + 1, z)]))
-    return np.concatenate(chunks)
-
-
-def case_one_block(rng, n):
-    u = (np.array([733.0, 801.0, 640.0])[None, :] + 0.02 + 0.96 * rng.random((n, 3))) / 1024.0
-    return (u * 8.0 - 6.0).astype(np.float32)
-
-
-def case_dead_between(rng):
-    """dead samples (outside the encoder's range) between two x-neighbouring blocks: at x blocks 1022 | 1023, where the
-    clamped key of a dead sample equals block 1023's, and below the box, where the walk is the buffer order"""
-    chunks = []
-    for k in (1022, 100, 101):
-        for (y, z) in _sites(rng, 50):
-            a = _block_points(rng, [(k, y, z)])
-            b = _block_points(rng, [(k + 1, y, z)])
-            nd = int(rng.integers(1, 4))
-            dead = b[:1].repeat(nd, 0).copy()
-            dead[:, 0] = 2.0 + 8.0 * rng.random(nd).astype(np.float32) + 0.01      # u0 > 1; y, z of block k + 1
-            chunks += [a, dead, b]
-    return np.concatenate(chunks)
-
-
-SYNTHETIC = {
-    'x_runs': lambda: case_x_runs(np.random.default_rng(101)),
-    'gaps': lambda: case_gaps(np.random.default_rng(102)),
-    'morton_quad': lambda: case_morton_quad(np.random.default_rng(103)),
-    'one_block': lambda: case_one_block(np.random.default_rng(104), 1500),
-    'one_block_16': lambda: case_one_block(np.random.default_rng(105), 16),
-    'one_block_17': lambda: case_one_block(np.random.default_rng(106), 17),
-    'dead_between': lambda: case_dead_between(np.random.default_rng(107)),
-}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -202,25 +113,6 @@ def _sorted_vs_tracker(m, xyzs, counter, seed):
     print('MLP gradients: rel-L2 %.3g' % r)
     assert r < 2e-5
     return perm
-
-
-def np_trilinear_scatter(O, u, live, genc, offsets, n_rows):
-    """fp64 scatter of genc [M, 16, C] (d loss / d encoder output) into [n_rows, C]: cell and fraction from the fp32
-    product u * res as in nsr_grid_locate (align_corners), weights and sums in fp64; rows from the oracle"""
-    pls = O.per_level_scale_from_cfg()
-    res = O.grid_resolutions(16, O.grid_S(pls), 16)
-    rows = O.grid_corner_rows(u, offsets, pls, 16, 0, True, 0).astype(np.int64)           # [L, M, 8]: corner i has bit d set -> +1 on axis d
-    out = np.zeros((n_rows, genc.shape[2]), np.float64)
-    for l in range(16):
-        pos = u * np.float32(res[l])
-        c = np.minimum(np.floor(pos), np.float32(int(res[l]) - 1))
-        f = (pos - c).astype(np.float64)
-        for i in range(8):
-            w = np.ones(len(u), np.float64)
-            for d in range(3):
-                w *= f[:, d] if (i >> d) & 1 else 1.0 - f[:, d]
-            np.add.at(out, int(offsets[l]) + rows[l, live, i], w[live, None] * genc[live, l].astype(np.float64))
-    return out
 
 
 def _vs_numpy(O, m, pts, dev):
