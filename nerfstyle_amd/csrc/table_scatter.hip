@@ -5,7 +5,7 @@
 // samples in the permutation's spatial order and accumulates the table gradient.  Why two kernels: the MLP backward
 // needs one wave per SIMD (240 weight-gradient accumulators per lane), and the scatter is a chain of dependent LDS
 // round trips and atomics that one wave per SIMD cannot hide (measured fused: MLP 13.8 ms + scatter 32 ms on the bench
-// frame).  Here a wave needs 136 registers and ~9.5 KB of LDS, so three of them share a SIMD.
+// frame).  Here a wave needs 166 registers and ~11 KB of LDS, so three of them share a SIMD.
 //
 // Lattice accumulator.  The order's key is the sample's BLOCK: its encoder input quantised to 10 bits per axis (a 4^3
 // group of finest-level cells for the reference's 16-level grid).  Consecutive samples -- of MANY rays -- share a block,
@@ -143,6 +143,25 @@ struct TableScatterArgs {
 };
 
 constexpr int TS_RING = 8;          // gradient rows in flight per wave
+static_assert(TS_RING % 4 == 0, "a quad of steps (one locate pass) must not straddle two parts of the ring");
+
+// v of lane (lane & ~3) + K of the caller's group of four lanes (DPP quad_perm: no LDS, no scalar round trip)
+template <int K>
+__device__ __forceinline__ int quad_lane(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, K * 0x55, 0xF, 0xF, true);      // every lane has a source: `old` is never taken
+}
+__device__ __forceinline__ int quad_lane_i(int v, int k) {
+    switch (k & 3) {                                                  // k is a constant wherever this is called: the switch folds
+    case 0: return quad_lane<0>(v);
+    case 1: return quad_lane<1>(v);
+    case 2: return quad_lane<2>(v);
+    default: return quad_lane<3>(v);
+    }
+}
+__device__ __forceinline__ float quad_lane_f(float v, int k) {
+    return __builtin_bit_cast(float, quad_lane_i(__builtin_bit_cast(int, v), k));
+}
+
 static size_t ts_wave_bytes(uint32_t lat_slots) { return 256 + (size_t)lat_slots * 16; }
 
 __global__ void __launch_bounds__(TS_THREADS)
@@ -197,6 +216,40 @@ k_table_scatter(TableScatterArgs a) {
 #pragma unroll
     for (int i = 0; i < TS_RING; i++) gq[i] = ts_gin(idx, i);
 
+    // The locate of a (sample, level) pair -- cell, fractions, lattice slot -- is the same for the four lanes of a level, so
+    // it runs once per QUAD of steps, not in every step: before steps 4q .. 4q + 3 lane (l, j = lane & 3) locates sample
+    // 4q + j on its own level, 64 different records in one pass, and in step 4q + k the lanes of a level read theirs from
+    // lane 4l + k (quad_lane_f).  A record: the slot relative to the lane-independent part of the level's lattice, the three
+    // fractions, and one bit of rq_past ("fp32 rounding put the cell past the lattice", bit = the lane that holds the record).
+    // The records are relative to the anchors: a re-anchor inside a quad runs the pass again.
+    float rq_f0 = 0.f, rq_f1 = 0.f, rq_f2 = 0.f;
+    uint32_t rq_slot = 0u;
+    unsigned long long rq_past = 0ull;
+    float us0 = 0.f, us1 = 0.f, us2 = 0.f;                            // this tile's u, 0 for a dead sample (see below)
+    const int rq_lane4 = (lane & 3) * 4;
+    auto locate_quad = [&](int q) {
+        const int from = q * 16 + rq_lane4;                           // byte address of lane 4q + j, which holds sample 4q + j
+        const float su0 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(from, __builtin_bit_cast(int, us0)));
+        const float su1 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(from, __builtin_bit_cast(int, us1)));
+        const float su2 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(from, __builtin_bit_cast(int, us2)));
+        // nsr_grid_locate (align_corners = 1) with the cell kept as a float: p = u * res, c = min(floor(p), res - 1), f = p - c
+        float cf0, cf1, cf2;
+        {
+#pragma clang fp contract(off)
+            const float p0 = su0 * lscale, p1 = su1 * lscale, p2 = su2 * lscale;
+            cf0 = fminf(floorf(p0), lcmax); cf1 = fminf(floorf(p1), lcmax); cf2 = fminf(floorf(p2), lcmax);
+            rq_f0 = p0 - cf0; rq_f1 = p1 - cf1; rq_f2 = p2 - cf2;
+        }
+        // cell relative to the anchor: 0 .. S - 2 by construction for a live sample (it lies in the block the anchor was taken
+        // from; floor(u * res) is monotonic in u), where the median is min(d, S - 2).  The records of dead samples and of
+        // samples in front of a re-anchor are never read; the lower bound only keeps their slot a number.
+        const float d0 = cf0 - bf0, d1 = cf1 - bf1, d2 = cf2 - bf2;
+        const float r0 = __builtin_amdgcn_fmed3f(d0, 0.0f, Sm2), r1 = __builtin_amdgcn_fmed3f(d1, 0.0f, Sm2),
+                    r2 = __builtin_amdgcn_fmed3f(d2, 0.0f, Sm2);
+        rq_slot = (uint32_t)fmaf(fmaf(r2, Sf, r1), Sf, r0);
+        rq_past = __ballot(fmaxf(d0, fmaxf(d1, d2)) > Sm2);
+    };
+
     for (uint32_t tile = w_begin; tile < w_end; tile++) {
         // next tile's inputs: the permutation entry was fetched one tile ahead, so these loads depend on nothing in flight
         float nx0 = x0, nx1 = x1, nx2 = x2;
@@ -210,6 +263,9 @@ k_table_scatter(TableScatterArgs a) {
                     u2 = field_unit(x2, a.bmin[2], a.bsize[2]);
         const bool live = valid && field_in_unit_cube(u0, u1, u2);
         const uint32_t live16 = (uint32_t)(__ballot(live) & 0xFFFFull);      // lanes 0..15 are samples 0..15
+        // what locate_quad reads: a dead sample (outside the cube, NaN, behind the count) is located at u = 0, so that its
+        // record -- which no step reads -- is made of numbers
+        us0 = live ? u0 : 0.0f; us1 = live ? u1 : 0.0f; us2 = live ? u2 : 0.0f;
         // this lane's sample's block: the sort key's quantisation (sample_order.hip), 10 bits per axis
         const uint32_t q0 = (uint32_t)fminf(fmaxf(u0 * kq, 0.0f), kq - 1.0f), q1 = (uint32_t)fminf(fmaxf(u1 * kq, 0.0f), kq - 1.0f),
                        q2 = (uint32_t)fminf(fmaxf(u2 * kq, 0.0f), kq - 1.0f);
@@ -231,6 +287,7 @@ k_table_scatter(TableScatterArgs a) {
             for (int ri = 0; ri < TS_RING; ri++) {
                 const int step = part * TS_RING + ri;
                 const float4 gr = gq[ri];
+                if ((ri & 3) == 0 && ((live16 >> step) & 0xFu)) locate_quad(step >> 2);       // wave-uniform
                 if ((live16 >> step) & 1u) {                                       // wave-uniform
                     uint32_t key = cur_key;
                     if ((chg16 >> step) & 1u) key = (uint32_t)__builtin_amdgcn_readlane((int)bkey, step);       // wave-uniform
@@ -263,44 +320,48 @@ k_table_scatter(TableScatterArgs a) {
                             lat_flush_dispatch(lat, fl, st, xl, lds_lv, gt, lane, td, tc);
                         }
                         if (chg) { st.b0 = n0; st.b1 = n1; st.b2 = n2; bf0 = (float)n0; bf1 = (float)n1; bf2 = (float)n2; }
+                        // the quad's records were taken against the old anchors: again for this and the steps to come (if no
+                        // level moved they come out the same; the steps before this one are done with theirs)
+                        if (__ballot(chg)) locate_quad(step >> 2);
                     }
-                    const float su0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u0), step));
-                    const float su1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u1), step));
-                    const float su2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, u2), step));
-                    // nsr_grid_locate (align_corners = 1) with the cell kept as a float: p = u * res, c = min(floor(p), res - 1), f = p - c
-                    float f0, f1, f2, cf0, cf1, cf2;
-                    {
-#pragma clang fp contract(off)
-                        const float p0 = su0 * lscale, p1 = su1 * lscale, p2 = su2 * lscale;
-                        cf0 = fminf(floorf(p0), lcmax); cf1 = fminf(floorf(p1), lcmax); cf2 = fminf(floorf(p2), lcmax);
-                        f0 = p0 - cf0; f1 = p1 - cf1; f2 = p2 - cf2;
-                    }
-                    // cell relative to the anchor: 0 .. S - 2 by construction (the sample lies in the block the anchor was taken
-                    // from; floor(u * res) is monotonic in u)
-                    const float d0 = cf0 - bf0, d1 = cf1 - bf1, d2 = cf2 - bf2;
-                    const float r0 = fminf(d0, Sm2), r1 = fminf(d1, Sm2), r2 = fminf(d2, Sm2);
+                    // this step's record of the lane's level, from the lane of the quad that located sample `step`
+                    // (step & 3 == ri & 3, a constant of the unrolled loop: TS_RING is a multiple of 4)
+                    const float f0 = quad_lane_f(rq_f0, ri), f1 = quad_lane_f(rq_f1, ri), f2 = quad_lane_f(rq_f2, ri);
+                    const uint32_t rslot = (uint32_t)quad_lane_i((int)rq_slot, ri);
                     // this sample's contribution to the lane's two x corners
                     const float wyz = fmaf(f1, sy, oy) * fmaf(f2, sz, oz);
                     float wB = f0 * wyz, wA = wyz - wB;
-                    if (fmaxf(d0, fmaxf(d1, d2)) > Sm2) {
-                        const uint32_t c0 = (uint32_t)cf0, c1 = (uint32_t)cf1, c2 = (uint32_t)cf2;
-                        // fp32 rounding put the cell one past the lattice (u * res of a sample at the very end of its block can
-                        // round up across a cell boundary that the block's real extent stops short of): this sample's two corners
-                        // go straight to the table, exactly; the (clamped) lattice slots get nothing
-                        const uint32_t rowA = lv.offset + lat_row(lv, c0, c1 + (uint32_t)py, c2 + (uint32_t)pz);
-                        const uint32_t rowB = lv.offset + lat_row(lv, c0 + 1u, c1 + (uint32_t)py, c2 + (uint32_t)pz);
-                        const float ga[4] = {gr.x, gr.y, gr.z, gr.w};
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            if ((i < 2 ? td : tc) && ga[i] != 0.0f) {
-                                atomicAdd(gt + (size_t)rowA * 4 + i, wA * ga[i]);
-                                atomicAdd(gt + (size_t)rowB * 4 + i, wB * ga[i]);
-                            }
+                    if (rq_past & (0x1111111111111111ull << (ri & 3))) {           // wave-uniform: some level's cell is past its lattice
+                        // fp32 rounding put the cell one past the lattice (u * res of a sample at the very end of its block can round
+                        // up across a cell boundary that the block's real extent stops short of): this sample's two corners go
+                        // straight to the table, exactly; the (clamped) lattice slots get nothing.  The absolute cell, as
+                        // locate_quad computed it:
+                        const float su0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, us0), step));
+                        const float su1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, us1), step));
+                        const float su2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, us2), step));
+                        float cf0, cf1, cf2;
+                        {
+#pragma clang fp contract(off)
+                            cf0 = fminf(floorf(su0 * lscale), lcmax); cf1 = fminf(floorf(su1 * lscale), lcmax);
+                            cf2 = fminf(floorf(su2 * lscale), lcmax);
                         }
-                        wA = 0.0f;
-                        wB = 0.0f;
+                        if ((rq_past >> ((lane & ~3) | (ri & 3))) & 1ull) {
+                            const uint32_t c0 = (uint32_t)cf0, c1 = (uint32_t)cf1, c2 = (uint32_t)cf2;
+                            const uint32_t rowA = lv.offset + lat_row(lv, c0, c1 + (uint32_t)py, c2 + (uint32_t)pz);
+                            const uint32_t rowB = lv.offset + lat_row(lv, c0 + 1u, c1 + (uint32_t)py, c2 + (uint32_t)pz);
+                            const float ga[4] = {gr.x, gr.y, gr.z, gr.w};
+#pragma unroll
+                            for (int i = 0; i < 4; i++) {
+                                if ((i < 2 ? td : tc) && ga[i] != 0.0f) {
+                                    atomicAdd(gt + (size_t)rowA * 4 + i, wA * ga[i]);
+                                    atomicAdd(gt + (size_t)rowB * 4 + i, wB * ga[i]);
+                                }
+                            }
+                            wA = 0.0f;
+                            wB = 0.0f;
+                        }
                     }
-                    float4 *const slot = mylat + (uint32_t)fmaf(fmaf(r2, Sf, r1), Sf, r0);
+                    float4 *const slot = mylat + rslot;
                     float4 va = slot[0], vb = slot[1];
                     va.x = fmaf(wA, gr.x, va.x); va.y = fmaf(wA, gr.y, va.y); va.z = fmaf(wA, gr.z, va.z); va.w = fmaf(wA, gr.w, va.w);
                     vb.x = fmaf(wB, gr.x, vb.x); vb.y = fmaf(wB, gr.y, vb.y); vb.z = fmaf(wB, gr.z, vb.z); vb.w = fmaf(wB, gr.w, vb.w);
