@@ -1076,6 +1076,52 @@ int nsr_occ_component_stats(const int32_t *labels, uint32_t C, uint32_t H, uint3
 int nsr_occ_cull(float *density_grid, uint8_t *bitfield, const int32_t *labels, const uint8_t *keep, uint32_t C, uint32_t H,
                  uint32_t *n_culled, nsr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * View reprojection: a rendered frame warped into a neighbouring camera through its depth, and the squared error of the
+ * pixels both cameras see (csrc/reproject.hip, csrc/reproject_core.h; nerfstyle_amd/consistency.py).  The warped error between
+ * views is the number the stylisation stage is judged by: short range between neighbouring frames, long range between frames
+ * several apart.  Additive: the ABI version stays.
+ *
+ * rgb   [F, H*W, 3] f32, pixel-major rows (the layout of rgb_map).
+ * dist  [F, H*W] f32: the distance from the camera origin to the surface along the pixel's unit ray.  "No surface" is any value
+ *       that is not finite or not > 0.
+ * poses [F, 3, 4] f32 camera to world: R = pose[:, :3], o = pose[:, 3].
+ * fx, fy, cx, cy, W, H (both >= 2), camera_flip (0..7): the pinhole of nsr_generate_rays and its flip signs f0, f1, f2 (bits
+ *       2, 1, 0 of camera_flip negate axes 0, 1, 2).
+ * pairs [P, 2] int32: (dst a, src b).  depth_tol: the relative tolerance of the depth test, >= 0.
+ *
+ * For pair (a, b) and dst pixel p = py * W + px, everything in fp64 from the f32 inputs, no operation contracted, sums of
+ * products added left to right as written:
+ *   1. t = dist[a, p]; invalid if it is no surface.
+ *   2. c = (((px + 0.5 - cx) / fx) * f0, ((py + 0.5 - cy) / fy) * f1, f2); v = R_a c (v_r = R[r][0] c0 + R[r][1] c1 + R[r][2] c2);
+ *      n = sqrt(v0 v0 + v1 v1 + v2 v2); X_r = o_a[r] + t * (v_r / n).
+ *   3. dx = X - o_b; q_k = R_b[0][k] dx0 + R_b[1][k] dx1 + R_b[2][k] dx2; z = q2 * f2; invalid unless z > 0.
+ *   4. u = fx * (q0 * f0 / z) + cx - 0.5, w = fy * (q1 * f1 / z) + cy - 0.5 (pixel centres at the integers); invalid unless
+ *      0 <= u <= W - 1 and 0 <= w <= H - 1.  x0 = min(floor(u), W - 2), y0 = min(floor(w), H - 2), ax = u - x0, ay = w - y0.
+ *      The bilinear mean of the taps v00 = [y0, x0], v01 = [y0, x0 + 1], v10 = [y0 + 1, x0], v11 = [y0 + 1, x0 + 1] is
+ *      (v00 (1 - ax) + v01 ax) (1 - ay) + (v10 (1 - ax) + v11 ax) ay.
+ *   5. All four taps of dist[b] must be a surface, whatever their weights; tbar = their bilinear mean,
+ *      r = sqrt(dx0 dx0 + dx1 dx1 + dx2 dx2); invalid (occluded or disoccluded) unless |r - tbar| <= depth_tol * r.
+ *   6. warped[p, k] = the bilinear mean of the four taps of rgb[b, :, k], rounded once to f32, and mask[p] = 1.  An invalid
+ *      pixel gets warped = 0 and mask = 0.
+ *   7. stats[pair] = (sse, n_valid) f64: n_valid the count of valid pixels, sse the sum over them of ((e0 e0 + e1 e1) + e2 e2)
+ *      with e_k = warped_k (before its rounding to f32) - rgb[a, p, k].  Summed in fp64 in a fixed order without atomics: per
+ *      block of 256 consecutive pixels the block sum of csrc/fixed_sum.h into the block's own slot of the workspace, then the
+ *      slots of a pair, thread t of one block taking slots t, t + 256, ... in that order, and the block sum again.  Two calls
+ *      give the same bits.
+ * A pair that names a frame outside [0, F) reads neither frame: stats = (0, 0), mask 0, warped 0.
+ *
+ * warped [P, H*W, 3] f32 and mask [P, H*W] uint8 may each be NULL: the metric alone writes stats [P, 2] only.  The outputs must
+ * not overlap the inputs.  workspace: nsr_reproject_frames_workspace_bytes(P, H, W) bytes, 8-byte aligned; the query answers 0
+ * for a shape the call refuses.  No host read, no allocation: legal inside a stream capture.  P = 0 is a no-op.
+ * NSR_ERR_INVALID_ARG before any launch: W < 2 or H < 2, H*W > 2^30, P * ceil(H*W / 256) >= 2^31, F = 0, camera_flip outside
+ * 0..7, fx or fy zero or NaN, depth_tol negative or NaN, a NULL rgb, dist, poses, pairs, stats or workspace, a misaligned pointer.
+ * ------------------------------------------------------------------------------------------ */
+uint64_t nsr_reproject_frames_workspace_bytes(uint32_t P, uint32_t H, uint32_t W);
+int nsr_reproject_frames(const float *rgb, const float *dist, const float *poses, uint32_t F, uint32_t H, uint32_t W, float fx, float fy,
+                         float cx, float cy, int camera_flip, const int32_t *pairs, uint32_t P, double depth_tol, float *warped,
+                         uint8_t *mask, double *stats, void *workspace, nsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

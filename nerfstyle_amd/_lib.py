@@ -143,6 +143,8 @@ SIGNATURES = {
     'nsr_occ_components': (i32, [vp, u32, u32, vp, vp]),
     'nsr_occ_component_stats': (i32, [vp, u32, u32, vp, vp, vp, vp]),
     'nsr_occ_cull': (i32, [vp, vp, vp, vp, u32, u32, vp, vp]),
+    'nsr_reproject_frames_workspace_bytes': (u64, [u32, u32, u32]),
+    'nsr_reproject_frames': (i32, [vp, vp, vp, u32, u32, u32, f32, f32, f32, f32, i32, vp, u32, f64, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -475,6 +475,10 @@ class Renderer(torch.nn.Module):
             return self.render_test_loop(rays, **kwargs)
         if self.fused_inference:
             return self.render_test_fused(rays, **kwargs)
+        return self._infer_epilogue(*self._render_test_buffered(rays))
+
+    def _render_test_buffered(self, rays: RayBatch):
+        """render_test's buffered path up to its epilogue -> (image [N,C], weights_sum [N], depth [N], nears, fars) as composited"""
         from . import _lib as L
         mt = self._march(rays, step=False)
         N, M, counter, nears = mt['N'], mt['M'], mt['counter'], mt['nears']
@@ -484,7 +488,7 @@ class Renderer(torch.nn.Module):
             # per frame (the reference reads the alive count every iteration); never taken with the default capacity.
             self.last_test_overflow = int(counter[0].item()) >= M
             if self.last_test_overflow:
-                return self.render_test_loop(rays, **kwargs)
+                return self._render_test_loop(rays)
         sigmas, rgbs = self.model.field(mt['xyzs'], sigma_only=False, m_dev=counter, density_scale=self.cfg.density_scale,
                                         dirs=mt['dirs'])
         C = self.raymarch_channels
@@ -494,7 +498,7 @@ class Renderer(torch.nn.Module):
         L.check(L.lib().nsr_composite_rays_infer(L.p(sigmas), L.p(rgbs), L.p(mt['deltas']), L.p(mt['rays_info']), L.p(nears), M, N,
                                                  C, float(self.cfg.t_thresh), L.p(weights_sum), L.p(depth), L.p(image),
                                                  L.stream()), 'composite_rays_infer')
-        return self._infer_epilogue(image, weights_sum, depth, nears, mt['fars'])
+        return image, weights_sum, depth, nears, mt['fars']
 
     @staticmethod
     def _infer_epilogue(image, weights_sum, depth, nears, fars):
@@ -585,6 +589,10 @@ class Renderer(torch.nn.Module):
     def render_test_loop(self, rays: RayBatch, **kwargs):
         """renderer.py:237-293.  Same iteration structure (n_step = max(min(N // n_alive, 8), 1));
         alive-ray compaction is a device scan instead of boolean-mask indexing."""
+        return self._infer_epilogue(*self._render_test_loop(rays))
+
+    def _render_test_loop(self, rays: RayBatch):
+        """render_test_loop up to its epilogue -> what _render_test_buffered returns"""
         nears, fars = raymarching.near_far_from_aabb(rays.origins, rays.dirs, self.aabb, self.cfg.min_near)
         N = len(rays)
         dev = self.device
@@ -612,7 +620,7 @@ class Renderer(torch.nn.Module):
             rays_alive, rays_alive_next = rays_alive_next, rays_alive
             n_alive = int(n_out.item())
             step += n_step
-        return self._infer_epilogue(image, weights_sum, depth, nears, fars)
+        return image, weights_sum, depth, nears, fars
 
     # ---- a training render in two halves (data-parallel overlap, parallel.py) ---------------------------------------
     def occupancy_update_due(self) -> bool:
@@ -699,6 +707,71 @@ class Renderer(torch.nn.Module):
         output['rgb_map'], output['trans_map'], output['classes'] = render_fn(rays, dense=dense, **extra)
         output.update(geometry or {})
         return output
+
+    # ---- metric depth and view consistency (nerfstyle_amd/consistency.py) ---------------------------------------------
+    @torch.no_grad()
+    def render_rgbd(self, pose, min_opacity: float = 0.5) -> Dict[str, torch.Tensor]:
+        """A no-grad inference render of the whole frame that also hands out the metric depth, which render() normalises away.
+        -> 'rgb_map', 'trans_map', 'classes': those of render(pose), bit for bit (the same launches on render_test's buffered path,
+        or on the reference loop with `reference_inference_loop`); 'weights_sum' [N]; 'distance' [N]: the composite's raw depth
+        divided by weights_sum where weights_sum >= min_opacity, else 0, the "no surface" value of reproject_frames; 'nears',
+        'fars' [N].
+        What the raw depth is (csrc/raymarch_infer.hip, k_composite_infer and the loop's composite): sum_i w_i t_i over the ray's
+        shaded samples, where t_i starts at the ray's near and advances by the march's second delta column, t_next - last_t, so
+        t_i is the ray parameter at the FAR end of sample i's step (one step past the position the field was asked at, and for
+        the last sample before `far` possibly a step beyond it).  The rays are unit vectors (ray generation normalises them), so a
+        parameter is a distance from the camera origin, and depth / weights_sum is the weight-averaged distance of the ray's
+        surface: the `dist` of include/nsr.h, "View reprojection".
+        Refuses use_ndc (an NDC depth is not a distance) and fused_inference (the streaming kernel is not what this method
+        launches; switch it off for the call).  No lens argument: the reprojection is a pinhole's."""
+        if self.cfg.use_ndc:
+            raise NotImplementedError('render_rgbd: use_ndc: the depth of an NDC march is not a distance along the ray')
+        if self.fused_inference and not self.reference_inference_loop:
+            raise NotImplementedError('render_rgbd: fused_inference: the metric depth comes from the buffered render_test path; switch '
+                                      'fused_inference off for this call')
+        precrop_frac = self.precrop_frac if self._use_precrop else 1.
+        rays, _ = generate_rays(pose, self.intr, None, precrop=precrop_frac, camera_flip=self.cfg.flip_camera, device=self.device)
+        raw = self._render_test_loop(rays) if self.reference_inference_loop else self._render_test_buffered(rays)
+        _, weights_sum, depth, nears, fars = raw
+        out = {'target': None}
+        out['rgb_map'], out['trans_map'], out['classes'] = self._infer_epilogue(*raw)
+        out['weights_sum'] = weights_sum
+        out['distance'] = torch.where(weights_sum >= min_opacity, depth / weights_sum, torch.zeros_like(depth))
+        out['nears'], out['fars'] = nears, fars
+        return out
+
+    @torch.no_grad()
+    def view_consistency(self, poses, gaps=(1, 7), depth_tol: float = 0.01, min_opacity: float = 0.5, frames=None):
+        """The warped error between views of this field: every pose of `poses` ([F,3,4] or [F,4,4]) is rendered with render_rgbd, the frames
+        and their distance maps stay on the device, and for every gap g each frame i + g is reprojected into frame i
+        (consistency.reproject_frames over sequence_pairs(F, g): one call per gap, metric only, neither warped frames nor masks
+        written) -> {g: [F - g, 2] float64 (rmse, coverage)} on the device (consistency.warp_error), no host read.  gap 1 is the
+        short-range protocol, a larger gap the long-range one; a gap >= F yields an empty tensor.
+        frames = (rgb [F,H*W,3] or [F,H,W,3], dist [F,H*W] or [F,H,W]): score images stylised elsewhere against this field's
+        geometry (dist None: the distance maps are rendered here, the images are the caller's); nothing is rendered when both
+        are given."""
+        from . import consistency
+        poses = torch.as_tensor(poses, dtype=torch.float32, device=self.device)
+        if poses.dim() != 3 or tuple(poses.shape[1:]) not in ((3, 4), (4, 4)):
+            raise ValueError('view_consistency: poses must be [F, 3, 4] or [F, 4, 4]; got {}'.format(tuple(poses.shape)))
+        poses = poses[:, :3].contiguous()                  # the cameras of scene.py are homogeneous 4 x 4
+        F = int(poses.shape[0])
+        rgb, dist = frames if frames is not None else (None, None)
+        if rgb is None or dist is None:
+            if self._use_precrop and self.precrop_frac < 1.:
+                raise NotImplementedError('view_consistency: the centre crop (use_precrop) renders only part of the frame')
+            outs = [self.render_rgbd(poses[i], min_opacity=min_opacity) for i in range(F)]
+            if dist is None:
+                dist = torch.stack([o['distance'] for o in outs])
+            if rgb is None:
+                rgb = torch.stack([o['rgb_map'] for o in outs])
+        result = {}
+        for gap in gaps:
+            pairs = consistency.sequence_pairs(F, gap)
+            _, _, stats = consistency.reproject_frames(rgb, dist, poses, self.intr, pairs, camera_flip=self.cfg.flip_camera,
+                                                       depth_tol=depth_tol, want_warped=False, want_mask=False)
+            result[int(gap)] = consistency.warp_error(stats, self.intr.h, self.intr.w)
+        return result
 
     def _refuse_lens(self, lens):
         if lens is not None and self.cfg.use_ndc:
