@@ -7,8 +7,12 @@
 //   a = Sigma^-1 u / k,  beta = s0/k - mu^T a
 //   L        = sum_w sum_c  s2 - s0^2/k - u^T a
 //   dL/dv_pc = 2 sum_{w contains p} (v_pc - beta_wc - I_p^T a_wc) = 2 (n_p v_pc - sum beta - I_p^T sum a)
-// All arithmetic in fp64.  Sigma is factorised as L D L^T (backward stable): an adjugate over the determinant loses the
-// small eigenvalues of a window that straddles a sharp edge (Sigma ~ rank 1 + eps/k), where the reference's LU does not.
+// All arithmetic in fp64.  The moments are taken of I minus the window's centre pixel: Sigma and u do not change with a shift
+// of I, and the subtraction sum I I^T / k - mu mu^T then cancels numbers of the size of the window's spread, not of the
+// image's level; on a step edge between two flat regions the raw moments lose the small eigenvalues' last digits (a
+// gradient 3e-10 of its maximum off where two centred fp64 evaluations agree to 5e-11).  Sigma is factorised as L D L^T
+// (backward stable): an adjugate over the determinant loses the small eigenvalues of a window that straddles a sharp edge
+// (Sigma ~ rank 1 + eps/k), where the reference's LU does not.
 //
 // One workgroup per 32x8 pixel tile.  It stages target and v of the tile plus a 2r halo in LDS (as f32: the inputs are
 // f32, converted to fp64 when read), solves every window whose centre lies within r of the tile (coefficients a, beta
@@ -69,7 +73,9 @@ k_matting(MattingArgs a) {
 #pragma unroll
         for (int q = 0; q < 12; q++) cf[q] = 0.0;
         if (cx >= R && cx < W - R && cy >= R && cy < H - R) {
-            // raw moments over the window (the reference's win_mu / win_var, loss.py:252-254)
+            // moments over the window (the reference's win_mu / win_var, loss.py:252-254) of I - I(centre)
+            const int pc = (wy + R) * PW + wx + R;
+            const double c0 = s_img[0][pc], c1 = s_img[1][pc], c2 = s_img[2][pc];
             double sI[3] = {0.0, 0.0, 0.0}, sII[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             double s0[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0}, sVI[3][3] = {};
 #pragma unroll 1
@@ -77,7 +83,7 @@ k_matting(MattingArgs a) {
 #pragma unroll
                 for (int dx = 0; dx < D; dx++) {
                     const int p = (wy + dy) * PW + wx + dx;
-                    const double i0 = s_img[0][p], i1 = s_img[1][p], i2 = s_img[2][p];
+                    const double i0 = (double)s_img[0][p] - c0, i1 = (double)s_img[1][p] - c1, i2 = (double)s_img[2][p] - c2;
                     sI[0] += i0; sI[1] += i1; sI[2] += i2;
                     sII[0] += i0 * i0; sII[1] += i0 * i1; sII[2] += i0 * i2;
                     sII[3] += i1 * i1; sII[4] += i1 * i2; sII[5] += i2 * i2;
@@ -102,13 +108,13 @@ k_matting(MattingArgs a) {
             const double d2 = S22 - l20 * S02 - l21 * e21, r2 = 1.0 / d2;
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                // u = sum v (I - mu) = sum v I - s0 mu
+                // u = sum v (I - mu) = sum v I - s0 mu, the same for the shifted I
                 const double u0 = sVI[c][0] - s0[c] * m0, u1 = sVI[c][1] - s0[c] * m1, u2 = sVI[c][2] - s0[c] * m2;
                 const double z0 = u0, z1 = u1 - l10 * z0, z2 = u2 - l20 * z0 - l21 * z1;
                 const double x2 = z2 * r2, x1 = z1 * r1 - l21 * x2, x0 = z0 * r0 - l10 * x1 - l20 * x2;
                 const double a0 = x0 * invk, a1 = x1 * invk, a2 = x2 * invk;
                 cf[4 * c + 0] = a0; cf[4 * c + 1] = a1; cf[4 * c + 2] = a2;
-                cf[4 * c + 3] = s0[c] * invk - (m0 * a0 + m1 * a1 + m2 * a2);
+                cf[4 * c + 3] = s0[c] * invk - ((m0 + c0) * a0 + (m1 + c1) * a1 + (m2 + c2) * a2);     // mu = m + I(centre)
                 if (wx >= R && wx < R + MT_TX && wy >= R && wy < R + MT_TY)     // this tile holds the centre
                     val += s2[c] - s0[c] * s0[c] * invk - (u0 * a0 + u1 * a1 + u2 * a2);
             }

@@ -1,6 +1,7 @@
 """Matting-Laplacian photorealism loss (the reference's MattingLaplacian, loss.py:217-278), host side: the test's own fp64
 restatements against the reference's recorded outputs (tests/golden/make_matting_goldens.py), properties of the loss,
-why the kernel computes in fp64, and the C ABI's host-only paths."""
+why the kernel computes in fp64, the C ABI's host-only paths, and the reference side of the edge tests
+(matting_cases.py): the noise floor of the two restatements and the closed-form window count."""
 import ctypes
 import os
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import matting_cases as C
 from matting_ref import fixture_cases, matting_dense, matting_fast, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -132,3 +134,65 @@ def test_style_criterion_photo_lambda_defaults_off():
     assert crit.photo_loss is None and crit.last_photo is None
     crit = StyleCriterion(None, None, photo_lambda=1e-4)
     assert crit.photo_loss.win_rad == 1 and crit.photo_loss.eps == 1e-7
+
+
+# ---- the reference side of tests/test_gpu_matting_edges.py ------------------------------------------------------------
+
+def test_edge_shapes_are_the_issue_list():
+    for r in (1, 2):
+        D = 2 * r + 1
+        shapes = C.edge_shapes(r)
+        assert len(shapes) == len(set(shapes)) and all(H >= D and W >= D for H, W in shapes)
+        assert {(D, D), (D, D + 1), (D + 1, D), (D, 97), (61, D), (8 + r + 1, 32 + r + 1), (17, 65),
+                (8 + 2 * r + 1, 64 + 2 * r + 1)} <= set(shapes)
+        assert {W for H, W in shapes if H == 11} >= {31, 32, 33, 32 + r, 32 + r + 1, 32 + 2 * r, 32 + 2 * r + 1, 63, 64, 65}
+        assert {H for H, W in shapes if W == 37} >= {7, 8, 9, 8 + r, 8 + r + 1, 8 + 2 * r, 8 + 2 * r + 1, 16, 17}
+        assert max(H * W for H, W in shapes) <= C.DENSE_LIMIT                  # matting_dense is the reference of every one
+    t, v = C.inputs(1, 11, 33)
+    t2, v2 = C.inputs(1, 11, 33)
+    assert t.dtype == v.dtype == np.float32 and np.array_equal(t, t2) and np.array_equal(v, v2)
+    assert not np.array_equal(t, C.inputs(2, 11, 33)[0]) and 0.0 <= t.min() and t.max() < 1.0
+
+
+def test_edge_shapes_dense_and_vectorised_restatements_agree():
+    """The noise floor under the per-element bars of the GPU edge tests: how far two fp64 evaluations of the same loss
+    differ.  The additive term of the bar, 1e-9 max|grad|, stands only while this floor is at most a quarter of it."""
+    worst_g = worst_v = 0.0
+    for r in (1, 2):
+        for H, W in C.edge_shapes(r):
+            t, v = C.inputs(r, H, W)
+            fg, fv = C.floor(t, v, r)
+            print('r={} {}x{}: dense vs fast, gradient {:.3e} max|grad| per element, value {:.3e} relative'.format(r, H, W, fg, fv))
+            worst_g, worst_v = max(worst_g, fg), max(worst_v, fv)
+    print('edge shapes: largest gradient floor {:.3e}, largest value floor {:.3e}'.format(worst_g, worst_v))
+    assert worst_g <= 0.25 * 1e-9 and worst_v <= 0.25 * VALUE_TOL
+    for r in (1, 2):
+        t, v = C.conditioned_inputs(r)
+        fg, fv = C.floor(t, v, r)
+        print('seam step r={}: dense vs fast, gradient {:.3e} max|grad| per element (recorded {:.3e}), value {:.3e} relative'.format(
+            r, fg, C.COND_FLOOR[r], fv))
+        # the GPU bar adds 4 x the recorded floor: the record must cover what is measured, and the case must stay testable
+        assert fg <= 2.0 * C.COND_FLOOR[r] and 4.0 * C.COND_FLOOR[r] <= 1e-5 and fv <= 0.25 * VALUE_TOL
+        # the windows on the seam are what the case is for: Sigma's smallest eigenvalue is orders below its largest
+        k = (2 * r + 1) ** 2
+        I = t[:, 8 - r:8 + r + 1, C.TX - r:C.TX + r + 1].reshape(3, k).astype(np.float64)
+        ev = np.linalg.eigvalsh(np.cov(I, bias=True) + C.EPS / k * np.eye(3))
+        assert ev[0] < 1e-4 * ev[-1], ev
+
+
+def test_closed_form_window_count_equals_a_brute_force_count():
+    for r in (1, 2):
+        for H, W in C.edge_shapes(r):
+            n = C.window_count(H, W, r)
+            assert np.array_equal(n, C.window_count_brute(H, W, r)), (r, H, W)
+            assert n.min() >= 1 and n.max() <= (2 * r + 1) ** 2 and n.sum() == (2 * r + 1) ** 2 * (H - 2 * r) * (W - 2 * r)
+
+
+def test_count_form_of_the_gradient_is_the_loss_with_a_drowned_sigma():
+    """eps = 1e30 leaves 2 (n_p v_p - sum of window means): what the GPU test of the window count compares against"""
+    for r in (1, 2):
+        for H, W in ((2 * r + 1, 2 * r + 2), (11, 32 + r + 1), (17, 65)):
+            t, v = C.inputs(r, H, W)
+            _, g = matting_fast(t, v, r, 1e30)
+            ref = C.count_gradient(v, r)
+            assert np.abs(g - ref).max() <= 1e-12 * np.abs(ref).max(), (r, H, W)
