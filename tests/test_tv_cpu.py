@@ -1,6 +1,7 @@
 """Total-variation regulariser without a GPU: the restatement (tv_ref.py) against torch autograd of its own loss, its row
-function against the oracle's, the estimator's mean, the neighbour counts at the lattice's border, and what the C entry point and
-the host layer refuse before anything touches a device."""
+function against the oracle's, the estimator's mean, the neighbour counts at the lattice's border, what the C entry point and
+the host layer refuse before anything touches a device, and the facts about the resolution-80 level that the GPU edge tests
+(test_gpu_tv_edges.py) rely on."""
 import ctypes
 import os
 import re
@@ -22,6 +23,32 @@ TINY = dict(num_levels=3, per_level_scale=2.0, base_resolution=4, log2_hashmap_s
 def tiny(gridtype=0):
     off = T.grid_offsets(**TINY)
     return off, T.grid_S(TINY['per_level_scale']), TINY['base_resolution'], T.levels(off, T.grid_S(2.0), 4, gridtype)
+
+
+# one 'tiled' level of resolution 80 for the GPU edge tests: side 81, V = 531 441 vertices in 531 448 rows, a row per vertex.  The
+# launch is capped at 2048 blocks of 256 threads = 524 288 draws a trip, so the sweep and 524 289 draws wrap the grid-stride loop;
+# 65 537 draws are 257 blocks, the first count at which the value's final pass strides over its partials
+BIG = dict(num_levels=1, per_level_scale=2.0, base_resolution=80, log2_hashmap_size=20)
+BIG_V, BIG_TRIP, BIG_DRAWS, BIG_LAM, BIG_SEED = 81 ** 3, 2048 * 256, (65537, 524289), (0.3, 0.7), 0x1234567855aa
+
+
+def big():
+    off = T.grid_offsets(**BIG)
+    S = T.grid_S(BIG['per_level_scale'])
+    return off, S, BIG['base_resolution'], T.levels(off, S, BIG['base_resolution'], 1)[0]
+
+
+def big_table():
+    """rows of two lanes, random in +-1; the same in the CPU and the GPU module"""
+    return np.random.default_rng(31).uniform(-1, 1, (int(T.grid_offsets(**BIG)[-1]), 2)).astype(np.float32)
+
+
+def big_refs(table):
+    """the references of the resolution-80 level, each built once: {n_samples: (Grad, value [1, 2], n [1])}"""
+    off, S, H, _ = big()
+    return {n: (T.gradient(table, off, S, H, BIG_LAM, n, gridtype=1, seed=BIG_SEED),) + T.value(table, off, S, H, BIG_LAM, n, gridtype=1,
+                                                                                                seed=BIG_SEED)
+            for n in (BIG_V,) + BIG_DRAWS}
 
 
 def test_tiny_grid_is_what_the_tests_assume():
@@ -71,6 +98,88 @@ def test_sweep_gradient_is_autograd_of_the_loss(gridtype):
     assert np.abs(got - auto).max() <= 2.0 ** -23 * ref.A.max() + 1e-15
     assert np.abs(auto).max() > 1e-4 and not got[:, 2].any()
     assert ref.k.sum() == 125 + 729 + 4913
+
+
+@pytest.mark.parametrize('rf', [1, 8])
+@pytest.mark.parametrize('gridtype', [0, 1])
+def test_sweep_gradient_is_autograd_of_the_loss_at_rows_of_1_and_8(gridtype, rf):
+    """the restatement at the widths the GPU edge tests add: every lane has a weight of its own and uses its own column"""
+    off, S, H, lvs = tiny(gridtype)
+    table = np.random.default_rng(5).uniform(-1, 1, (int(off[-1]), rf)).astype(np.float32)
+    lam = (0.3, 0.7, 0.45, 1.1, 0.9, 0.0, 0.6, 1.3)[:rf]
+    t = torch.tensor(table.astype(np.float64), requires_grad=True)
+    T.tv_loss_torch(t, off, S, H, [np.float32(v) for v in lam], gridtype).backward()
+    auto = t.grad.numpy()
+    ref = T.gradient(table, off, S, H, lam, 8192, gridtype)
+    got = ref.dense(int(off[-1]))
+    assert got.shape == auto.shape == (int(off[-1]), rf)
+    assert np.abs(got - auto).max() <= 2.0 ** -23 * ref.A.max() + 1e-15                # c is rounded to float once
+    assert (np.abs(auto).max(0)[[k for k in range(rf) if lam[k]]] > 1e-4).all() and ref.k.sum() == 125 + 729 + 4913
+    if rf == 8:
+        assert not got[:, 5].any()
+        # no two lanes agree: a lane computed from another lane's column or weight is off by far more than any bound
+        assert all(np.abs(got[:, j] - got[:, k]).max() > 1e-3 for j in range(8) for k in range(j))
+    # the value is the loss: sum_k lambda_k value[:, k] over the levels
+    val, n = T.value(table, off, S, H, lam, 8192, gridtype)
+    loss = float(T.tv_loss_torch(t.detach(), off, S, H, [np.float32(v) for v in lam], gridtype))
+    assert list(n) == [125, 729, 4913] and abs(float((val * [float(np.float32(v)) for v in lam]).sum()) - loss) <= 1e-12 * loss
+
+
+@pytest.fixture(scope='module')
+def big_level():
+    import time
+    table = big_table()
+    t0 = time.perf_counter()
+    refs = big_refs(table)
+    return table, refs, time.perf_counter() - t0
+
+
+def test_big_level_is_what_the_gpu_tests_assume(big_level):
+    table, refs, seconds = big_level
+    print('resolution-80 level: the sweep and the {} / {}-draw references took {:.2f} s'.format(BIG_DRAWS[0], BIG_DRAWS[1], seconds))
+    off, S, H, lv = big()
+    # dense: a row per vertex, and more vertices than one trip of the capped grid covers
+    assert not lv['use_hash'] and lv['res'] == 80 and lv['mul'] == [1, 81, 6561]
+    assert T.vertex_count(lv) == BIG_V == 531441 > BIG_TRIP == 524288 and lv['size'] >= BIG_V
+    assert table.nbytes < 5 << 20
+    xyz, swept = T.draws(lv, 0, BIG_V)
+    assert swept and np.array_equal(T.grid_row(lv, *xyz.T), np.arange(BIG_V))
+    ref, val, n = refs[BIG_V]
+    assert len(ref.rows) == BIG_V and (ref.k == 1).all() and n[0] == BIG_V
+    assert -(-BIG_V // 256) > 2048                                   # 2048 partial blocks: eight for every thread of the final pass
+    # the two sampled counts draw (below V): 257 blocks, and one draw more than a trip
+    for n_samples, blocks in zip(BIG_DRAWS, (257, 2049)):
+        xyz, swept = T.draws(lv, 0, n_samples, seed=BIG_SEED)
+        assert not swept and len(xyz) == n_samples < BIG_V and -(-n_samples // 256) == blocks
+        assert refs[n_samples][0].k.sum() == n_samples and refs[n_samples][2][0] == n_samples
+
+
+def test_big_level_checks_see_a_lost_wrap(big_level):
+    """what the GPU tests' bars can see: the one draw of the second trip (524 288), every vertex past the first trip of the
+    sweep, and the partial sums past the first 256 blocks are each worth far more than the bar they are measured against"""
+    table, refs, _ = big_level
+    off, S, H, lv = big()
+    # the last of 524 289 draws, which only the second trip reaches
+    n = BIG_DRAWS[1]
+    ref = refs[n][0]
+    xyz = T.draws(lv, 0, n, seed=BIG_SEED)[0][BIG_TRIP:]
+    assert len(xyz) == 1
+    g, _, _, _, row = T.level_terms(table, lv, xyz)
+    at = np.searchsorted(ref.rows, row[0])
+    lost = np.abs(g[0] * [T.c_factor(v, n) for v in BIG_LAM])
+    assert ref.rows[at] == row[0] and (lost > 100 * ref.bound()[at]).any()
+    # the sweep's vertices past the first trip: lost (or added twice), nearly all of them miss the bound
+    ref = refs[BIG_V][0]
+    tail = ref.rows >= BIG_TRIP
+    assert tail.sum() == BIG_V - BIG_TRIP and (np.abs(ref.grad[tail]) > 100 * ref.bound()[tail]).any(1).mean() > 0.99
+    # the value of 65 537 draws without block 256 (its last draw), and of the sweep from the first 256 of 2048 blocks only
+    n = BIG_DRAWS[0]
+    _, val, cnt = refs[n]
+    fwd = T.level_terms(table, lv, T.draws(lv, 0, n, seed=BIG_SEED)[0][65536:])[3]
+    assert len(fwd) == 1 and (fwd[0] / n > 100 * n * 6 * 2.0 ** -52 * val[0]).any()
+    _, val, cnt = refs[BIG_V]
+    head = T.level_terms(table, lv, T.all_vertices(lv)[:65536])[3].sum(0) / BIG_V
+    assert (val[0] - head > 0.8 * val[0]).all()
 
 
 def test_sampled_estimator_is_unbiased():
