@@ -275,6 +275,46 @@ uint64_t nsr_color_moments_workspace_bytes(uint64_t n);
 int nsr_color_moments(const float *rows, uint64_t n, uint32_t stride, double *moments, void *workspace, nsr_stream_t stream);
 int nsr_color_apply(const float *src, float *dst, uint64_t n, uint32_t stride, const float *tf, int clamp, nsr_stream_t stream);
 
+/* Region-wise colour transfer: the same two passes with one set of moments and one transform per region (a scene class on the
+ * content side, a style cluster on the style side; nerfstyle_amd/color_match.py solves one 3x3 pair per matched region on the
+ * host).  rows / src / dst and their alignment as above.  K regions, 1 <= K <= NSR_COLOR_MAX_REGIONS, and slot K for every
+ * row that belongs to none of them.
+ *
+ * region(i):  labels != NULL (i32 [n], 4-byte aligned): labels[i] when 0 <= labels[i] < K, else K.
+ *             labels == NULL (stride 4 only): with w the row's fourth float, k when w == (float)k for an integer 0 <= k < K
+ *             (-0.0 is 0), else K: negative, >= K, fractional, NaN and inf all select slot K.
+ * The fourth float of a stride-4 row is a label or ignored, never a colour; nsr_color_region_apply carries it bit for bit.
+ *
+ * nsr_color_region_moments: moments [K+1][10] (device fp64, 8-byte aligned); moments[k] = count, sum r, sum g, sum b, sum rr,
+ * sum rg, sum rb, sum gg, sum gb, sum bb over the rows of region k, values converted to fp64 first, every sum fp64, the count
+ * exact.  A region without rows is ten +0.0.  No floating-point atomics anywhere.  Order of summation, a function of
+ * (n, stride, K, region(.)) only -- not of the alignment of rows or labels, which decides the loads alone:
+ *   unit, grid: those of nsr_color_moments (U units, B blocks of 256 threads, T = 256 B), so a wave of 64 lanes holds 64
+ *            consecutive units per trip; wave w of the grid takes units 64 w + lane + j T, j = 0, 1, ... in that order.
+ *   slot:    stride 4: the lane's row.  stride 3: rows 4u, 4u+1, 4u+2, 4u+3 of the lane's unit, one slot after the other.
+ *   region:  per slot, while lanes remain: k = region of the lowest remaining lane; the lanes of region k contribute their nine
+ *            values, all others +0.0, to the butterfly over the 64 lanes (lane ^ 32, 16, 8, 4, 2, 1); the nine sums and the
+ *            number of those lanes (as a double) are added to entry k of the wave's own table; those lanes are done.
+ *   block:   entry by entry its four waves' tables in ascending order, starting from +0 -> partial[b][K+1][10] in the workspace.
+ *   final:   one block of 256 threads per region; thread t adds partial[t][k], partial[t + 256][k], ... in that order, then
+ *            butterfly and the four wave sums in ascending order from +0.
+ * workspace: nsr_color_region_moments_workspace_bytes(n, K) bytes (enough for either stride; 0 for K outside 1..64), 8-byte
+ * aligned; nothing of it is read that this call did not write.
+ *
+ * nsr_color_region_apply: tfs [K+1][4][4] f32 row-major in DEVICE memory (read by the kernel; the last row of each is not
+ * read); row i is mapped by tfs[region(i)] with exactly the fma chain and clamp of nsr_color_apply: with all K+1 transforms
+ * equal the output is that of nsr_color_apply bit for bit.  dst == src is allowed, src and dst that overlap otherwise are refused.
+ *
+ * Both: n == 0, stride outside {3, 4}, K == 0 or K > NSR_COLOR_MAX_REGIONS, labels == NULL with stride 3, a NULL or misaligned
+ * pointer, such an overlap -> NSR_ERR_INVALID_ARG, nothing launched.  Neither call reads the host, allocates or synchronises;
+ * both are capture-safe. */
+#define NSR_COLOR_MAX_REGIONS 64
+uint64_t nsr_color_region_moments_workspace_bytes(uint64_t n, uint32_t K);
+int nsr_color_region_moments(const float *rows, uint64_t n, uint32_t stride, const int32_t *labels, uint32_t K, double *moments,
+                             void *workspace, nsr_stream_t stream);
+int nsr_color_region_apply(const float *src, float *dst, uint64_t n, uint32_t stride, const int32_t *labels, uint32_t K,
+                           const float *tfs, int clamp, nsr_stream_t stream);
+
 /* replaces march_rays (raymarching.h:17, raymarching.cu:1004-1130), inference.  noises [n_alive] f32 or NULL (= zeros).
  * C, H as for nsr_march_rays_train: H a power of two in 8..512, C <= 8, else NSR_ERR_INVALID_ARG. */
 int nsr_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t *rays_alive, const float *rays_t,

@@ -66,6 +66,9 @@ SIGNATURES = {
     'nsr_color_moments_workspace_bytes': (u64, [u64]),
     'nsr_color_moments': (i32, [vp, u64, u32, vp, vp, vp]),
     'nsr_color_apply': (i32, [vp, vp, u64, u32, vp, i32, vp]),
+    'nsr_color_region_moments_workspace_bytes': (u64, [u64, u32]),
+    'nsr_color_region_moments': (i32, [vp, u64, u32, vp, u32, vp, vp, vp]),
+    'nsr_color_region_apply': (i32, [vp, vp, u64, u32, vp, u32, vp, i32, vp]),
     'nsr_march_rays': (i32, [u32, u32, vp, vp, vp, vp, vp, f32, f32, u32, i32, u32, u32, vp, vp, vp, vp, vp, vp, vp,
                              vp]),
     'nsr_composite_rays': (i32, [u32, u32, f32, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp]),

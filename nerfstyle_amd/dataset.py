@@ -49,6 +49,7 @@ class ResidentDataset:
         self.bbox = BBox.from_radius(bound)
         self._rgb_rows = self._cls_rows = None
         self.color_tf = None            # [4,4] f32 on the device once match_colors() has run
+        self.region_tf = None           # [num_classes+1,4,4] f32 on the device once match_colors_by_region() has run
 
     def __len__(self):
         return self.poses.shape[0]
@@ -89,6 +90,50 @@ class ResidentDataset:
         if self._rgb_rows is not None and self._rgb_rows.data_ptr() != self.targets.data_ptr():       # C == 3: one storage
             self._rgb_rows.copy_(self.targets[:, :, :3].reshape(-1, 3))
         return self.color_tf
+
+    def match_colors_by_region(self, style_image: torch.Tensor, style_clusters: torch.Tensor, matching, min_rows: int = 256,
+                               fallback: str = 'global') -> torch.Tensor:
+        """match_colors per scene class: the pixels of class i get the mean and covariance of cluster matching[i] of the style
+        image, not the image's average palette.  style_image [3,H,W] f32 in [0,1]; style_clusters [H,W] integer, the cluster of
+        each style pixel (-1 = unlabelled); matching [num_classes] is the caller's (SemanticStyleLoss.matching, or a fixed list;
+        -1 = unmatched), it is not computed here.
+
+        The class ids are read from the targets where they lie (the fourth float of every row, no label copy); the style side
+        passes its cluster map as explicit labels.  Classes that are unmatched or hold fewer than `min_rows` pixels on either
+        side, and pixels of no class, get the fallback ('global': all pixels against the whole style image, what match_colors
+        computes; 'identity').  The maps are applied to `targets` IN PLACE and clamped to [0, 1]; the segment channel keeps its
+        bits; a `target_rgb_rows` handed out before is refreshed as match_colors does.
+        -> region_tf [num_classes+1, 4, 4] f32 on the device, kept as `self.region_tf` (apply it to rendered rows with
+        color_match.apply_region_transforms and labels = preds.to(torch.int32)); `self.color_tf` is set to the fallback slot.
+        One host read of 10 (num_classes + clusters + 2) doubles: set-up, not a training step."""
+        from . import color_match as CM
+        if self.targets.shape[2] < 4:
+            raise ValueError('match_colors_by_region: the dataset was built without segment maps')
+        if style_image.dim() != 3 or style_image.shape[0] != 3:
+            raise ValueError('match_colors_by_region: style_image must be [3,H,W]; got {}'.format(tuple(style_image.shape)))
+        if tuple(style_clusters.shape) != tuple(style_image.shape[1:]) or style_clusters.is_floating_point():
+            raise ValueError('match_colors_by_region: style_clusters must be integer [H,W] of the style image {}; got {} {}'.format(
+                tuple(style_image.shape[1:]), style_clusters.dtype, tuple(style_clusters.shape)))
+        if not 1 <= self.num_classes <= CM.MAX_REGIONS:
+            raise ValueError('match_colors_by_region: num_classes must be in 1..{}; got {}'.format(CM.MAX_REGIONS, self.num_classes))
+        matching = [int(m) for m in (matching.tolist() if isinstance(matching, torch.Tensor) else matching)]
+        if len(matching) != self.num_classes:
+            raise ValueError('match_colors_by_region: matching has {} entries for {} classes'.format(len(matching), self.num_classes))
+        dev = self.targets.device
+        ks = max(int(style_clusters.max()) + 1, max(matching) + 1, 1)
+        if ks > CM.MAX_REGIONS:
+            raise ValueError('match_colors_by_region: {} style clusters; at most {}'.format(ks, CM.MAX_REGIONS))
+        CM._rows(self.targets, 'match_colors_by_region')                  # a CPU dataset is refused before anything is moved
+        style = style_image.detach().to(dev, torch.float32).permute(1, 2, 0).contiguous()
+        clusters = style_clusters.detach().to(dev, torch.int32).contiguous().reshape(-1)
+        content_m = CM.region_moments(self.targets, self.num_classes)
+        style_m = CM.region_moments(style, ks, clusters)
+        self.region_tf = CM.solve_region_transforms(content_m, style_m, matching, min_rows=min_rows, fallback=fallback)
+        self.color_tf = self.region_tf[self.num_classes]
+        CM.apply_region_transforms(self.targets, self.region_tf, clamp=True, out=self.targets)
+        if self._rgb_rows is not None:
+            self._rgb_rows.copy_(self.targets[:, :, :3].reshape(-1, 3))
+        return self.region_tf
 
     @property
     def target_cls_rows(self):
