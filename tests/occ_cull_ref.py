@@ -6,6 +6,8 @@ labels_propagation(bits, C, H)    the same definition written apart from it: on 
                                   occupied face neighbours (array shifts), iterated to a fixed point (a pointer jump
                                   label = label[label] a round only shortens the way)
 component_stats(labels, C, H), keep_rule(stats, C, H, bound, ...), cull(grid_words, bits, labels, keep, C, H)
+box_case(C, H, boxes)             bitfield and labels of a grid of separate boxes, by construction: for grids too large for the two
+                                  above (boxes_for(H), box_reference(H): the three-cascade layout of tests/test_gpu_occ_cull_edges.py)
 plus the bitfields the tests run (cases())."""
 import functools
 
@@ -130,11 +132,18 @@ def labels_propagation(bits, C, H):
     return out.astype(np.int32)
 
 
+def own_labels(labels, C, H):
+    """bool [cells]: the label is a cell of this grid.  -1 is the unoccupied cell; any other label outside 0 .. cells - 1 is not
+    this grid's: the statistics count such a cell as unoccupied, and the cull leaves it as it is"""
+    labels = np.asarray(labels, np.int64)
+    return (labels >= 0) & (labels < C * H ** 3)
+
+
 def component_stats(labels, C, H):
     """-> dict(n_cells uint32 [cells], lo, hi int32 [cells,3]): 0, H, -1 at every cell that is no root"""
     labels = np.asarray(labels, np.int64)
     cells = C * H ** 3
-    occ = np.flatnonzero(labels >= 0)
+    occ = np.flatnonzero(own_labels(labels, C, H))
     n_cells = np.bincount(labels[occ], minlength=cells).astype(np.uint32)
     xyz = cell_coords(H)[occ % H ** 3]
     lo = np.full((cells, 3), H, np.int32)
@@ -177,7 +186,8 @@ def cull(grid_words, bits, labels, keep, C, H):
     """-> (grid words uint32 | None, bitfield, n_culled uint32 [C]); grid_words None: the bits only"""
     labels = np.asarray(labels, np.int64)
     occ = occupied(bits, C, H)
-    gone = occ & (np.asarray(keep)[np.where(occ, labels, 0)] == 0)
+    mine = occ & own_labels(labels, C, H)                                       # a label that is not this grid's decides nothing
+    gone = mine & (np.asarray(keep)[np.where(mine, labels, 0)] == 0)
     out = None
     if grid_words is not None:
         out = np.array(grid_words, np.uint32).reshape(-1)
@@ -226,9 +236,93 @@ def snake(H):
     return from_volume(vol)
 
 
+def checkerboard(H):
+    """one cascade: the cells with (x + y + z) even.  No two share a face: every occupied cell is its own root"""
+    ix, iy, iz = np.meshgrid(np.arange(H), np.arange(H), np.arange(H), indexing='ij')
+    return from_volume((((ix + iy + iz) & 1) == 0)[None])
+
+
+# ---- grids too large for labels_propagation: boxes, labelled by construction ----------------------------------------------------
+def box_case(C, H, boxes):
+    """boxes: (c, (x0, y0, z0), (x1, y1, z1)), the cells x0 <= ix < x1, ... of cascade c; no two boxes of a cascade overlap or
+    share a face (asserted), so every box is one component.  -> (bitfield, labels int32 [cells]) by construction: rm_morton3d
+    grows with every coordinate, so the smallest cell id of a box is that of its corner (x0, y0, z0), and every cell of the box
+    gets it.  The statistics are component_stats(labels) as for every other case.
+
+    Time on one CPU core for boxes_for(128) (C = 3, 6 291 456 cells, 2 208 155 of them occupied, 4513 boxes): box_case 0.9 s,
+    component_stats 1.2 s, keep_rule and cull 0.1 s a rule: well under the ten seconds at which the np.minimum.at of the
+    statistics would have to give way to box arithmetic."""
+    H3 = H ** 3
+    owner = np.zeros((C, H, H, H), np.int32)                                    # 1 + the index of the box that holds the cell
+    lab = np.full((C, H, H, H), -1, np.int32)
+    filled = 0
+    for i, (c, lo, hi) in enumerate(boxes):
+        assert 0 <= c < C and all(0 <= a < b <= H for a, b in zip(lo, hi)), (c, lo, hi)
+        at = (c, slice(lo[0], hi[0]), slice(lo[1], hi[1]), slice(lo[2], hi[2]))
+        owner[at] = i + 1
+        lab[at] = c * H3 + int(morton(*lo))
+        filled += (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
+    assert int((owner != 0).sum()) == filled                                    # no overlap
+    for axis in (1, 2, 3):                                                      # no face between two boxes
+        a = [slice(None)] * 4
+        b = [slice(None)] * 4
+        a[axis], b[axis] = slice(0, H - 1), slice(1, H)
+        p, q = owner[tuple(a)], owner[tuple(b)]
+        assert not ((p != 0) & (q != 0) & (p != q)).any(), axis
+    labels = np.empty((C, H3), np.int32)
+    labels[:, cell_ids(H).reshape(-1)] = lab.reshape(C, -1)
+    return from_volume(owner != 0), labels.reshape(-1)
+
+
+def boxes_for(H):
+    """three cascades, a different pattern each, scaled by H (a multiple of 32):
+    0  slabs two cells thick every fourth z-plane, over all of x and y: H/4 components, and a 16 x 16 x 8 brick of cells (one
+       block of the statistics and the cull) holds nothing but the cells of two of them.  The plane z = H - 1 touches no slab: it
+       carries single cells at period 16 in x and 8 in y
+    1  3x3x3 cubes at period 8 from coordinate 1, so that each lies across a 2x2x2 block boundary on every axis: (H/8)^3
+       components.  Two of them are longer along z (4 and 5 cells), so that one of 27 cells is not the largest
+    2  the half x < H/2 as one box, and single cells at period 16 in the other half: one large root and many of one cell
+    The single cells of cascade 0 and the two longer cubes are there for min_cells = 28: without them that rule would cull
+    nothing in cascade 0 and everything in cascade 1."""
+    assert H % 32 == 0
+    out = [(0, (0, 0, z), (H, H, z + 2)) for z in range(0, H, 4)]
+    out += [(0, (x, y, H - 1), (x + 1, y + 1, H)) for x in range(5, H, 16) for y in range(3, H, 8)]
+    for x in range(1, H, 8):
+        for y in range(1, H, 8):
+            for z in range(1, H, 8):
+                tall = {(9, 17, 1): 4, (17, 9, 9): 5}.get((x, y, z), 3)
+                out.append((1, (x, y, z), (x + 3, y + 3, z + tall)))
+    out.append((2, (0, 0, 0), (H // 2, H, H)))
+    out += [(2, (x, y, z), (x + 1, y + 1, z + 1)) for x in range(H // 2 + 8, H, 16) for y in range(8, H, 16) for z in range(8, H, 16)]
+    return out
+
+
+BOX_RULES = (dict(keep_largest=1), dict(min_cells=28))     # and min_cells = H^3 + 1, which keeps nothing
+
+
+@functools.lru_cache(maxsize=None)
+def box_reference(H):
+    """computed once per H and shared read-only: (bitfield, labels, stats) of box_case(3, H, boxes_for(H))"""
+    bits, labels = box_case(3, H, boxes_for(H))
+    stats = component_stats(labels, 3, H)
+    for a in (bits, labels) + tuple(stats.values()):
+        a.setflags(write=False)
+    return bits, labels, stats
+
+
+def brick_roots(labels, brick_bytes):
+    """the number of distinct roots among the cells of every run of brick_bytes bitfield bytes"""
+    labels = np.asarray(labels, np.int64).reshape(-1, brick_bytes * 8)
+    return np.asarray([np.unique(row[row >= 0]).size for row in labels])
+
+
 # the 30 % fills: the seeds were chosen on the CPU so that every cascade has at least 20 components and one component reaches over
 # more than one 2x2x2 block on every axis (tests/test_occ_cull_cpu.py asserts both)
 RANDOM_16_SEED = 3
+# cascades 2..7 of eight_cascades_8 and the four of four_cascades_8: chosen on the CPU so that keep_largest = 1 culls a different
+# number of cells in every one of these cascades (tests/test_occ_cull_cpu.py asserts it)
+EIGHT_CASCADES_SEEDS = (21, 22, 23, 24, 25, 26)
+FOUR_CASCADES_SEEDS = (31, 32, 33, 34)
 
 
 def hand_cells():
@@ -273,6 +367,11 @@ def cases():
     for i in range(0, 16, 2):
         vol[2, i:i + 2, i:i + 2, i:i + 2] = True
     out['three_patterns_16x3'] = (3, 16, from_volume(vol))
+    # H = 8: a cascade is 64 bytes, one wave, and a block of 256 threads spans four cascades.  Cascade 0 empty, cascade 1 full
+    out['eight_cascades_8'] = (8, 8, np.concatenate([np.zeros(64, np.uint8), np.full(64, 0xFF, np.uint8)] +
+                                                    [random_fill(1, 8, 0.3, s) for s in EIGHT_CASCADES_SEEDS]))
+    out['four_cascades_8'] = (4, 8, np.concatenate([random_fill(1, 8, 0.3, s) for s in FOUR_CASCADES_SEEDS]))      # one block exactly
+    out['checkerboard_16'] = (1, 16, checkerboard(16))                          # 1024 roots in each 2048-cell brick
     for _, _, b in out.values():
         b.setflags(write=False)
     return out

@@ -153,6 +153,117 @@ def test_the_named_cases_are_what_the_issue_asks_for():
     assert R.roots(R.reference('first_and_last_8')[0]).tolist() == [0, 511]
 
 
+def _n_culled(name, **rule):
+    C, H, bits = R.cases()[name]
+    labels, stats = R.reference(name)
+    return R.cull(None, bits, labels, R.keep_rule(labels, stats, C, H, R.BOUND, **rule), C, H)[2].tolist()
+
+
+def test_cascades_that_share_a_block_cull_different_counts():
+    """H = 8: a cascade is one wave of the cull, a block spans four.  A count that lands in the wrong cascade must show"""
+    C, H, bits = R.cases()['eight_cascades_8']
+    assert (C, H) == (8, 8) and not bits[:64].any() and (bits[64:128] == 0xFF).all()
+    n = _n_culled('eight_cascades_8', keep_largest=1)
+    assert len(set(n)) > 1 and len(set(n)) >= 6, n
+    assert n[0] == n[1] == 0 and len(set(n[2:])) == 6 and min(n[2:]) > 0, n    # nothing to cull in the empty and the full cascade
+    C, H, bits = R.cases()['four_cascades_8']
+    assert (C, H) == (4, 8) and bits.size == _kernel_constant('OC_BLOCK')      # one block exactly
+    n = _n_culled('four_cascades_8', keep_largest=1)
+    assert len(set(n)) == 4 and min(n) > 0, n
+
+
+def _kernel_constant(name):
+    src = open(os.path.join(ROOT, 'nerfstyle_amd', 'csrc', 'occ_components.hip')).read()
+    found = re.findall(r'^#define\s+' + name + r'\s+(\d+)u?\b', src, re.M)
+    assert len(found) == 1, (name, found)
+    return int(found[0])
+
+
+def test_roots_per_brick_overflow_the_statistics_table_or_fill_one_slot():
+    """a block of the statistics gathers the roots of OC_BLOCK bytes, one brick, in OC_SLOTS slots of LDS; a root past them goes
+    to global memory directly, and a root may reach its totals both ways.  The constants are read from the kernel's source: with
+    other values these cases may no longer do what this test says they do"""
+    slots, block = _kernel_constant('OC_SLOTS'), _kernel_constant('OC_BLOCK')
+    assert (slots, block, _kernel_constant('OC_PROBES')) == (128, 256, 4)
+    per_brick = {name: R.brick_roots(R.reference(name)[0], block) for name in ('checkerboard_16', 'random_16x2', 'full_32x2')}
+    assert per_brick['checkerboard_16'].tolist() == [block * 8 // 2] * 2       # every occupied cell its own root: the most a block can meet
+    assert per_brick['checkerboard_16'].max() > slots and per_brick['random_16x2'].max() > slots
+    assert (per_brick['full_32x2'] == 1).all() and per_brick['full_32x2'].size == 32
+    labels, stats = R.reference('checkerboard_16')
+    occ = R.occupied(R.cases()['checkerboard_16'][2], 1, 16)
+    assert np.array_equal(R.roots(labels), np.flatnonzero(occ)) and (stats['n_cells'][occ] == 1).all()
+
+
+# ---- the closed form for large grids ------------------------------------------------------------------------------------------
+def test_box_case_equals_both_restatements_at_32():
+    C, H = 3, 32
+    bits, labels, stats = R.box_reference(H)
+    assert labels.dtype == np.int32 and labels.shape == (C * H ** 3,) and bits.shape == (C * H ** 3 // 8,)
+    assert np.array_equal(labels, R.labels_propagation(bits, C, H))
+    assert np.array_equal(labels, R.labels_union_find(bits, C, H))
+    rts = R.roots(labels)
+    assert [int((rts // H ** 3 == c).sum()) for c in range(C)] == [H // 4 + (H // 16) * (H // 8), (H // 8) ** 3, 1 + (H // 32) * (H // 16) ** 2]
+    r = H ** 3 + int(R.morton(9, 17, 1))                                        # one of the two longer cubes of cascade 1
+    assert stats['n_cells'][r] == 36 and stats['lo'][r].tolist() == [9, 17, 1] and stats['hi'][r].tolist() == [11, 19, 4]
+    assert stats['n_cells'][0] == 2 * H * H and stats['n_cells'][2 * H ** 3] == H ** 3 // 2
+
+
+def test_box_case_refuses_boxes_that_touch_or_overlap():
+    R.box_case(1, 8, [(0, (0, 0, 0), (2, 2, 2)), (0, (3, 0, 0), (4, 2, 2)), (0, (2, 2, 2), (3, 3, 3))])       # a gap; a corner only
+    for other in ((2, 0, 0), (0, 2, 1), (1, 1, 2), (1, 1, 1)):                  # a face along x, y, z; an overlap
+        with pytest.raises(AssertionError):
+            R.box_case(1, 8, [(0, (0, 0, 0), (2, 2, 2)), (0, other, tuple(v + 2 for v in other))])
+    bits, labels = R.box_case(2, 8, [(0, (7, 0, 0), (8, 8, 1)), (1, (0, 0, 0), (1, 8, 1))])                  # cascades never touch
+    assert np.array_equal(labels, R.labels_propagation(bits, 2, 8))
+
+
+@pytest.mark.parametrize('H', (32, 128))
+def test_box_layout_meets_the_conditions_of_the_large_gpu_case(H):
+    """on the reference alone: what tests/test_gpu_occ_cull_edges.py::test_past_the_grid_cap relies on"""
+    C = 3
+    bits, labels, stats = R.box_reference(H)
+    assert len(R.roots(labels)) == len(R.boxes_for(H)) <= 10000
+    if H == 128:
+        assert bits.size > 2048 * _kernel_constant('OC_BLOCK')                  # the grids are capped at 2048 blocks: a second trip
+        assert bits.size - 2048 * 256 == bits.size // C                         # ... which is cascade 2, from blocks that began in cascade 0
+    per_cascade = R.occupied(bits, C, H).reshape(C, -1).sum(1)
+    for rule in R.BOX_RULES:
+        keep = R.keep_rule(labels, stats, C, H, R.BOUND, **rule)
+        _, _, n = R.cull(None, bits, labels, keep, C, H)
+        assert ((n > 0) & (n < per_cascade)).all(), (rule, n)                   # every cascade culls something and keeps something
+        assert len(set(n.tolist())) == C, (rule, n)
+    keep = R.keep_rule(labels, stats, C, H, R.BOUND, min_cells=H ** 3 + 1)
+    assert not keep.any() and np.array_equal(R.cull(None, bits, labels, keep, C, H)[2], per_cascade)
+
+
+# ---- labels that are not this grid's ------------------------------------------------------------------------------------------
+def test_foreign_labels_count_as_unoccupied_and_are_never_culled():
+    C, H, cells_list = R.hand_cells()['L_shape']
+    bits = R.cases()['L_shape'][2]
+    labels, stats = R.reference('L_shape')
+    cells = C * H ** 3
+    ids = [_id(H, *c) for c in cells_list]
+    r = min(ids[:6])
+    for foreign in (cells, cells + 7, 0x7fffffff, -2):
+        lab = np.array(labels)
+        lab[ids[3]] = foreign                                                  # (4, 2, 3): the corner of the L
+        lab[ids[6]] = foreign                                                  # the single cell, a root
+        assert R.own_labels(lab, C, H).sum() == 5
+        s = R.component_stats(lab, C, H)
+        assert s['n_cells'][r] == 5 and s['lo'][r].tolist() == [1, 2, 3] and s['hi'][r].tolist() == [4, 4, 3]
+        assert s['n_cells'].sum() == 5 and s['n_cells'][ids[6]] == 0 and s['lo'][ids[6]].tolist() == [H] * 3
+        grid = np.arange(cells, dtype=np.uint32)
+        out, out_bits, n = R.cull(grid, bits, lab, np.zeros(cells, np.uint8), C, H)          # keep nothing
+        left = np.flatnonzero(R.occupied(out_bits, C, H)).tolist()
+        assert left == sorted([ids[3], ids[6]]) and n.tolist() == [5]
+        assert (out[[i for i in ids if i not in left]] == 0xBF800000).all() and np.array_equal(out[left], grid[left])
+    lab = np.array(labels)
+    lab[ids[1]] = -1                                                           # -1 on an occupied cell is no label either
+    assert R.cull(None, bits, lab, np.zeros(cells, np.uint8), C, H)[2].tolist() == [6]
+    # with labels of its own grid the filter changes nothing
+    assert np.array_equal(R.own_labels(labels, C, H), labels >= 0)
+
+
 # ---- the kernels' edge enumeration and union-find from many host threads ------------------------------------------------------
 def test_labelling_core_from_sixteen_host_threads(tmp_path):
     cxx = next((c for c in (os.environ.get('CXX'), 'c++', 'g++', 'clang++') if c and shutil.which(c)), None)
