@@ -1162,6 +1162,55 @@ int nsr_reproject_frames(const float *rgb, const float *dist, const float *poses
                          float cx, float cy, int camera_flip, const int32_t *pairs, uint32_t P, double depth_tol, float *warped,
                          uint8_t *mask, double *stats, void *workspace, nsr_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Style image clustering: Lloyd k-means over pixel rows in colour plus weighted position (csrc/kmeans.hip, csrc/km_core.h;
+ * nerfstyle_amd/segment.py).  It makes the cluster map of a style image that SemanticStyleLoss(clusters=...) and the region-wise
+ * colour transfer above take.  Additive: the ABI version stays.
+ *
+ * rows: n rows of `stride` f32, stride 3 or 4, read in place, 4-byte aligned (16 with stride 4); the fourth float is never read.
+ * H, W >= 1 with n a multiple of H*W (a stack of n / (H*W) frames): row i has x = i % W, y = (i / W) % H.  n <= 2^27.
+ * Feature: f = (r, g, b, wxy * x / m, wxy * y / m), m = max(H, W), the position terms formed in fp64 as (wxy * x) / m;
+ *   0 <= wxy <= 8, wxy = 0 clusters colour alone.  A row is UNLABELLED (label -1, it contributes to nothing) if any of r, g, b is
+ *   NaN, infinite or outside [-8, 8]; so |f_j| <= 8.
+ * Assignment: centroids [K][5] fp64 in device memory, 1 <= K <= NSR_COLOR_MAX_REGIONS.  t_j = f_j - c_kj,
+ *   d_k = ((((t0 t0 + t1 t1) + t2 t2) + t3 t3) + t4 t4) in fp64, every operation rounded on its own (nothing contracted).  The
+ *   label starts as 0 and becomes k, for k = 1 .. K-1 in turn, when d_k < d_label: the smallest distance, the lowest k among
+ *   equals.  (Centroids are expected to be finite; a NaN distance never wins that comparison.)
+ * Sums are integers: counts[k] = the rows labelled k, sums[k][j] = sum over them of llrint(f_j * 2^32) (exact product, round to
+ *   nearest even), both int64.  |sum| <= 2^27 * 2^35 = 2^62.  Integer addition has no order: whichever mix of wave butterflies,
+ *   LDS atomics and per-block partials ran, the result is the same, and a NumPy restatement reproduces it exactly.
+ * Update: centroids_out[k][j] = (double)sums[k][j] / 4294967296.0 / (double)counts[k]; a cluster with count 0 keeps
+ *   centroids[k].  centroids_out may be NULL (no update) or `centroids` itself.
+ * stats [2] fp64: stats[0] = the number of rows i with labels[i] != prev_labels[i] (exact; every one of the n rows when prev_labels
+ *   is NULL; an unlabelled row that stays unlabelled has not changed), stats[1] = the inertia, the sum of d_label(i) over the
+ *   labelled rows, added in fp64 in a fixed order without atomics: per thread in the order of its rows, the block sum of
+ *   csrc/fixed_sum.h, one partial per block, then thread t of one block adds partials t, t + 256, ... and the block sum again.  The
+ *   order depends on n, stride and, for stride 3, on the rows' offset from a 16-byte boundary, nothing else: two calls give the
+ *   same bits.  prev_labels may be `labels` itself (a row's label is read and written by one thread).
+ * workspace: the _workspace_bytes query of the same name gives its size in bytes (0 for arguments the call refuses), 8-byte
+ *   aligned.  No host read, no allocation: legal inside a stream capture.
+ *
+ * Maximin init.  Candidates are rows j * s, s = ceil(n / 65536); unlabelled candidates are skipped.  Centre 0 is the candidate
+ *   with the smallest d to `mean` [5] (device fp64; segment.py passes the centroid that one step with K = 1 gives: the
+ *   fixed-point mean of all labelled rows); centre r the candidate with the largest distance to its nearest centre among 0 .. r-1;
+ *   equal distances: the lowest row index; a chosen candidate is not chosen again.  Distances as d above.  centroids [K][5] gets
+ *   the chosen rows' features (fp64, not quantised), chosen_rows [K] int32 their row indices, n_labelled [1] uint32 the number of
+ *   labelled candidates.  With fewer labelled candidates than K the remaining centres repeat the last one chosen (`mean` if
+ *   none) with chosen_rows = -1; the caller reads n_labelled to refuse that case.
+ *   workspace: its _workspace_bytes query, 8-byte aligned.  One block; no host read.
+ *
+ * NSR_ERR_INVALID_ARG before any launch: n = 0 or n > 2^27, stride outside {3, 4}, K = 0 or K > NSR_COLOR_MAX_REGIONS, H or W
+ * zero or n not a multiple of H*W, xy_weight outside [0, 8] or NaN, a NULL pointer other than prev_labels and centroids_out, a
+ * misaligned pointer.
+ * ------------------------------------------------------------------------------------------ */
+uint64_t nsr_kmeans_step_workspace_bytes(uint64_t n, uint32_t K);
+int nsr_kmeans_step(const float *rows, uint64_t n, uint32_t stride, uint32_t H, uint32_t W, double xy_weight, const double *centroids,
+                    uint32_t K, const int32_t *prev_labels, int32_t *labels, int64_t *counts, int64_t *sums, double *centroids_out,
+                    double *stats, void *workspace, nsr_stream_t stream);
+uint64_t nsr_kmeans_init_workspace_bytes(uint64_t n);
+int nsr_kmeans_init(const float *rows, uint64_t n, uint32_t stride, uint32_t H, uint32_t W, double xy_weight, const double *mean,
+                    uint32_t K, double *centroids, int32_t *chosen_rows, uint32_t *n_labelled, void *workspace, nsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,10 @@ SIGNATURES = {
     'nsr_occ_cull': (i32, [vp, vp, vp, vp, u32, u32, vp, vp]),
     'nsr_reproject_frames_workspace_bytes': (u64, [u32, u32, u32]),
     'nsr_reproject_frames': (i32, [vp, vp, vp, u32, u32, u32, f32, f32, f32, f32, i32, vp, u32, f64, vp, vp, vp, vp, vp]),
+    'nsr_kmeans_step_workspace_bytes': (u64, [u64, u32]),
+    'nsr_kmeans_step': (i32, [vp, u64, u32, u32, u32, f64, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'nsr_kmeans_init_workspace_bytes': (u64, [u64]),
+    'nsr_kmeans_init': (i32, [vp, u64, u32, u32, u32, f64, vp, u32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -14,14 +14,16 @@ OBJ = os.path.join(HERE, 'csrc', '_obj')
 LIB = os.path.join(HERE, 'libnsr_hip.so')
 ARCH = 'gfx950'
 SOURCES = ['raymarch.hip', 'raymarch_infer.hip', 'ray_util.hip', 'frame_batch.hip', 'lens.hip', 'error_map.hip', 'composite.hip', 'occupancy.hip', 'occ_untrained.hip', 'sample_order.hip', 'gridenc.hip', 'grid_tv.hip', 'field.hip', 'field_normal.hip', 'field_xgrad.hip', 'render_infer.hip', 'field_bwd.hip', 'field_bwd_gout.hip', 'table_scatter.hip', 'mlp.hip',
-           'optim.hip', 'matting.hip', 'color_match.hip', 'color_regions.hip', 'ssim.hip', 'surface_nets.hip', 'mesh_clean.hip', 'occ_components.hip', 'reproject.hip']
+           'optim.hip', 'matting.hip', 'color_match.hip', 'color_regions.hip', 'ssim.hip', 'surface_nets.hip', 'mesh_clean.hip', 'occ_components.hip', 'reproject.hip', 'kmeans.hip']
 # MFMA destinations in VGPRs (no AGPR round trip for results that VALU code consumes next): the forwards, and the GOUT backward,
 # whose 240 weight-gradient accumulators are pinned to AGPRs by inline assembly instead (field_bwd_gout.hip)
 EXTRA_FLAGS = {'field.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'field_normal.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
                'render_infer.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
-               'field_bwd_gout.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form']}
-HEADERS = ['nsr_common.h', 'fixed_sum.h', 'color_common.h', 'seg_sum.h', 'rm_util.h', 'rm_probe.h', 'philox.h', 'ray_pose.h', 'table_scatter.h', 'lattice.h', 'mfma_tiles.h', 'field_common.h', 'field_bwd.h', 'block_scan.h', 'uf_core.h', 'occ_cc_core.h', 'reproject_core.h',
+               'field_bwd_gout.hip': ['-mllvm', '--amdgpu-mfma-vgpr-form'],
+               # every fp64 operation rounded on its own, as the host build of km_core.h and the NumPy restatement round it
+               'kmeans.hip': ['-ffp-contract=off']}
+HEADERS = ['nsr_common.h', 'fixed_sum.h', 'color_common.h', 'seg_sum.h', 'rm_util.h', 'rm_probe.h', 'philox.h', 'ray_pose.h', 'table_scatter.h', 'lattice.h', 'mfma_tiles.h', 'field_common.h', 'field_bwd.h', 'block_scan.h', 'uf_core.h', 'occ_cc_core.h', 'reproject_core.h', 'km_core.h',
            os.path.join('..', '..', 'include', 'nsr.h')]
 FLAGS = ['-O3', '-fPIC', '-std=c++17', '--offload-arch=' + ARCH, '-Wall', '-Wno-unused-function']
 

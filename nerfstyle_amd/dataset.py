@@ -91,11 +91,12 @@ class ResidentDataset:
             self._rgb_rows.copy_(self.targets[:, :, :3].reshape(-1, 3))
         return self.color_tf
 
-    def match_colors_by_region(self, style_image: torch.Tensor, style_clusters: torch.Tensor, matching, min_rows: int = 256,
+    def match_colors_by_region(self, style_image: torch.Tensor, style_clusters, matching, min_rows: int = 256,
                                fallback: str = 'global') -> torch.Tensor:
         """match_colors per scene class: the pixels of class i get the mean and covariance of cluster matching[i] of the style
         image, not the image's average palette.  style_image [3,H,W] f32 in [0,1]; style_clusters [H,W] integer, the cluster of
-        each style pixel (-1 = unlabelled); matching [num_classes] is the caller's (SemanticStyleLoss.matching, or a fixed list;
+        each style pixel (-1 = unlabelled), or an int K: the image is clustered first (segment.segment_style_image(style_image, K):
+        colour alone, 10 steps), with the same result as passing that map; matching [num_classes] is the caller's (SemanticStyleLoss.matching, or a fixed list;
         -1 = unmatched), it is not computed here.
 
         The class ids are read from the targets where they lie (the fourth float of every row, no label copy); the style side
@@ -111,6 +112,10 @@ class ResidentDataset:
             raise ValueError('match_colors_by_region: the dataset was built without segment maps')
         if style_image.dim() != 3 or style_image.shape[0] != 3:
             raise ValueError('match_colors_by_region: style_image must be [3,H,W]; got {}'.format(tuple(style_image.shape)))
+        if isinstance(style_clusters, int) and not isinstance(style_clusters, bool):
+            from .segment import segment_style_image
+            CM._rows(self.targets, 'match_colors_by_region')
+            style_clusters = segment_style_image(style_image, style_clusters, device=self.targets.device).labels
         if tuple(style_clusters.shape) != tuple(style_image.shape[1:]) or style_clusters.is_floating_point():
             raise ValueError('match_colors_by_region: style_clusters must be integer [H,W] of the style image {}; got {} {}'.format(
                 tuple(style_image.shape[1:]), style_clusters.dtype, tuple(style_clusters.shape)))
